@@ -6,8 +6,10 @@ host-side episode generation for finished envs) over one batch of 4096 envs per 
 actions already resident in HBM.  Workload at N=1 = BASELINE.json configs[1]: num_agents=2, batch=4096,
 96x96 RGB obs.  Multi-GPU: independent env slices (weak scaling), one scalar all-reduce at the end.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (view/raster kernel vs HBM) and `cpu_baseline`
-(the oracle = CPU restatement, timed on this host's cores on a bounded sample; N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline; --full adds
+`roofline` (view/raster kernel vs HBM, from HIP events around sampled raster launches in the timed region) and
+`cpu_baseline` (the oracle = CPU restatement, timed on this host's cores on a bounded sample; N=1 only).
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -82,6 +84,52 @@ def cpu_baseline(num_agents, obs):
                      {"value": vc, "unit": "env-steps/s", "cores": 1, "sample": f"BASELINE configs[0]: 1 env x {sc} steps, num_agents=1, use_random_direction=False, backwards_flag=False, obs=96x96x3, {dc:.1f} s"}]}
 
 
+def _env_sample(B, bytes_per_env, budget):
+    """every env when all of them fit in `budget` bytes, otherwise a fixed, seeded sample of envs (sorted) that does"""
+    import numpy as np
+    if B * bytes_per_env <= budget:
+        return np.arange(B)
+    return np.sort(np.random.RandomState(0).choice(B, max(1, budget // bytes_per_env), replace=False))
+
+
+def dump_outputs(venv, out_dir, rank=0, world=1):
+    """What the last step handed its caller — (obs, reward, done, info) of VecMultiCarRacing.step — as out_dir/<name>.npy in float32
+    (flags, pixels) or float64 (f64 rewards and returns, lengths): under 64 MB for any batch.  Per-env arrays hold every env while they
+    fit in 12 MB, obs up to 40 MB and terminal frames up to 8 MB; beyond that, seeded env samples (`*_envs` lists which).  With several
+    ranks each writes its own slice as <name>_rank<r>.npy within 1/world of those budgets."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    B, N = venv.B, venv.N
+    frame = 96 * 96 * 3
+    suffix = "_rank%d" % rank if world > 1 else ""
+    MB = 10 ** 6 // world
+
+    def save(name, t, dtype):
+        a = t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a.astype(dtype))
+    torch.cuda.synchronize(venv.device)
+    envs = _env_sample(B, 8 * (2 * N + 3), 12 * MB)
+    ix = torch.from_numpy(envs).to(venv.device)
+    save("step_envs", envs, np.float64)
+    save("reward", venv.reward[ix], np.float64)
+    save("done", venv.done[ix], np.float32)
+    save("truncated", venv.truncated[ix], np.float32)
+    save("episode_return", venv.episode_return[ix], np.float64)
+    save("episode_length", venv.episode_length[ix], np.float64)
+    if venv.obs is not None:
+        envs = _env_sample(B, 4 * N * frame, 40 * MB)
+        save("obs_envs", envs, np.float64)
+        save("obs", venv.obs[torch.from_numpy(envs).to(venv.device)], np.float32)
+    if venv.terminal_obs is not None:
+        # entries in env order (the kernels append them in whatever order the envs finish): the first that fit in 8 MB
+        k = int(venv.terminal_count.item())
+        ids = venv.terminal_env_ids[:k].long()
+        order = torch.argsort(ids)[:8 * MB // (4 * N * frame)]
+        save("terminal_env_ids", ids.sort().values, np.float64)
+        save("terminal_observation", venv.terminal_obs[:k][order], np.float32)
+
+
 def _free_port():
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
@@ -113,13 +161,17 @@ def main():
     ap.add_argument("--streams", type=int, default=2, help="2 (default): contact side stream (envs in car<->car contact run their chain concurrently); 1: single stream")
     ap.add_argument("--stagger", type=int, default=1, help="1: spread the TimeLimit phases of the envs uniformly before timing (steady state); 0: all envs expire in the same step")
     ap.add_argument("--debug-bits", type=int, default=0, help="mcr_debug_set value for timing experiments (results are WRONG when non-zero)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the raster roofline (HIP events in "
+                    "the timed region) and the CPU baseline (about 25 s of oracle runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned (obs, reward, "
+                    "done, info) as DIR/<name>.npy in float32/float64; obs as a fixed, seeded sample of envs (at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--time-all-kernels", action="store_true", help="HIP-event time all three kernels (adds overhead)")
     ap.add_argument("--action-seed", type=int, default=1234)
     ap.add_argument("--actions", choices=["random", "drive"], default="random", help="random (default): i.i.d. actions over the action space (BASELINE's random-action rollout); "
                     "drive: gas 1, brake 0, steering noise +-0.1 from the same counter-based stream — cars that actually drive off the grid, lap and collide "
                     "(what a competent policy's rollout looks like to the contact chain); reported with the contact-list length")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="do not bracket the raster launch with HIP events (no roofline object; lets --graph 1 replay)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: do not bracket the raster launch with HIP events (no roofline object; lets --graph 1 replay)")
     ap.add_argument("--emulate-world", type=int, default=0, help="W > 1: ONE GPU, but the host side of a W-rank job on this node: the process is pinned to 1/W of the "
                     "cores the cgroup allows and its track generator takes the threads VecMultiCarRacing gives a rank of a W-rank job; reports "
                     "env-steps/s, the time step() was blocked on the refill thread and the env-steps frozen waiting for the host")
@@ -244,11 +296,11 @@ def main():
     # consumed-episode poll inside env.step() sees the device-side auto-resets while the rollout is still running
     # and the replacement tracks are generated + staged by the refill thread INSIDE the timed region.
     LOOKAHEAD = 16
-    # Instrumentation is sampled: every HIP event costs the queue a few microseconds, so the raster launch is bracketed
+    # Instrumentation (--full) is sampled: every HIP event costs the queue a few microseconds, so the raster launch is bracketed
     # by timing events in every TIME_EVERY-th step only (the average over those launches is `roofline.avg_launch_ms`)
     # and the look-ahead fence is one event per LOOKAHEAD // 4 steps.
     TIME_EVERY = 8
-    tmask = 0 if args.no_kernel_timing else (255 if args.time_all_kernels else 4)
+    tmask = 0 if args.no_kernel_timing else (255 if args.time_all_kernels else (4 if args.full else 0))
     FENCE = LOOKAHEAD // 4
     evs = [torch.cuda.Event(blocking=True) for _ in range(4)]       # the host sleeps at the look-ahead fence instead of spinning on a core the refill thread needs
     thr0 = thread_cpu()
@@ -291,6 +343,8 @@ def main():
     generated = env.env.episodes_generated - gen0
     episodes, return_sum = env.env.rollout_stats()            # counted on the device: episodes that ended in the timed region
     m = reduce_metrics(B * K, elapsed, episodes=episodes, return_sum=return_sum)
+    if args.dump_outputs:
+        dump_outputs(env.env, args.dump_outputs, rank, world)
 
     # roofline of the dominant kernel (view raster): algorithmic bytes per env-step:
     #   N*27648 (obs write) + 36*P (road quads read once per env) + 76*N (car transforms+phases) + 48*N (camera+HUD)
@@ -359,7 +413,7 @@ def main():
             out["kernel_ms"] = {"collide": ms[0] / max(nl[0], 1), "dynamics": ms[1] / max(nl[1], 1), "view": ms[2] / max(nl[2], 1),
                                 "collide_reset_pass": ms[3] / max(nl[3], 1), "dynamics_reset_pass": ms[4] / max(nl[4], 1),
                                 "side_dynamics": ms[5] / max(nl[5], 1), "side_view": ms[6] / max(nl[6], 1), "side_reset_pass_kernel": ms[7] / max(nl[7], 1)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(N, bool(args.obs))
         line = json.dumps(out)
     env.close()

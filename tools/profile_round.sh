@@ -5,8 +5,9 @@ set -x
 export TMPDIR=/tmp
 R=${1:-r01}
 OUT=gpurun_out/prof_$R
+PROF=$(dirname $OUT)/profiles_$R
 mkdir -p $OUT gpurun_out/profiles_$R
-CMD="timeout 400 python bench.py --no-cpu-baseline"     # default workload/steps; the CPU baseline leg is not profiled
+CMD="timeout 400 python bench.py --full --no-cpu-baseline"     # default workload/steps with the roofline; the CPU baseline leg is not profiled
 $CMD > $OUT/bench_plain.json 2> $OUT/bench_plain.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $CMD > $OUT/bench_stats.json 2> $OUT/stats.err
 timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o p -- $CMD > /dev/null 2> $OUT/pmc_fetch.err
@@ -34,8 +35,8 @@ rm -rf gpurun_out/pmc_view
 # the other configurations of the DESIGN table (one bench line each)
 for cfg in "--streams 1" "--stagger 0" "--obs 0" "--agents 8" "--agents 1" "--agents 4" "--emulate-world 8" "--actions drive" "--envs 16384" "--envs 32768" "--rccl" "--terminal-obs 1"; do
   tag=$(echo $cfg | tr -d ' -')
-  timeout 400 python bench.py --no-cpu-baseline $cfg > gpurun_out/profiles_$R/bench_$tag.json 2> /dev/null
+  timeout 400 python bench.py --full --no-cpu-baseline $cfg > $PROF/bench_$tag.json 2> /dev/null
 done
-# the default command as the driver runs it (with the CPU baseline legs: BASELINE.json configs[1] sample and configs[0])
-timeout 600 python bench.py > gpurun_out/profiles_$R/bench_default.json 2> /dev/null
+# the default workload with everything --full measures (roofline and the CPU baseline legs: BASELINE.json configs[1] sample and configs[0])
+timeout 600 python bench.py --full > $PROF/bench_default.json 2> /dev/null
 ls -la gpurun_out/profiles_$R

@@ -11,7 +11,7 @@ R = sys.argv[1] if len(sys.argv) > 1 else "r01"
 src = f"gpurun_out/prof_{R}"
 os.makedirs("profiles", exist_ok=True)
 STEPS = 1000
-lines = [f"# {R}: rocprofv3 summary of `python bench.py --no-cpu-baseline` (default configuration: contact side stream on, 1000 timed steps after 64 warm-up steps and the steady-state pre-roll; B=4096, N=2, 1x MI355X)\n"]
+lines = [f"# {R}: rocprofv3 summary of `python bench.py --full --no-cpu-baseline` (default configuration: contact side stream on, 1000 timed steps after 64 warm-up steps and the steady-state pre-roll; B=4096, N=2, 1x MI355X)\n"]
 try:
     b = json.loads(open(f"{src}/bench_plain.json").read().strip().splitlines()[-1])
     lines.append("Un-profiled bench line of the same command:\n\n```json\n" + json.dumps(b) + "\n```\n")
