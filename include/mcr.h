@@ -31,6 +31,9 @@ extern "C" {
 #define MCR_OBS_H 96
 #define MCR_OBS_W 96
 #define MCR_MT_WORDS 625      /* MT19937 key[624] + pos — numpy RandomState layout */
+#define MCR_OBS_RGB 0         /* mcr_set_obs_format: 96x96x3 RGB frames (default) */
+#define MCR_OBS_GRAY 1        /* ... 96x96 luma frames, optionally stacked */
+#define MCR_OBS_STACK_MAX 8
 
 typedef struct mcr_env mcr_env; /* opaque */
 
@@ -116,11 +119,12 @@ int mcr_world_proxy_ids(const mcr_world* w, int32_t* out, int cap);
 int mcr_stage_episodes(mcr_env* h, const int32_t* env_ids, int n, const void* blobs, void* stream);
 /* reset() (:340-408): installs the staged episode for every env whose d_env_mask byte != 0 (NULL = all),
  * spawns the cars, runs the no-action step of :408 and writes the first observation.
- * d_obs: [B,N,96,96,3] u8 or NULL. */
+ * d_obs: [B,N,96,96,3] u8 or NULL; with mcr_set_obs_format the layout that call describes. */
 int mcr_reset(mcr_env* h, const uint8_t* d_env_mask, uint8_t* d_obs, void* stream);
 /* step() (:410-509) for all B envs.
  *   d_actions  [B,N,3] f32 (steer,gas,brake), NULL = the action-less step of :408
- *   d_obs      [B,N,96,96,3] u8 or NULL (ignored when obs_enabled == 0)
+ *   d_obs      [B,N,96,96,3] u8 or NULL (ignored when obs_enabled == 0); gray: [B,N,96,96] (k = 1) or the ring [B,N,2k,96,96] (k > 1,
+ *              mcr_set_obs_format), which must not be NULL
  *   d_reward   [B,N] f64 step_reward (:443,:507)
  *   d_done     [B] u8   (:498-499, :503-506, TimeLimit)
  *   d_trunc    [B] u8 or NULL: info['TimeLimit.truncated']
@@ -138,12 +142,28 @@ int mcr_set_episode_stats(mcr_env* h, double* d_ep_return, int32_t* d_ep_len);
 /* Terminal observations (what a baselines / SB3-style VecEnv hands out as info["terminal_observation"]).  The reference renders
  * the state AFTER the last solve of an episode and returns it with done = True (multi_car_racing.py:431, :509; TimeLimit: __init__.py:8); with
  * auto_reset the env's row of d_obs already shows the first observation of the next episode.  With this set, every step that ends an env's
- * episode and re-spawns it also draws that last frame: entry i = env d_term_ids[i], frames d_term_obs[i] [N,96,96,3]; *d_term_count = the
+ * episode and re-spawns it also draws that last frame: entry i = env d_term_ids[i], frames d_term_obs[i] [N,96,96,3] (gray: [N,96,96], or with
+ * k > 1 [N,k,96,96] — the previous k - 1 frames of the episode, then its last one, what a stacked VecEnv hands out); *d_term_count = the
  * number of entries of the last completed step (0 when no episode ended), at most `cap` — episodes that end beyond `cap` in one step get no
  * entry (cap = num_envs never drops one).  The three buffers are the caller's device memory, overwritten by every mcr_step with actions and
  * valid once that step is complete on its stream.  An env that ends while the host has not staged its next episode FREEZES instead of being
  * re-spawned (mcr_debug_read_counters [3]) and gets no entry.  All NULL: off.  Synchronises the device (allocates the entries' state). */
 int mcr_set_terminal_obs(mcr_env* h, uint8_t* d_term_obs, int32_t* d_term_ids, int32_t* d_term_count, int cap);
+/* Observation format (gym's GrayScaleObservation + FrameStack(k), drawn by the raster itself).  format MCR_OBS_RGB (stack 1) or MCR_OBS_GRAY
+ * with stack k = 1 .. MCR_OBS_STACK_MAX.  A gray pixel is (4899 R + 9617 G + 1868 B + 8192) >> 14 of the RGB bytes the RGB format would
+ * store (OpenCV's COLOR_RGB2GRAY on 8-bit data), HUD included.  Per view d_obs then holds one 96x96 frame (k = 1) or a RING of 2k frames
+ * (k > 1): drawing step d (an mcr_step with d_obs, counted from the handle's creation) writes its frame into slots j = d mod k and j + k;
+ * after it the observation is slots j + 1 .. j + k, oldest first, contiguous per view (mcr_obs_window) — no frame is ever shifted.  A reset
+ * or re-spawn writes the env's first frame into slots j .. j + k (j: the head of the last drawing step); the observation is then that
+ * frame k times, as gym's FrameStack does (SB3's VecFrameStack zero-fills instead).  The format shapes the terminal entries, so it is set
+ * before mcr_set_terminal_obs, and before the first mcr_reset (MCR_ERR_STATE otherwise, and with obs_enabled == 0);
+ * MCR_ERR_ARG for a NULL handle, a bad format or stack, or RGB with stack > 1.  With k > 1 every mcr_step must pass d_obs (MCR_ERR_ARG
+ * otherwise: a step that skipped its draw would leave a hole in the ring), and episodes must last at least k steps (max_episode_steps). */
+int mcr_set_obs_format(mcr_env* h, int format, int stack);
+/* bytes of d_obs per view: 27,648 (RGB), 9,216 (gray, k = 1), 2k x 9,216 (gray, k > 1) */
+size_t mcr_obs_bytes_per_view(const mcr_env* h);
+/* the first ring slot of the observation after the last ENQUEUED drawing step (k > 1: 1 .. k; k = 1 and RGB: 0) */
+int mcr_obs_window(const mcr_env* h);
 /* Rollout statistics accumulated on the device since creation / the last reset of the counters (synchronises):
  * out2[0] = episodes finished, out2[1] = sum of their returns over all agents.  These are the per-rank inputs of the
  * job-wide metric all-reduce. */

@@ -9,6 +9,7 @@ MAX_AGENTS = 8
 TILE_CAP = 512
 QUAD_CAP = 768
 MT_WORDS = 625
+OBS_RGB, OBS_GRAY, OBS_STACK_MAX = 0, 1, 8
 
 _vp, _i, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
 
@@ -60,6 +61,9 @@ SYMBOLS = {
     "mcr_debug_read_view_scratch": (_i, [_vp, _i, _vp, _i]),
     "mcr_set_episode_stats": (_i, [_vp, _vp, _vp]),
     "mcr_set_terminal_obs": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "mcr_set_obs_format": (_i, [_vp, _i, _i]),
+    "mcr_obs_bytes_per_view": (ctypes.c_size_t, [_vp]),
+    "mcr_obs_window": (_i, [_vp]),
     "mcr_read_rollout_stats": (_i, [_vp, _vp, _i]),
     "mcr_render": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mcr_debug_read_contact_counts": (_i, [_vp, _vp]),

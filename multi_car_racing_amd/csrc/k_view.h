@@ -156,13 +156,54 @@ __device__ __forceinline__ HudState hud_prep(const float* __restrict__ vr, const
   H.lvalid = cg == 0 ? 0xeu : cg < 4 ? 0xfu : cg == 4 ? 0x1u : 0u;
   return H;
 }
-__device__ __forceinline__ void hud_store(const HudState& H, uint32_t* __restrict__ frame, const int lane, const bool flag_on) {
+// GRAY: the colour classes of my 4 pixels in GL row `row` (= 2k + rsel): black bar (:638-642), gauges, then label and flag in GL rows 4..7.
+// The same lines as the RGB trip of hud_store, which keeps its own copy: routed through this function the RGB instantiations' instructions
+// come out scheduled differently, and their code is to stay what it was.
+__device__ __forceinline__ uint32_t hud_classes(const HudState& H, const int k, const int row, const int cg, const bool flag_on) {
+  uint32_t win = 0u;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const uint32_t cls = i == 0 ? 0x01010101u : i <= 2 ? 0x02020202u : i <= 4 ? 0x03030303u : i == 5 ? 0x04040404u : 0x05050505u;
+    const uint32_t m = H.xm[i] & (uint32_t)__builtin_amdgcn_sbfe((int)H.rm[i], row, 1);  // all ones iff the gauge holds my row
+    win = (win & ~m) | (cls & m);
+  }
+  if (k == 2 || k == 3) {                                                  // GL rows 4..7: label, then flag
+    const int r4 = row - 4;
+    uint32_t nib = cg == 0 ? ((uint32_t)(H.lmask >> (r4 * 16)) << 1) : (uint32_t)(H.lmask >> (r4 * 16 + 4 * min(cg, 4) - 1));
+    nib &= H.lvalid;
+    const uint32_t lm = ((nib * 0x00204081u) & 0x01010101u) * 0xffu;
+    win = (win & ~lm) | (0x01010101u & lm);
+    if (flag_on) {
+      const uint32_t fm = hud_flag_mask(cg, r4);
+      win = (win & ~fm) | (0x02020202u & fm);
+    }
+  }
+  return win;
+}
+// GRAY frames (include/mcr.h: mcr_set_obs_format): the fixed-point BT.601 luma of OpenCV's COLOR_RGB2GRAY on 8-bit data (what gym's
+// GrayScaleObservation calls), of the very bytes the RGB frame would hold.  A key word holds R in its low byte.
+__host__ __device__ constexpr uint32_t luma(uint32_t r, uint32_t g, uint32_t b) { return (4899u * r + 9617u * g + 1868u * b + 8192u) >> 14; }
+__device__ __forceinline__ uint32_t luma_key(uint32_t c) { return luma(c & 255u, (c >> 8) & 255u, (c >> 16) & 255u); }
+// the HUD's colour classes as gray bytes for one byte permute: classes 0..3 from the low word, 4 and 5 from the high one
+constexpr uint32_t HUD_GRAY_LO = luma(0, 0, 0) | luma(255, 255, 255) << 8 | luma(0, 0, 255) << 16 | luma(51, 0, 255) << 24;
+constexpr uint32_t HUD_GRAY_HI = luma(0, 255, 0) | luma(255, 0, 0) << 8;
+constexpr int GRAY_FRAME_WORDS = 96 * 96 / 4;
+// GRAY: the frame is stored `ns` times, `sstride` words apart (the ring slots of include/mcr.h; RGB: once)
+template <bool GRAY = false>
+__device__ __forceinline__ void hud_store(const HudState& H, uint32_t* __restrict__ frame, const int lane, const bool flag_on, const int ns = 1, const int sstride = 0) {
   if (lane >= 48) return;
   const int cg = H.cg, rsel = H.rsel;
   typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 #pragma unroll
   for (int k = 0; k < HUD_ROWS / 2; ++k) {
     const int row = 2 * k + rsel;
+    if constexpr (GRAY) {
+      const uint32_t win = hud_classes(H, k, row, cg, flag_on);
+      const uint32_t g4 = __builtin_amdgcn_perm(HUD_GRAY_HI, HUD_GRAY_LO, win);
+      uint32_t* o = frame + (95 - row) * 24 + cg;
+      for (int q = 0; q < ns; ++q, o += sstride) __builtin_nontemporal_store(g4, o);
+      continue;
+    }
     u32x3 wv; wv.x = wv.y = wv.z = 0u;                                       // black bar (:638-642)
     {                                                                        // (no "nothing is drawn in these two rows" shortcut: the six trips are
       uint32_t win = 0u;                                                     // independent dependency chains that the scheduler interleaves — branches between them would stop it)
@@ -205,8 +246,11 @@ __device__ __forceinline__ void hud_store(const HudState& H, uint32_t* __restric
 // requested a view ahead, the three dependent round trips to HBM of a workgroup's first view are paid once per workgroup instead of once
 // per env —: every view then costs what the FIRST view of a workgroup costs here (it carries the next view's block list and fetch), and
 // the launch ends with a tail of one env's time (20 us of 80): 102 us instead of 81.  NOTES.md.)
-template <bool PHASES, bool LIST>
-__global__ __launch_bounds__(VIEW_THREADS, LIST ? 3 : 4) void k_view(McrParams p, unsigned long long* __restrict__ stamps, const int only_just_reset) {
+// GRAY (include/mcr.h: mcr_set_obs_format): luma frames instead of RGB ones, into the view's ring of 2k frames (k > 1) — `ring` says
+// where; the RGB instantiations never read it.
+template <bool PHASES, bool LIST, bool GRAY = false>
+__global__ __launch_bounds__(VIEW_THREADS, LIST ? 3 : 4) void k_view(McrParams p, unsigned long long* __restrict__ stamps, const int only_just_reset,
+                                                                    const McrObsRing ring) {
   using namespace view;
   constexpr bool PERSIST = LIST;
   const int tid = threadIdx.x;
@@ -309,7 +353,15 @@ __global__ __launch_bounds__(VIEW_THREADS, LIST ? 3 : 4) void k_view(McrParams p
   auto vp_of = [&](int t) -> const float* { return (LIST && t) ? p.term_viewp : p.viewp; };
   auto cp_of = [&](int t) -> const float* { return (LIST && t) ? p.term_carpoly : p.carpoly; };
   auto tf_of = [&](int t) -> const uint16_t* { return (LIST && t) ? p.term_tflags : p.tile_flags; };
-  auto ob_of = [&](int t) -> uint8_t* { return (LIST && t) ? p.term_obs : p.obs; };
+  // Every frame address goes through ob_of: frame `s` of view `vw` of the live buffer or of the terminal entries.  RGB: one frame per view.
+  // GRAY: a terminal entry holds k frames (oldest first), a live view k = 1 frame or its ring of 2k
+  auto ob_of = [&](int t, int vw, int s) -> uint8_t* {
+    if constexpr (!GRAY) return ((LIST && t) ? p.term_obs : p.obs) + (size_t)vw * (96 * 96 * 3);
+    else {
+      const int per_view = (LIST && t) ? ring.k : (ring.k > 1 ? 2 * ring.k : 1);
+      return ((LIST && t) ? p.term_obs : p.obs) + ((size_t)vw * per_view + s) * (96 * 96);
+    }
+  };
   // what a candidate needs from HBM, requested one round ahead: a quad's 4 vertices + meta word, or 4 vertices of a Car.draw polygon +
   // its vertex count (the 8-gon's two slots fetch vertices 0..3 and 4..7)
   struct Raw { float4 a, b; uint32_t m; };
@@ -453,6 +505,18 @@ __global__ __launch_bounds__(VIEW_THREADS, LIST ? 3 : 4) void k_view(McrParams p
   for (int agent = a_lo; agent < a_hi; ++agent, ++vs) {
     const int vw = env * N + agent;
     const int buf = vs & 1;
+    // GRAY: the frame goes to `gns` slots from `gs0` on, `gds` apart — a terminal entry's last frame; the one frame of k = 1; slots j and
+    // j + k of the ring; a first frame (reset, re-spawn, thaw: the env's just_reset) to slots j .. j + k
+    // (gpend: the view's fresh byte, read here — every wavefront passes a barrier of the span fill before thread 0 rewrites it)
+    int gs0 = 0, gns = 1, gds = 1, gpend = 0; bool gfresh = false;
+    if constexpr (GRAY) {
+      if (LIST && term) gs0 = ring.k - 1;
+      else if (ring.k > 1) {
+        gfresh = UNI(p.env[env].just_reset) != 0;
+        gpend = UNI((int)ring.fresh[vw]);
+        gs0 = ring.j; gns = gfresh ? ring.k + 1 : 2; gds = gfresh ? 1 : ring.k;
+      }
+    }
     const float* __restrict__ vr = vrec[buf];
     // the view after this one: the env's next agent, or agent 0 of the workgroup's next env
     const bool last = agent + 1 == a_hi;
@@ -497,7 +561,8 @@ __global__ __launch_bounds__(VIEW_THREADS, LIST ? 3 : 4) void k_view(McrParams p
       const bool hud_flag = (__float_as_uint(vr[VP_OLDFLAGS]) & 1u) != 0u && p.backwards_flag != 0;
       const HudState hud = hud_prep(vr, glyphs, ll, hud_flag);
       if (nv_ok) lb_finish(lbr, buf ^ 1, ll);
-      if (!(dbg & 8)) hud_store(hud, (uint32_t*)(ob_of(term) + (size_t)vw * (96 * 96 * 3)), ll, hud_flag);
+      if constexpr (GRAY) { if (!(dbg & 8)) hud_store<true>(hud, (uint32_t*)ob_of(term, vw, gs0), ll, hud_flag, gns, gds * GRAY_FRAME_WORDS); }
+      else if (!(dbg & 8)) hud_store(hud, (uint32_t*)ob_of(term, vw, 0), ll, hud_flag);
       __builtin_amdgcn_s_setprio(LIST ? 3 : 0);
     }
     const Layout L = layout_of(buf);
@@ -706,8 +771,57 @@ __global__ __launch_bounds__(VIEW_THREADS, LIST ? 3 : 4) void k_view(McrParams p
       } while (t0 < total);
     }
     // ---- resolve + packed RGB write-out of the scene rows: 4 pixels -> 12 bytes per ll, rows top-down (arr[::-1], :602)
-    if (!(dbg & 8)) {
-      uint32_t* __restrict__ out = (uint32_t*)(ob_of(term) + (size_t)vw * (96 * 96 * 3));
+    if constexpr (GRAY) {
+      if (!(dbg & 8)) {
+        // the same 4 key words per lane as the RGB path -> 4 luma bytes, one streaming dword store per row trip and slot
+        const int r0 = tl / 24, c4 = (tl - r0 * 24) * 4;
+        if (tl < 240) {
+          const uint32_t* kp0 = &keyb[(ROWS - 1 - r0) * KS + c4];
+          constexpr int NT = (ROWS + 9) / 10;
+          uint32_t gv[NT];
+#pragma unroll
+          for (int g0 = 0; g0 < NT; ++g0) {
+            const uint32_t* kp = kp0 - g0 * 10 * KS;
+            gv[g0] = (g0 * 10 + 10 <= ROWS || r0 + g0 * 10 < ROWS) ? luma_key(kp[0]) | luma_key(kp[1]) << 8 | luma_key(kp[2]) << 16 | luma_key(kp[3]) << 24 : 0u;
+          }
+          uint32_t* o0 = (uint32_t*)ob_of(term, vw, gs0) + tl;
+          for (int q = 0; q < gns; ++q, o0 += gds * GRAY_FRAME_WORDS) {
+#pragma unroll
+            for (int g0 = 0; g0 < NT; ++g0)
+              if (g0 * 10 + 10 <= ROWS || r0 + g0 * 10 < ROWS) __builtin_nontemporal_store(gv[g0], o0 + g0 * 240);
+          }
+        }
+        if (ring.k > 1) {
+          // a frame copy: 9,216 bytes, 16 per thread
+          auto copy_frame = [&](const uint8_t* src, uint8_t* dst) {
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            for (int i = tl; i < GRAY_FRAME_WORDS / 4; i += VIEW_THREADS) __builtin_nontemporal_store(((const u32x4*)src)[i], (u32x4*)dst + i);
+          };
+          const int j = ring.j, k = ring.k;
+          if (LIST && term) {
+            // a terminal entry's k - 1 older frames: the live ring's frames of the steps j + 1 - k .. j - 1 from the copies this step's first
+            // frame of the re-spawned env does not overwrite (slots outside j .. j + k)
+            const int lvw = p.term_env[env].env * N + agent;
+            for (int i = 0; i + 1 < k; ++i) {
+              const int r = (j + 1 + i) % k;
+              copy_frame(ob_of(0, lvw, r > j ? r + k : r), ob_of(term, vw, i));
+            }
+          } else if (gfresh) {
+            // the first frame's copies in slots 1 .. j - 1 (they hold the previous episode's frames, which its terminal entry may be
+            // reading in this very launch) are written by the view's next draw: remember where the first frame is
+            if (tl == 0) ring.fresh[vw] = (uint8_t)(j >= 2 ? j + 1 : 0);
+          } else {
+            if (gpend != 0) {
+              const int r = gpend - 1;                                          // (this draw writes slots j, j + k: neither is one of 1 .. r - 1)
+              for (int s = 1; s < r; ++s) copy_frame(ob_of(0, vw, r), ob_of(0, vw, s));
+              if (tl == 0) ring.fresh[vw] = 0;
+            }
+          }
+        }
+      }
+    }
+    else if (!(dbg & 8)) {
+      uint32_t* __restrict__ out = (uint32_t*)ob_of(term, vw, 0);
       // 240 threads x 9 trips of 10 rows: a thread keeps its 4-pixel group's column and walks down 10 rows per trip, so that key-buffer and
       // frame addresses are one division per view plus constants (256 threads x 8 trips: a division and a bounds check per trip); the
       // winners' RGB bytes are packed with three byte permutes

@@ -55,7 +55,7 @@ struct mcr_env {
   unsigned long long* view_stamps;   // [BN][16] phase clocks of the rasteriser (debug bit 5)
   // hipGraph of one step (mcr_set_step_graph): one per contact-list parity, re-captured when any argument changes
   struct StepGraph { bool valid; McrParams P; hipStream_t st; int view_flags; hipGraph_t graph; hipGraphExec_t exec; };
-  StepGraph sg[2];
+  StepGraph sg[2 * MCR_OBS_STACK_MAX];   // [ring head j][parity] (mcr_set_obs_format: the raster's launches carry j)
   int use_graph;              // 0 off, 1 on, -1 capture failed once: stay off
   bool unfused_collide;       // MCR_UNFUSED_COLLIDE=1 (read at create): the contact chain waits for the all-env contact pass instead of running its envs' own
   bool concurrent_collide;    // the contact pass may run beside the main dynamics (kernels of different streams do overlap here: probed at create)
@@ -81,6 +81,9 @@ struct mcr_env {
   int32_t* term_cnt2 = nullptr;   // [2][4] counters by step parity
   int32_t* term_list2 = nullptr;  // [2][2][cap] entry lists by step parity and chain
   struct RefillSvc* svc = nullptr;  // mcr_refill_start: the handle's own host thread that generates and stages consumed episodes
+  bool obs_gray = false;      // mcr_set_obs_format: the raster's GRAY instantiations ...
+  McrObsRing ring{nullptr, 1, 0};   // ... and where their frames go (ring.j: set per launch)
+  uint64_t obs_draws = 0;     // drawing steps enqueued (mcr_step with an observation buffer): the ring head is obs_draws mod k
 };
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -130,7 +133,7 @@ extern "C" int mcr_create(const mcr_config* cfg, mcr_env** out) {
   if (cfg->num_envs < 1 || cfg->num_envs > MCR_VORDER_ENV_MASK || cfg->num_agents < 1 || cfg->num_agents > MCR_MAX_AGENTS) { g_err = "num_envs/num_agents out of range"; return MCR_ERR_ARG; }
   HIPCHK(hipSetDevice(cfg->device));
   mcr_env* h = new mcr_env();
-  h->cfg = *cfg; h->timing = 0; h->any_reset = false; h->use_graph = 0; h->verdict_fresh = false; h->concurrent_collide = false; h->unfused_collide = getenv("MCR_UNFUSED_COLLIDE") != nullptr; h->sg[0].valid = h->sg[1].valid = false;
+  h->cfg = *cfg; h->timing = 0; h->any_reset = false; h->use_graph = 0; h->verdict_fresh = false; h->concurrent_collide = false; h->unfused_collide = getenv("MCR_UNFUSED_COLLIDE") != nullptr; for (auto& g : h->sg) g.valid = false;
   h->vorder_dirty[0] = h->vorder_dirty[1] = false;
   // A list chain is a serial solver chain per wavefront (2 envs each).  With i.i.d. random actions and two cars per env the
   // contact list holds ~15 envs of 4096, but a policy that actually drives (or N = 8: ~340 envs) fills it with hundreds, and
@@ -292,6 +295,7 @@ extern "C" int mcr_destroy(mcr_env* h) {
   }
   (void)hipFree(h->slab);
   if (h->term_slab) (void)hipFree(h->term_slab);
+  if (h->ring.fresh) (void)hipFree(h->ring.fresh);
   (void)hipHostFree(h->consumed_host);
   (void)hipHostFree(h->status_host);
   delete[] h->consumed_seen;
@@ -351,7 +355,8 @@ static hipEvent_t get_event(mcr_env* h) {
 // a launch of the dynamics over all envs: with or without the contact code (k_dynamics.h)
 #define LAUNCH_DYN(kid_, cc_, grid, st, ...) do { if (cc_) LAUNCH(kid_, k_dynamics<true>, grid, 64, st, __VA_ARGS__); else LAUNCH(kid_, k_dynamics<false>, grid, 64, st, __VA_ARGS__); } while (0)
 
-void mcr_view_launch(int variant, int grid, hipStream_t st, const McrParams& P, unsigned long long* stamps, int only_just_reset, hipEvent_t stop, hipEvent_t start);   // mcr_view.hip
+void mcr_view_launch(int variant, int grid, hipStream_t st, const McrParams& P, unsigned long long* stamps, int only_just_reset, hipEvent_t stop, hipEvent_t start,
+                     bool gray, const McrObsRing& ring);   // mcr_view.hip
 // raster launch (k_view.h).  Main launches: one workgroup per work slot.  List launches (role >= 2): MCR_LIST_GRID
 // persistent workgroups that walk the list (lane k of a wavefront holds a workgroup's k-th env, so never fewer than
 // slots / 64 workgroups).
@@ -366,8 +371,8 @@ static void launch_view(mcr_env* h, int kid, int slots, hipStream_t st, const Mc
   if (tm) { tl.id = kid; tl.a = get_event(h); tl.b = get_event(h); if (own_ts) { start = tl.a; stop = tl.b; } else (void)hipEventRecord(tl.a, st); }
   // (list launches: with more than two cars per env the contact list is long — N = 8: ~340 envs x 8 views per step — and 128
   // workgroups would draw ~20 views each, one after the other, at the end of the side stream's chain)
-  if (P.role >= 2) { McrParams Q = P; Q.split_views = 1; mcr_view_launch(2, list_grid(slots * (Q.split_views ? P.N : 1), std::max(h->list_view_grid, want_grid)) + Q.flags_blocks, st, Q, h->view_stamps, only_just_reset, stop, start); }
-  else mcr_view_launch((P.debug & 32) ? 1 : 0, slots, st, P, h->view_stamps, only_just_reset, stop, start);
+  if (P.role >= 2) { McrParams Q = P; Q.split_views = 1; mcr_view_launch(2, list_grid(slots * (Q.split_views ? P.N : 1), std::max(h->list_view_grid, want_grid)) + Q.flags_blocks, st, Q, h->view_stamps, only_just_reset, stop, start, h->obs_gray, h->ring); }
+  else mcr_view_launch((P.debug & 32) ? 1 : 0, slots, st, P, h->view_stamps, only_just_reset, stop, start, h->obs_gray, h->ring);
   if (tm) { if (!own_ts) (void)hipEventRecord(tl.b, st); h->pending.push_back(tl); }
 }
 
@@ -649,6 +654,7 @@ extern "C" int mcr_reset(mcr_env* h, const uint8_t* d_env_mask, uint8_t* d_obs, 
   hipStream_t st = (hipStream_t)stream;
   McrParams P = h->P;
   P.reset_mask = d_env_mask; P.obs = h->cfg.obs_enabled ? d_obs : nullptr; P.actions = nullptr;
+  h->ring.j = (int)((h->obs_draws + (uint64_t)h->ring.k - 1u) % (uint64_t)h->ring.k);     // the head of the last drawing step: the window stays put
   launch_reset(h, P, st);
   HIPCHK(hipGetLastError());
   h->any_reset = true; h->verdict_fresh = false;
@@ -658,6 +664,7 @@ extern "C" int mcr_reset(mcr_env* h, const uint8_t* d_env_mask, uint8_t* d_obs, 
 extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* d_reward, uint8_t* d_done, uint8_t* d_trunc, void* stream) {
   if (!h || !d_reward || !d_done) { g_err = "null argument"; return MCR_ERR_ARG; }
   if (!h->any_reset) { g_err = "step() before reset()"; return MCR_ERR_STATE; }
+  if (h->ring.k > 1 && !d_obs) { g_err = "mcr_step: a stacked observation format needs d_obs every step (a skipped draw leaves a hole in the ring)"; return MCR_ERR_ARG; }
   if (int rc = check_status(h)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (h->use_graph <= 0) {
@@ -670,6 +677,7 @@ extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, doub
   P.actions = d_actions; P.obs = h->cfg.obs_enabled ? d_obs : nullptr;
   P.reward_out = d_reward; P.done_out = d_done; P.trunc_out = d_trunc;
   P.bp_fresh = h->bp_fresh ? 1 : 0; h->bp_fresh = false;
+  if (P.obs) { h->ring.j = (int)(h->obs_draws % (uint64_t)h->ring.k); ++h->obs_draws; }
   h->step_count = (int32_t)((uint32_t)h->step_count + 1u);      // (wraps: epochs are compared as 32-bit distances, mcr_kernels.h)
   // with auto_reset, finished envs are re-spawned on the device and take the action-less first step of their
   // new episode inside this call; the view kernel always runs (it also owns the backward/on-grass flags)
@@ -695,7 +703,7 @@ extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, doub
     // dependent kernels are GPU-side drain/start-up, not host launch cost — so VecMultiCarRacing leaves it off).  Any change of an argument
     // (other buffers, another stream, debug switches) re-captures.
     const int par = h->step_parity;
-    mcr_env::StepGraph& G = h->sg[par];
+    mcr_env::StepGraph& G = h->sg[par + 2 * (P.obs ? h->ring.j : 0)];
     if (G.valid && G.st == st && G.view_flags == vf && memcmp(&G.P, &P, sizeof(P)) == 0) {
       h->step_parity ^= 1;                              // what launch_step does on the host side
       HIPCHK(hipGraphLaunch(G.exec, st));
@@ -775,6 +783,33 @@ extern "C" int mcr_set_terminal_obs(mcr_env* h, uint8_t* d_term_obs, int32_t* d_
   P.term_idx = (int32_t*)(base + o_idx); P.term_carf = (float*)(base + o_carf); P.term_card = (double*)(base + o_card);
   P.term_viewp = (float*)(base + o_vp); P.term_carpoly = (float*)(base + o_cp); P.term_tflags = (uint16_t*)(base + o_tf); P.term_env = (McrTermEnv*)(base + o_te);
   return MCR_OK;
+}
+
+extern "C" int mcr_set_obs_format(mcr_env* h, int format, int stack) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if ((format != MCR_OBS_RGB && format != MCR_OBS_GRAY) || stack < 1 || stack > MCR_OBS_STACK_MAX || (format == MCR_OBS_RGB && stack != 1)) {
+    g_err = "mcr_set_obs_format: format MCR_OBS_RGB with stack 1, or MCR_OBS_GRAY with stack 1 .. MCR_OBS_STACK_MAX"; return MCR_ERR_ARG;
+  }
+  if (!h->cfg.obs_enabled) { g_err = "mcr_set_obs_format needs obs_enabled"; return MCR_ERR_STATE; }
+  if (h->any_reset) { g_err = "mcr_set_obs_format after the first mcr_reset"; return MCR_ERR_STATE; }
+  if (h->term_slab) { g_err = "mcr_set_obs_format after mcr_set_terminal_obs: set the format first (it shapes the terminal entries)"; return MCR_ERR_STATE; }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  if (h->ring.fresh) { (void)hipFree(h->ring.fresh); h->ring.fresh = nullptr; }
+  const size_t bn = (size_t)h->cfg.num_envs * h->cfg.num_agents;
+  if (stack > 1) {
+    if (hipMalloc(&h->ring.fresh, bn) != hipSuccess) { h->ring.fresh = nullptr; g_err = "hipMalloc failed"; return MCR_ERR_HIP; }
+    HIPCHK(hipMemset(h->ring.fresh, 0, bn));
+  }
+  h->obs_gray = format == MCR_OBS_GRAY; h->ring.k = stack; h->ring.j = 0;
+  return MCR_OK;
+}
+extern "C" size_t mcr_obs_bytes_per_view(const mcr_env* h) {
+  if (!h) return 0;
+  return !h->obs_gray ? (size_t)96 * 96 * 3 : (size_t)96 * 96 * (h->ring.k > 1 ? 2 * h->ring.k : 1);
+}
+extern "C" int mcr_obs_window(const mcr_env* h) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  return h->ring.k > 1 ? (int)((h->obs_draws + (uint64_t)h->ring.k - 1u) % (uint64_t)h->ring.k) + 1 : 0;
 }
 
 extern "C" int mcr_set_step_graph(mcr_env* h, int enable) {

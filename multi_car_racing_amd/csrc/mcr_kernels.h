@@ -109,6 +109,16 @@ struct McrParams {
   double h_ratio;
 };
 
+// The observation format of the raster (include/mcr.h: mcr_set_obs_format): a launch argument of k_view beside McrParams, read by its GRAY
+// instantiations only.  A stacked view owns a ring of 2k frames: a drawing step's frame goes to slots j and j + k, a first frame to
+// slots j .. j + k, and the observation is slots j + 1 .. j + k.
+struct McrObsRing {
+  uint8_t* fresh;               // [BN] k > 1: 1 + the slot j >= 2 of the view's last first frame, until its next draw copies that frame into
+                                // slots 1 .. j - 1; else 0
+  int32_t k;                    // frames per observation, 1 .. MCR_OBS_STACK_MAX
+  int32_t j;                    // ring head of the launch, 0 .. k - 1
+};
+
 // status words (mapped host memory).  FATAL ones (give-up, verdict) make the next mcr_step return MCR_ERR_STATE; an OVERFLOW truncated a
 // capacity-bound list (documented deviation): the step goes on, mcr_status shows the count
 enum { ST_SPIN_GIVEUP = 0,     // a kernel gave up waiting for another stream's kernels (three-chain step: the contact pass of an env, a phase word)

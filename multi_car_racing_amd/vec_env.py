@@ -22,6 +22,13 @@ Determinism: env with global index g uses two numpy-compatible MT19937 streams,
   draw stream   RandomState((seed + g + 2**31) % 2**32)   (stands in for the reference's *global* np.random:
                 direction choice then car order, multi_car_racing.py:351-357)
 so results do not depend on B, on the GPU count, or on scheduling.
+
+Observation format: `obs_format="rgb"` (default) hands out [B, N, 96, 96, 3] frames.  `obs_format="gray"` is gym's GrayScaleObservation
+(OpenCV's fixed-point COLOR_RGB2GRAY, (4899 R + 9617 G + 1868 B + 8192) >> 14, of the bytes the RGB frame would hold), drawn by the raster
+itself: [B, N, 96, 96].  With `frame_stack=k > 1` it is also gym's FrameStack(k): [B, N, k, 96, 96], oldest frame first, and after a reset or
+an auto-reset the env's first frame k times (gym's rule; SB3's VecFrameStack zero-fills instead).  The stack is a strided VIEW of a ring of
+2k frames per agent that the raster writes in place (include/mcr.h: mcr_set_obs_format): nothing is shifted or copied, and the view
+changes with every step — keep the tensor step() returns, not an older one.
 """
 import atexit
 import collections
@@ -61,7 +68,7 @@ class VecMultiCarRacing:
                  use_random_direction=True, backwards_flag=True, h_ratio=0.25, use_ego_color=False,
                  obs=True, auto_reset=True, max_episode_steps=1000, car_contacts=True,
                  gen_threads=None, async_refill=True, streams=None, refill_lag=64, world_size=1, graph=None,
-                 skid_particles=False, terminal_obs=False, terminal_cap=None, fresh_world=False):
+                 skid_particles=False, terminal_obs=False, terminal_cap=None, fresh_world=False, obs_format="rgb", frame_stack=1):
         if not torch.cuda.is_available():
             raise _lib.McrError("VecMultiCarRacing needs a HIP device: the step path has no CPU fallback")
         self.L = _lib.load()
@@ -70,6 +77,19 @@ class VecMultiCarRacing:
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         torch.cuda.set_device(self.device)
         self.obs_enabled = bool(obs)
+        if obs_format not in ("rgb", "gray"):
+            raise ValueError(f"obs_format must be 'rgb' or 'gray', got {obs_format!r}")
+        frame_stack = int(frame_stack)
+        if obs_format == "rgb" and frame_stack != 1:
+            raise ValueError("frame_stack > 1 needs obs_format='gray'")
+        if not 1 <= frame_stack <= _lib.OBS_STACK_MAX:
+            raise ValueError(f"frame_stack must be 1..{_lib.OBS_STACK_MAX}, got {frame_stack}")
+        if (obs_format != "rgb" or frame_stack != 1) and not self.obs_enabled:
+            raise ValueError("obs_format / frame_stack need obs=True")
+        if 0 < int(max_episode_steps) < frame_stack:
+            raise ValueError("max_episode_steps must be 0 or at least frame_stack: a terminal stack reads the ring copies of the episode's last "
+                             "frame_stack - 1 frames")
+        self.obs_format, self.frame_stack = obs_format, frame_stack
         if streams is None:           # contact side stream (include/mcr.h: num_streams) pays as soon as there is a batch
             streams = 2 if int(num_envs) >= 64 and int(num_agents) > 1 and car_contacts else 1
         self.auto_reset = bool(auto_reset)
@@ -107,8 +127,23 @@ class VecMultiCarRacing:
         if graph is None:             # hipGraph replay of the step: measured r02 at B=4096 — 0.433 vs 0.435 ms per step, i.e. the gaps
             graph = False             # between the step's dependent kernels are drain/start-up on the GPU, not host launch cost: off
         _lib.check(self.L.mcr_set_step_graph(self.h, int(bool(graph))), "mcr_set_step_graph")
-        # persistent outputs (overwritten by every step)
-        self.obs = torch.zeros((self.B, self.N, 96, 96, 3), dtype=torch.uint8, device=self.device) if self.obs_enabled else None
+        if obs_format == "gray":
+            _lib.check(self.L.mcr_set_obs_format(self.h, _lib.OBS_GRAY, frame_stack), "mcr_set_obs_format")
+        # the shape of one env's observation as step() hands it out (learners size their buffers from it)
+        self.obs_shape = ((self.N, 96, 96, 3) if obs_format == "rgb" else (self.N, 96, 96) if frame_stack == 1
+                          else (self.N, frame_stack, 96, 96)) if self.obs_enabled else None
+        # persistent outputs (overwritten by every step).  Stacked gray: self._ring [B, N, 2k, 96, 96] is what the raster writes; self.obs
+        # is the window of the last drawing step (_window)
+        self._ring = None
+        if self.obs_enabled and frame_stack > 1:
+            self._ring = torch.zeros((self.B, self.N, 2 * frame_stack, 96, 96), dtype=torch.uint8, device=self.device)
+            assert self._ring[0, 0].numel() == int(self.L.mcr_obs_bytes_per_view(self.h))
+            self.obs = self._window()
+        elif self.obs_enabled:
+            self.obs = torch.zeros((self.B,) + self.obs_shape, dtype=torch.uint8, device=self.device)
+            assert self.obs[0, 0].numel() == int(self.L.mcr_obs_bytes_per_view(self.h))
+        else:
+            self.obs = None
         self.reward = torch.zeros((self.B, self.N), dtype=torch.float64, device=self.device)
         self.done = torch.zeros((self.B,), dtype=torch.uint8, device=self.device)
         self.truncated = torch.zeros((self.B,), dtype=torch.uint8, device=self.device)
@@ -123,7 +158,7 @@ class VecMultiCarRacing:
             if not (self.obs_enabled and self.auto_reset):
                 raise ValueError("terminal_obs needs obs=True and auto_reset=True")
             cap = self.B if terminal_cap is None else max(1, min(int(terminal_cap), self.B))
-            self.terminal_obs = torch.zeros((cap, self.N, 96, 96, 3), dtype=torch.uint8, device=self.device)
+            self.terminal_obs = torch.zeros((cap,) + self.obs_shape, dtype=torch.uint8, device=self.device)
             self.terminal_env_ids = torch.zeros((cap,), dtype=torch.int32, device=self.device)
             self.terminal_count = torch.zeros((1,), dtype=torch.int32, device=self.device)
             _lib.check(self.L.mcr_set_terminal_obs(self.h, ctypes.c_void_p(self.terminal_obs.data_ptr()), ctypes.c_void_p(self.terminal_env_ids.data_ptr()),
@@ -300,7 +335,7 @@ class VecMultiCarRacing:
 
     # ------------------------------------------------------------------ API
     def reset(self):
-        """Reset every env; returns obs [B,N,96,96,3] uint8 (device tensor, overwritten by later steps)."""
+        """Reset every env; returns obs [B, *obs_shape] uint8 (device tensor, overwritten by later steps)."""
         st = torch.cuda.current_stream(self.device)
         self.wait_refills()
         if not self._has_reset:
@@ -310,8 +345,7 @@ class VecMultiCarRacing:
             # envs re-spawned by steps whose consumption has not been polled yet would find their staged slot empty
             # (k_install skips those): drain, poll and refill first, then every env installs a fresh episode
             self._settle_staging(st)
-        _lib.check(self.L.mcr_reset(self.h, None, ctypes.c_void_p(self.obs.data_ptr()) if self.obs_enabled else None,
-                                    ctypes.c_void_p(st.cuda_stream)), "mcr_reset")
+        _lib.check(self.L.mcr_reset(self.h, None, self._obs_ptr(), ctypes.c_void_p(st.cuda_stream)), "mcr_reset")
         st.synchronize()
         self._has_reset = True
         self._poll_and_refill()
@@ -328,9 +362,7 @@ class VecMultiCarRacing:
             if mask.numel() != self.B:
                 raise ValueError(f"mask must have {self.B} elements")
         self._settle_staging(st)              # a masked env must find its staged slot filled
-        _lib.check(self.L.mcr_reset(self.h, ctypes.c_void_p(mask.data_ptr()),
-                                    ctypes.c_void_p(self.obs.data_ptr()) if self.obs_enabled else None,
-                                    ctypes.c_void_p(st.cuda_stream)), "mcr_reset")
+        _lib.check(self.L.mcr_reset(self.h, ctypes.c_void_p(mask.data_ptr()), self._obs_ptr(), ctypes.c_void_p(st.cuda_stream)), "mcr_reset")
         st.synchronize()
         self._poll_and_refill()
         return self.obs
@@ -361,10 +393,12 @@ class VecMultiCarRacing:
             if actions.numel() != self.B * self.N * 3:
                 raise ValueError(f"actions must have {self.B * self.N * 3} elements, got {actions.numel()}")
             a_ptr = ctypes.c_void_p(actions.data_ptr())
-        _lib.check(self.L.mcr_step(self.h, a_ptr, ctypes.c_void_p(self.obs.data_ptr()) if self.obs_enabled else None,
+        _lib.check(self.L.mcr_step(self.h, a_ptr, self._obs_ptr(),
                                    ctypes.c_void_p(self.reward.data_ptr()), ctypes.c_void_p(self.done.data_ptr()),
                                    ctypes.c_void_p(self.truncated.data_ptr()), ctypes.c_void_p(st.cuda_stream)), "mcr_step")
         self._step_idx += 1                   # (only a step that was launched counts: a reported McrError leaves the accounting alone)
+        if self._ring is not None:
+            self.obs = self._window()
         self._warn_degraded()
         if self.auto_reset:
             self._poll_and_refill()
@@ -375,8 +409,19 @@ class VecMultiCarRacing:
             info["terminal_count"] = self.terminal_count
         return self.obs, self.reward, self.done, info
 
+    def _obs_ptr(self):
+        """the observation buffer the raster writes: the frames, or the ring of a stacked format"""
+        if not self.obs_enabled:
+            return None
+        return ctypes.c_void_p((self._ring if self._ring is not None else self.obs).data_ptr())
+
+    def _window(self):
+        """stacked gray: the ring's slots j + 1 .. j + k of the last enqueued drawing step (include/mcr.h: mcr_obs_window), a view"""
+        w = int(self.L.mcr_obs_window(self.h))
+        return self._ring[:, :, w:w + self.frame_stack]
+
     def terminal_observations(self):
-        """(env ids [k], frames [k, N, 96, 96, 3]) of the episodes that ended in the last step — what the reference returns as its observation
+        """(env ids [k], frames [k, *obs_shape]) of the episodes that ended in the last step — what the reference returns as its observation
         with done = True (multi_car_racing.py:431, :509) — as device tensors; synchronises (reads the count)."""
         if self.terminal_obs is None:
             raise _lib.McrError("created without terminal_obs=True")
