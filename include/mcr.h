@@ -270,8 +270,8 @@ int mcr_concurrent_collide(const mcr_env* h);
  *   1  phase words in device memory, posted and awaited by kernels (no marker / barrier packets; needs overlapping kernels, like
  *      the concurrent contact pass; MCR_SOFT_SYNC=0 turns it off) — for steps launched on a caller stream that mcr_bind_stream
  *      accepted; on any other stream, and without this bit: events;
- *   2  on the event path, events are completed by the launches they mark (hipExtLaunchKernelGGL) rather than recorded behind them
- *      (MCR_STOP_EVENTS=0 turns it off);
+ *   2  on the event path, events are completed by the launches they mark (hipExtLaunchKernelGGL) rather than recorded behind them;
+ *      always set for a three-chain handle (inside a graph capture the events are recorded behind the kernels);
  *   4  kernels do overlap here, but the internal streams of this handle share a hardware queue with those of another live phase-word
  *      handle of this process (probed pairwise at mcr_create; HIP spreads the streams of a priority class over GPU_MAX_HW_QUEUES queues,
  *      4 by default): this handle runs on events (same results, ~0.02 ms more per step).  Handles whose streams have queues of their own

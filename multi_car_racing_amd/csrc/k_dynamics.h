@@ -1468,10 +1468,11 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   uint32_t tvc = 0, flags = 0;
   if (p.cc_mode && mode == 0 && p.role == 1 && run)               // k_collide pass 0 runs beside this launch: wait until it is through with this env
   {
-    // p.epoch is the handle's step counter: no earlier pass can have left the same value behind.  The wait is bounded (~3 s; the
-    // contact pass was enqueued before this launch, takes ~25 us and — mcr_hip.hip gates cc_mode on it — always finds room beside
-    // this launch's one wavefront per SIMD); a give-up is REPORTED (status word -> mcr_step fails, the handle falls back to the
-    // contact pass in front), never silent.  debug bit 12 shortens the bound (tests).
+    // p.epoch is the handle's step counter: no earlier pass can have left the same value behind.  The wait is bounded (~3 s; on the
+    // phase-word path this launch is enqueued first and the contact pass after it, on another stream, so the bound also covers the host's
+    // delay before the k_collide launch; the pass takes ~25 us and — mcr_hip.hip gates cc_mode on it — always finds room beside this launch's one
+    // wavefront per SIMD); a give-up is REPORTED (status word -> mcr_step fails, the handle falls back to the contact pass in front),
+    // never silent.  debug bit 12 shortens the bound (tests).
     const int bound = (p.debug & 4096) ? (1 << 14) : (1 << 24);
     const int epoch = mcr_epoch(p);
     int spin = 0;
@@ -1823,13 +1824,18 @@ __global__ __launch_bounds__(64) void k_dynamics(McrParams p, int mode) {
     if (p.term_cnt_next) { p.term_cnt_next[0] = 0; p.term_cnt_next[1] = 0; p.term_cnt_next[2] = 0; }
   }
   dynamics_block<CC>(p, mode, (int)blockIdx.x);
-  if (mode == 0 && p.post_dyn) {
-    // W_DYN from inside the kernel: every workgroup (= wavefront) releases what it stored (agent scope: its XCD's L2 is written back), then
-    // counts itself; the last one posts.  The HIP memory model's release pattern — the consumer's kernels behind k_await start with the usual acquire.
+  if (mode == 0 && p.soft_sync && p.role == 1) {
+    // W_DYN from inside the kernel (the phase-word step's main dynamics): every workgroup (= wavefront) releases what it stored (agent scope:
+    // its XCD's L2 is written back), then counts itself; the last one acquires what the others released (fence-fence synchronisation through
+    // the counter's RMWs: every workgroup's stores happen before the post) and posts.  The consumer's kernels behind k_await start with the
+    // usual acquire.
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     if (threadIdx.x == 0) {
       const int done = __hip_atomic_fetch_add(&p.sync_words[W_DYN_COUNT * 16], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-      if (done == (int)gridDim.x) { __hip_atomic_store(&p.sync_words[W_DYN_COUNT * 16], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); mcr_post(p, W_DYN); }
+      if (done == (int)gridDim.x) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        __hip_atomic_store(&p.sync_words[W_DYN_COUNT * 16], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); mcr_post(p, W_DYN);
+      }
     }
   }
 }

@@ -57,7 +57,6 @@ struct mcr_env {
   struct StepGraph { bool valid; McrParams P; hipStream_t st; int view_flags; hipGraph_t graph; hipGraphExec_t exec; };
   StepGraph sg[2 * MCR_OBS_STACK_MAX];   // [ring head j][parity] (mcr_set_obs_format: the raster's launches carry j)
   int use_graph;              // 0 off, 1 on, -1 capture failed once: stay off
-  bool unfused_collide;       // MCR_UNFUSED_COLLIDE=1 (read at create): the contact chain waits for the all-env contact pass instead of running its envs' own
   bool concurrent_collide;    // the contact pass may run beside the main dynamics (kernels of different streams do overlap here: probed at create)
   bool verdict_fresh;         // the touch verdicts (k_touch.h) of the next step's entry poses are in place (last step's bookkeeping wrote them)
   bool last_fused = false;    // ... and so is the next step's contact list (the last step ran with McrParams::fuse_collide)
@@ -73,9 +72,7 @@ struct mcr_env {
   bool soft_denied = false;   // kernels overlap here, but another handle of this process holds the device's one phase-word token (mcr_create)
   bool soft_token = false;    // this handle is its device's one phase-word handle (mcr_create)
   bool soft_sync = false;     // the step's streams meet through phase words in device memory (mcr_kernels.h: mcr_post / mcr_await) instead of events
-  bool stop_events = true;    // events completed by the launches they mark (hipExtLaunchKernelGGL) instead of marker packets behind them
   int chain_grid;             // workgroups of a list chain launch (each walks the list, 2 envs at a time)
-  bool post_dyn = true;       // the main dynamics posts its own completion (McrParams::post_dyn; MCR_POST_DYN=0, read at create: the kernel behind it does, as in rounds 3-5)
   bool vorder_dirty[2];       // the raster order list of that step parity was filled by a step that did not draw
   void* term_slab = nullptr;  // terminal observations (mcr_set_terminal_obs): entry state, view records, per-parity counters and lists
   int32_t* term_cnt2 = nullptr;   // [2][4] counters by step parity
@@ -128,12 +125,59 @@ static bool kernels_overlap(hipStream_t sa, hipStream_t sb) {
   return ok;
 }
 
+// The three-chain step's internal streams and how it orders its streams (mcr_config.num_streams == 2, launch_step): sets the handle's split
+// (false where a stream cannot be created), soft_sync, soft_token, soft_denied and concurrent_collide.  MCR_SOFT_SYNC=0 forces events and
+// MCR_SEQUENTIAL_COLLIDE=1 the contact pass in front of the dynamics: what serialising profilers, graph capture and a give-up get (the parity
+// suite covers each).
+static void select_step_ordering(mcr_env* h) {
+  const int B = h->cfg.num_envs, N = h->cfg.num_agents, G = h->P.G;
+  // highest priority: their few workgroups must not queue behind the main stream's saturating raster launch.
+  // (Tried: giving the chains CUs of their own with hipExtStreamCreateWithCUMask — tools/ubench/cumask_probe.hip shows
+  // the mask layout — restores their stand-alone kernel times beside the raster, but every launch and event hop on a
+  // masked stream costs ~10 us more: 0.81 ms per step.)
+  int prio_lo = 0, prio_hi = 0; (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+  if (hipStreamCreateWithPriority(&h->s_side, hipStreamNonBlocking, prio_hi) != hipSuccess) { (void)hipGetLastError(); return; }
+  // (the priority of the third stream — it carries the main raster, whose backlog of workgroups competes with the list raster at the
+  // tail of the caller's stream for every LDS slot that frees up — makes no difference: high / normal / low 14.73 / 14.72 / 14.72 M)
+  if (hipStreamCreateWithPriority(&h->s_defer, hipStreamNonBlocking, prio_hi) != hipSuccess) { (void)hipStreamDestroy(h->s_side); (void)hipGetLastError(); return; }
+  const unsigned evf = hipEventDisableTiming;     // (hipEventReleaseToDevice changes nothing measurable: tools/ubench/event_gap.hip)
+  for (hipEvent_t* e : {&h->ev_fork, &h->ev_join, &h->ev_fork2, &h->ev_join2, &h->ev_col}) (void)hipEventCreateWithFlags(e, evf);
+  h->soft_sync = kernels_overlap(h->s_defer, h->s_side);     // (a waiting kernel needs the kernels it waits for to run beside it)
+  if (const char* g = getenv("MCR_SOFT_SYNC")) h->soft_sync = h->soft_sync && atoi(g) != 0;
+  // A further phase-word handle on the device needs internal streams on hardware queues of its own.  The main dynamics, which posts
+  // "begin", goes out before every wait of its step, but host threads stepping two handles interleave their enqueues freely: with the
+  // streams of both multiplexed over the same hardware queues, handle A's waiting kernel can sit in front of a kernel handle B's step
+  // waits for, and B's in front of one of A's — a cycle that only the wait bound would break.  A handle whose streams share a queue
+  // with another phase-word handle's orders its streams with events (every wait there is for work enqueued earlier).
+  if (h->soft_sync) {
+    std::lock_guard<std::mutex> lk(g_soft_mu);
+    bool own_queues = true;
+    for (mcr_env* o : g_soft_list)
+      if (own_queues && o->cfg.device == h->cfg.device)
+        own_queues = kernels_overlap(h->s_side, o->s_side) && kernels_overlap(h->s_side, o->s_defer) && kernels_overlap(h->s_defer, o->s_side) && kernels_overlap(h->s_defer, o->s_defer) &&
+                     kernels_overlap(o->s_side, h->s_side) && kernels_overlap(o->s_defer, h->s_defer);
+    if (own_queues) { h->soft_token = true; g_soft_list.push_back(h); }
+    else { h->soft_sync = false; h->soft_denied = true; }
+  }
+  // (at 8 cars per env the one-step-ahead touch verdict — a second pass over up to 28 car pairs — costs more than the
+  // contact pass gains by running beside the dynamics: measured at N = 8, round 2: 3.66 vs 4.28 M env-steps/s.  Round 3 tried a
+  // CONSERVATIVE verdict there instead — bounding discs + car boxes, no narrowphase, the contact chain taking every env it
+  // marks: with ~340 of 4096 envs in contact and as many near misses per step the side stream's chain, bookkeeping and raster
+  // grow faster than the 110 us of k_collide that leave the critical path: 1.40 vs 0.975 ms per step.  What bounds N = 8 is the
+  // contact chain itself — 585 us for its slowest wavefront, a sequential Gauss-Seidel over the contacts between the joint sweeps)
+  // (round 3, phase-word path, contact pass beside / in front of the dynamics: N = 5 8.99 / 8.50 M env-steps/s, N = 6 7.87 / 7.49,
+  // N = 7 7.16 / 6.80, N = 8 4.90 / 5.47 — up to seven cars per env it runs beside)
+  h->concurrent_collide = N <= 8 && !getenv("MCR_SEQUENTIAL_COLLIDE") && (B * G + 63) / 64 <= h->simd_count && kernels_overlap(h->s_defer, h->s_side);
+  h->split = true;
+  (void)hipGetLastError();
+}
+
 extern "C" int mcr_create(const mcr_config* cfg, mcr_env** out) {
   if (!cfg || !out) { g_err = "null argument"; return MCR_ERR_ARG; }
   if (cfg->num_envs < 1 || cfg->num_envs > MCR_VORDER_ENV_MASK || cfg->num_agents < 1 || cfg->num_agents > MCR_MAX_AGENTS) { g_err = "num_envs/num_agents out of range"; return MCR_ERR_ARG; }
   HIPCHK(hipSetDevice(cfg->device));
   mcr_env* h = new mcr_env();
-  h->cfg = *cfg; h->timing = 0; h->any_reset = false; h->use_graph = 0; h->verdict_fresh = false; h->concurrent_collide = false; h->unfused_collide = getenv("MCR_UNFUSED_COLLIDE") != nullptr; for (auto& g : h->sg) g.valid = false;
+  h->cfg = *cfg; h->timing = 0; h->any_reset = false; h->use_graph = 0; h->verdict_fresh = false; h->concurrent_collide = false; for (auto& g : h->sg) g.valid = false;
   h->vorder_dirty[0] = h->vorder_dirty[1] = false;
   // A list chain is a serial solver chain per wavefront (2 envs each).  With i.i.d. random actions and two cars per env the
   // contact list holds ~15 envs of 4096, but a policy that actually drives (or N = 8: ~340 envs) fills it with hundreds, and
@@ -219,61 +263,9 @@ extern "C" int mcr_create(const mcr_config* cfg, mcr_env** out) {
   memset(h->status_host, 0, sizeof(uint32_t) * (MCR_STATUS_WORDS + MCR_HOST_COUNTS));
   (void)hipHostGetDevicePointer(&dptr, h->status_host, 0);
   P.status = (uint32_t*)dptr; P.host_counts = P.status + MCR_STATUS_WORDS;
-  // Contact side stream.  k_dynamics is a serial dependency chain whose duration is set by its slowest wavefront,
-  // and a wavefront holding a touching car<->car pair takes 2-3x as long as the others (sequential Gauss-Seidel
-  // over the contacts).  With num_streams == 2 those envs (a handful per step) run dynamics -> reset pass ->
-  // raster on an internal stream, concurrently with the same chain of all the other envs on the caller's stream;
-  // the two event hops are off the critical path because the side chain is the shorter one.
   P.env0 = 0; P.nenv = B; P.split = 0; P.role = 0;
   h->split = false; h->step_parity = 0;
-  if (cfg->num_streams == 2) {
-    // highest priority: their few workgroups must not queue behind the main stream's saturating raster launch.
-    // (Tried: giving the chains CUs of their own with hipExtStreamCreateWithCUMask — tools/ubench/cumask_probe.hip shows
-    // the mask layout — restores their stand-alone kernel times beside the raster, but every launch and event hop on a
-    // masked stream costs ~10 us more: 0.81 ms per step.)
-    int prio_lo = 0, prio_hi = 0; (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    if (hipStreamCreateWithPriority(&h->s_side, hipStreamNonBlocking, prio_hi) == hipSuccess) {
-      // (the priority of the third stream — it carries the main raster, whose backlog of workgroups competes with the list raster at the
-      // tail of the caller's stream for every LDS slot that frees up — makes no difference: high / normal / low 14.73 / 14.72 / 14.72 M)
-      if (hipStreamCreateWithPriority(&h->s_defer, hipStreamNonBlocking, prio_hi) == hipSuccess) {
-        const unsigned evf = hipEventDisableTiming;     // (hipEventReleaseToDevice changes nothing measurable: tools/ubench/event_gap.hip)
-        for (hipEvent_t* e : {&h->ev_fork, &h->ev_join, &h->ev_fork2, &h->ev_join2, &h->ev_col}) (void)hipEventCreateWithFlags(e, evf);
-        // (the switches of the environment — MCR_SOFT_SYNC=0, MCR_STOP_EVENTS=0, MCR_SEQUENTIAL_COLLIDE=1 — select paths that exist for
-        // environments where the default cannot run: profilers that serialise kernels, graph capture; the parity suite covers each)
-        if (const char* g = getenv("MCR_STOP_EVENTS")) h->stop_events = atoi(g) != 0;
-        if (const char* g = getenv("MCR_POST_DYN")) h->post_dyn = atoi(g) != 0;
-        h->soft_sync = kernels_overlap(h->s_defer, h->s_side);     // (a waiting kernel needs the kernels it waits for to run beside it)
-        if (const char* g = getenv("MCR_SOFT_SYNC")) h->soft_sync = h->soft_sync && atoi(g) != 0;
-        // One handle per device and process at a time: the side stream's wait for "begin" is enqueued BEFORE the kernel that posts it.
-        // With the streams of two handles multiplexed over the same hardware queues and their steps interleaved on one caller's stream,
-        // handle A's waiting kernel can sit in front of the post handle B's join waits for, which in turn sits in front of A's dynamics:
-        // a cycle that only the wait bound would break.  Further handles order their streams with events (every wait there is for work
-        // enqueued earlier).
-        if (h->soft_sync) {
-          std::lock_guard<std::mutex> lk(g_soft_mu);
-          bool own_queues = !getenv("MCR_ONE_SOFT_HANDLE");
-          for (mcr_env* o : g_soft_list)
-            if (own_queues && o->cfg.device == cfg->device)
-              own_queues = kernels_overlap(h->s_side, o->s_side) && kernels_overlap(h->s_side, o->s_defer) && kernels_overlap(h->s_defer, o->s_side) && kernels_overlap(h->s_defer, o->s_defer) &&
-                           kernels_overlap(o->s_side, h->s_side) && kernels_overlap(o->s_defer, h->s_defer);
-          bool other = false; for (mcr_env* o : g_soft_list) other = other || o->cfg.device == cfg->device;
-          if (own_queues || !other) { h->soft_token = true; g_soft_list.push_back(h); }
-          else { h->soft_sync = false; h->soft_denied = true; }
-        }
-        // (at 8 cars per env the one-step-ahead touch verdict — a second pass over up to 28 car pairs — costs more than the
-        // contact pass gains by running beside the dynamics: measured at N = 8, round 2: 3.66 vs 4.28 M env-steps/s.  Round 3 tried a
-        // CONSERVATIVE verdict there instead — bounding discs + car boxes, no narrowphase, the contact chain taking every env it
-        // marks: with ~340 of 4096 envs in contact and as many near misses per step the side stream's chain, bookkeeping and raster
-        // grow faster than the 110 us of k_collide that leave the critical path: 1.40 vs 0.975 ms per step.  What bounds N = 8 is the
-        // contact chain itself — 585 us for its slowest wavefront, a sequential Gauss-Seidel over the contacts between the joint sweeps)
-        // (round 3, phase-word path, contact pass beside / in front of the dynamics: N = 5 8.99 / 8.50 M env-steps/s, N = 6 7.87 / 7.49,
-        // N = 7 7.16 / 6.80, N = 8 4.90 / 5.47 — up to seven cars per env it runs beside)
-        h->concurrent_collide = N <= 8 && !getenv("MCR_SEQUENTIAL_COLLIDE") && (B * G + 63) / 64 <= h->simd_count && kernels_overlap(h->s_defer, h->s_side);
-        h->split = true;
-      } else (void)hipStreamDestroy(h->s_side);
-    }
-    (void)hipGetLastError();
-  }
+  if (cfg->num_streams == 2) select_step_ordering(h);
   (void)hipDeviceSynchronize();
   *out = h;
   return MCR_OK;
@@ -387,176 +379,154 @@ static void launch_reset(mcr_env* h, McrParams P, hipStream_t st) {
   if (P.obs) launch_view(h, 2, B, st, P, 1);
 }
 
-// step(): collide -> dynamics [-> auto-reset pass] -> view on the caller's stream `st`; with num_streams == 2 the step forks
-// into three chains that meet again at the end (see the diagram inside; grids are sized for the worst case, surplus workgroups
-// exit on their first load).  Contact envs: a wavefront holding a touching car<->car pair takes 2-4x as long as the others.
-// Deferred envs: the few whose position loop is still iterating after 3 sweeps (a slow marginal crawl that would hold the whole
-// main launch for up to 60).  An env of either list that ended its episode in this step (rare) takes its reset pass inside its
-// own chain.
 // may a step launched on caller stream `st` order its streams with phase words?  (mcr_bind_stream checked it; an unbound stream: events)
 static bool stream_bound(const mcr_env* h, hipStream_t st) {
   for (const auto& b : h->bound) if (b.first == st) return b.second;
   return false;
 }
-// Do the contact chain's workgroups run their envs' contact pass themselves (McrParams::fuse_collide)?  With the contact pass beside the
-// dynamics (the list then comes from the one-step-ahead verdicts) and the phase-word ordering (the side stream's last kernel empties the list)
-// — measured +0.9 % (N = 2 default), +1.8 % (N = 4).  MCR_UNFUSED_COLLIDE=1: off (the round-4 topology).  (Round 5's first attempt diverged in 7
-// of 10 rollouts with ~1000 contact envs: the chain's wavefronts, filling the machine at the step's begin, held the contact pass of the OTHER
-// envs up long enough for a latent race of the contact-pass-beside-the-dynamics mode to show — k_dynamics.h "Parking overwrites", NOTES 11.)
-static bool fused_collide(const mcr_env* h, hipStream_t st) {
-  if (!cc_active(h) || h->unfused_collide) return false;
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(st, &capturing);
-  return h->soft_sync && h->use_graph <= 0 && capturing == hipStreamCaptureStatusNone && stream_bound(h, st);
+static bool capturing(hipStream_t st) { hipStreamCaptureStatus c = hipStreamCaptureStatusNone; (void)hipStreamIsCapturing(st, &c); return c != hipStreamCaptureStatusNone; }
+// Does a three-chain step launched on `st` order its streams with phase words (step_phase_words)?  Otherwise with events (step_events).
+static bool phase_words(const mcr_env* h, hipStream_t st) {
+  return h->soft_sync && h->use_graph <= 0 && !capturing(st) && stream_bound(h, st);
 }
-static void launch_step(mcr_env* h, McrParams P, hipStream_t st, int view_flags) {
-  const int B = P.B, N = P.N;
-  const int dyn_blocks = (B * P.G + 63) / 64;
-  // list launches (contact / deferred / re-spawned envs): small grids whose workgroups walk the device-side lists
-  const int lg_col = std::min(B, MCR_LIST_GRID), lg_dyn = std::min((B + MCR_SIDE_ENVS_PER_WAVE - 1) / MCR_SIDE_ENVS_PER_WAVE, h->chain_grid);
-  const int lg_con = std::min(B, 2 * h->chain_grid);             // the contact chain: one env per wavefront
-  const int prev_contacts = std::min(B, (int)((volatile uint32_t*)h->status_host)[MCR_STATUS_WORDS + HC_CONTACT_ENVS]);   // (mapped host word: no synchronisation)
-  const bool draw = P.obs != nullptr;
+// Do the contact chain's workgroups run their envs' contact pass themselves (McrParams::fuse_collide)?  Whenever the contact pass runs beside the
+// dynamics (the list then comes from the one-step-ahead verdicts) on the phase-word path (the side stream's last kernel empties the list) — measured
+// +0.9 % (N = 2 default), +1.8 % (N = 4) against a chain that waits for the all-env pass.  (Round 5's first attempt diverged in 7 of 10 rollouts
+// with ~1000 contact envs: the chain's wavefronts, filling the machine at the step's begin, held the contact pass of the OTHER envs up long enough
+// for a latent race of the contact-pass-beside-the-dynamics mode to show — k_dynamics.h "Parking overwrites", NOTES 11.)
+static bool fused_collide(const mcr_env* h, hipStream_t st) { return cc_active(h) && phase_words(h, st); }
+
+// The host side of every step: the raster order list of the step's parity, the parity's device-side lists, the terminal counts; flips step_parity
+static void step_prologue(mcr_env* h, McrParams& P, hipStream_t st) {
+  const int B = P.B;
   // (the raster workgroups reset the raster order entries they consume; a step that filled the list of its parity without
   // drawing — mcr_step without an observation buffer on a handle that has one — left it unconsumed: wipe it before its next use)
   if (h->vorder_dirty[h->step_parity]) { (void)hipMemsetAsync(h->P.vcount + (size_t)h->step_parity * (B + 2) + 2, 0xff, sizeof(int32_t) * (size_t)B, st); h->vorder_dirty[h->step_parity] = false; }
-  if (!draw && h->cfg.obs_enabled) h->vorder_dirty[h->step_parity] = true;
+  if (!P.obs && h->cfg.obs_enabled) h->vorder_dirty[h->step_parity] = true;
   P.role = 0; P.split = h->split ? 1 : 0; P.defer_after = 0; P.respawn_list = 0;
-  {   // the device-side lists of a step are double-buffered by step parity: no memset, and nobody zeroes a list somebody reads
-    const size_t par = (size_t)h->step_parity, oth = par ^ 1;
-    P.clist = h->P.clist + par * (B + 1); P.clist_next = h->P.clist + oth * (B + 1);
-    P.dlist = h->P.dlist + par * (B + 1); P.rlist = h->P.rlist + par * (B + 1);
-    P.vcount = h->P.vcount + par * (B + 2); P.vorder = P.vcount + 2;
-    P.part = h->P.part + par * B; P.part_next = cc_active(h) ? h->P.part + oth * B : nullptr;
-    P.next_counts[0] = h->P.dlist + oth * (B + 1); P.next_counts[1] = h->P.rlist + oth * (B + 1);
-    P.next_counts[2] = h->P.vcount + oth * (B + 2); P.next_counts[3] = P.next_counts[2] + 1;
-    if (h->term_slab && P.obs && P.actions) { P.term_cnt = h->term_cnt2 + par * 4; P.term_cnt_next = h->term_cnt2 + oth * 4; P.term_list = h->term_list2 + par * 2 * (size_t)P.term_cap; }
-    else {
-      // a step that draws no terminal frames (no actions: frame skip, step(None); no observation buffer) still flips the parity: it zeroes
-      // the counters the NEXT step starts from in the drawing step's stead, and reports "no entries" (the next terminal step of
-      // that parity started from the counts of two steps back)
-      if (h->term_slab) {
-        (void)hipMemsetAsync(h->term_cnt2 + oth * 4, 0, sizeof(int32_t) * 4, st);
-        if (P.term_count_out) (void)hipMemsetAsync(P.term_count_out, 0, sizeof(int32_t), st);
-      }
-      P.term_cnt = P.term_cnt_next = nullptr; P.term_idx = nullptr;
+  // the device-side lists of a step are double-buffered by step parity: no memset, and nobody zeroes a list somebody reads
+  const size_t par = (size_t)h->step_parity, oth = par ^ 1;
+  P.clist = h->P.clist + par * (B + 1); P.clist_next = h->P.clist + oth * (B + 1);
+  P.dlist = h->P.dlist + par * (B + 1); P.rlist = h->P.rlist + par * (B + 1);
+  P.vcount = h->P.vcount + par * (B + 2); P.vorder = P.vcount + 2;
+  P.part = h->P.part + par * B; P.part_next = cc_active(h) ? h->P.part + oth * B : nullptr;
+  P.next_counts[0] = h->P.dlist + oth * (B + 1); P.next_counts[1] = h->P.rlist + oth * (B + 1);
+  P.next_counts[2] = h->P.vcount + oth * (B + 2); P.next_counts[3] = P.next_counts[2] + 1;
+  if (h->term_slab && P.obs && P.actions) { P.term_cnt = h->term_cnt2 + par * 4; P.term_cnt_next = h->term_cnt2 + oth * 4; P.term_list = h->term_list2 + par * 2 * (size_t)P.term_cap; }
+  else {
+    // a step that draws no terminal frames (no actions: frame skip, step(None); no observation buffer) still flips the parity: it zeroes
+    // the counters the NEXT step starts from in the drawing step's stead, and reports "no entries" (the next terminal step of
+    // that parity started from the counts of two steps back)
+    if (h->term_slab) {
+      (void)hipMemsetAsync(h->term_cnt2 + oth * 4, 0, sizeof(int32_t) * 4, st);
+      if (P.term_count_out) (void)hipMemsetAsync(P.term_count_out, 0, sizeof(int32_t), st);
     }
-    h->step_parity ^= 1;
+    P.term_cnt = P.term_cnt_next = nullptr; P.term_idx = nullptr;
   }
-  if (!h->split) {
-    // single stream: collide -> dynamics -> reset pass of the re-spawned envs (:408) -> raster -> bookkeeping, all envs
-    LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), st, P, 0);
-    LAUNCH_DYN(1, P.car_contacts && N > 1, dyn_blocks, st, P, 0);
-    if (P.auto_reset) {
-      if (P.term_cnt) hipLaunchKernelGGL(k_term_prep, dim3(B), dim3(64), 0, st, P);     // (the terminal entries of the envs that end here, before the pass clears their tile flags)
-      LAUNCH_LDS(3, k_collide, B, 64, col::lds_bytes(N), st, P, 1);
-      LAUNCH_DYN(4, P.car_contacts && N > 1, dyn_blocks, st, P, 1);
-    }
-    P.use_vorder = 1;
-    if (draw) launch_view(h, 2, B, st, P, 0);
-    P.use_vorder = 0;
-    if (P.term_cnt) { McrParams Pt = P; Pt.role = 6; launch_view(h, 7, B, st, Pt, 0); hipLaunchKernelGGL(k_term_finish, dim3(1), dim3(256), 0, st, P); }
-    if (view_flags) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, st, P);
-    return;
+  h->step_parity ^= 1;
+}
+
+// single stream: collide -> dynamics -> reset pass of the re-spawned envs (:408) -> raster -> bookkeeping, all envs
+static void step_single_stream(mcr_env* h, McrParams P, hipStream_t st, int view_flags) {
+  const int B = P.B, N = P.N, dyn_blocks = (B * P.G + 63) / 64;
+  const bool draw = P.obs != nullptr;
+  LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), st, P, 0);
+  LAUNCH_DYN(1, P.car_contacts && N > 1, dyn_blocks, st, P, 0);
+  if (P.auto_reset) {
+    if (P.term_cnt) hipLaunchKernelGGL(k_term_prep, dim3(B), dim3(64), 0, st, P);     // (the terminal entries of the envs that end here, before the pass clears their tile flags)
+    LAUNCH_LDS(3, k_collide, B, 64, col::lds_bytes(N), st, P, 1);
+    LAUNCH_DYN(4, P.car_contacts && N > 1, dyn_blocks, st, P, 1);
   }
-  // Three chains that meet again at the end (k_list_chain.h: a list chain is one fused launch + its raster):
-  //   st      : -+-> dynamics(main envs, 3 position sweeps) -+-> chain(resume the deferred envs || reset pass of the re-spawned envs) -> their raster -+
-  //   s_side  :  +-> collide(all) -> chain(contact envs) -> their raster ---------------------------------------------------------------------------+
-  //   s_defer :                                              +-> view records, bookkeeping(main envs) -> raster(main envs) -------------------------+
-  // ordered by phase words that kernels post and await (the first branch below) or by events (the second).
-  // Contact envs: a wavefront holding a touching car<->car pair takes 2-4x as long as the others.  Deferred envs: the
-  // few whose position loop is still iterating after 3 sweeps (a slow marginal crawl that would hold the whole main
-  // launch for up to 60).  Re-spawned envs (auto-reset, ~B/1000 per step): their reset pass would hold the raster of
-  // everybody else (they are not in the main raster's list, see k_dynamics).
-  P.defer_after = MCR_DEFER_AFTER; P.respawn_list = P.auto_reset ? 1 : 0; P.list_envs_per_block = MCR_SIDE_ENVS_PER_WAVE;
-  // The contact pass runs on the side stream BESIDE the main dynamics (cc_mode, mcr_kernels.h): nothing the solver needs
-  // comes from it (Car.step reads the wheels' tile bits of the PREVIOUS pass; which envs are the contact chain's follows
-  // from the entry poses), only the step's bookkeeping at the end of the dynamics kernel does, and that waits for
-  // k_collide's per-env "done" word.  24 us + a kernel boundary off the critical path.
-  // Where kernels of different streams do not overlap (mcr_create probes it: counter-collecting profilers, debuggers) the
-  // contact pass simply runs first, on the caller's stream.
-    const bool cc = cc_active(h);
-  P.cc_mode = cc ? 1 : 0; P.epoch = h->step_count; P.epoch_ptr = nullptr;
-  P.fuse_collide = fused_collide(h, st) ? 1 : 0;
-  if (h->use_graph > 0) {
-    // a replayed graph has constant arguments: the epoch lives in a device-side counter that the first node of the step advances
-    // (before the fork: the contact pass and the dynamics read the same value)
-    hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, st, h->dev_step_ctr);
-    P.epoch = 0; P.epoch_ptr = h->dev_step_ctr;
+  P.use_vorder = 1;
+  if (draw) launch_view(h, 2, B, st, P, 0);
+  P.use_vorder = 0;
+  if (P.term_cnt) { McrParams Pt = P; Pt.role = 6; launch_view(h, 7, B, st, Pt, 0); hipLaunchKernelGGL(k_term_finish, dim3(1), dim3(256), 0, st, P); }
+  if (view_flags) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, st, P);
+}
+
+// The three chains ordered by phase words (mcr_kernels.h: soft_sync) — no marker / barrier packets on any stream ([...]: with the contact pass
+// beside the dynamics, cc_active; (...): without it):
+//   s_side  : await(BEGIN) -> chain(contact envs [, each with its own contact pass in front]) -> raster -> post(SIDE)
+//   st      : (collide(all) ->) dynamics(main envs: posts BEGIN, then DYN) -> [await(COL)] chain(resume + re-spawned envs) -> raster -> await(SIDE, MAIN)
+//   s_defer : [await(BEGIN) -> collide(main envs) -> post(COL) ->] await(DYN) -> view records, bookkeeping(main envs) -> raster(main envs) -> post(MAIN)
+// (kernel trace, round 3: the resume chain starts 3 us after the dynamics instead of 11-21, the next step's dynamics 0-1 us after
+// the step's last kernel instead of 20-32; the chains' bookkeeping: list launches behind the chains; N > 3: the main envs'
+// bookkeeping on the caller's stream)
+static void step_phase_words(mcr_env* h, McrParams P, hipStream_t st, int view_flags) {
+  const int B = P.B, N = P.N, dyn_blocks = (B * P.G + 63) / 64;
+  const int lg_con = std::min(B, 2 * h->chain_grid);             // the contact chain (a list launch): one env per wavefront
+  const int prev_contacts = std::min(B, (int)((volatile uint32_t*)h->status_host)[MCR_STATUS_WORDS + HC_CONTACT_ENVS]);   // (mapped host word: no synchronisation)
+  const bool draw = P.obs != nullptr, cc = P.cc_mode != 0;
+  P.soft_sync = 1;
+  const int lg_flags = std::min(B * N, (N <= 2 ? 4 : 32) * MCR_LIST_GRID);
+  if (!cc) LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), st, P, 0);
+  // The step's critical kernel goes out FIRST (round 6): everything the other two streams run in this step waits for a word the dynamics posts
+  // (BEGIN from its first thread), so the order of enqueueing across the streams is free — and behind a host synchronisation (an RL loop
+  // reads its observations every step) the seven launches that used to precede it cost the step their enqueue time, ~45 us.
+  const int vif = (view_flags && draw && h->viewprep_in_flags) ? 1 : 0;
+  { McrParams Pd = P; Pd.split = 0; Pd.role = 1; Pd.viewprep_in_flags = vif; LAUNCH(1, k_dynamics<false>, dyn_blocks, 64, st, Pd, 0); }          // (the main envs: no touching car<->car pair)
+  hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_side, P, (int)W_BEGIN, -1);
+  if (cc) {
+    // the contact pass of the main envs on the THIRD stream (idle until the dynamics is through), the contact chain — each workgroup with its
+    // env's own contact pass in front (fuse_collide) — on the side stream from the step's begin: the chain, the step's critical path when cars
+    // pile up, does not wait for the 4096-env launch
+    hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_BEGIN, -1);
+    LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), h->s_defer, P, 0);
+    hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_COL);
   }
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(st, &capturing);
-  if (h->soft_sync && h->use_graph <= 0 && capturing == hipStreamCaptureStatusNone && stream_bound(h, st)) {
-    // ---- the three chains ordered by phase words (mcr_kernels.h: soft_sync) — no marker / barrier packets on any stream:
-    //   s_side  : await(BEGIN) -> [collide -> post(COL)] -> chain(contact envs) -> raster -> post(SIDE)
-    //   st      : [posts BEGIN] dynamics(main envs) -> [posts DYN, awaits COL] chain(resume + re-spawned envs) -> raster -> await(SIDE, MAIN)
-    //   s_defer : await(DYN, COL) -> view records -> bookkeeping(main envs) -> raster(main envs) -> post(MAIN)
-    // (kernel trace, round 3: the resume chain starts 3 us after the dynamics instead of 11-21, the next step's dynamics 0-1 us after
-    // the step's last kernel instead of 20-32; the chains' bookkeeping: list launches behind the chains; N > 3: the main envs'
-    // bookkeeping on the caller's stream)
-    P.soft_sync = 1;
-    const int lg_flags = std::min(B * N, (N <= 2 ? 4 : 32) * MCR_LIST_GRID);
-    if (!cc) LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), st, P, 0);
-    // The step's critical kernel goes out FIRST (round 6): everything the other two streams run in this step waits for a word the dynamics posts
-    // (BEGIN from its first thread), so the order of enqueueing across the streams is free — and behind a host synchronisation (an RL loop
-    // reads its observations every step) the seven launches that used to precede it cost the step their enqueue time, ~45 us.
-    const int vif = (view_flags && draw && h->viewprep_in_flags) ? 1 : 0;
-    { McrParams Pd = P; Pd.split = 0; Pd.role = 1; Pd.post_dyn = h->post_dyn ? 1 : 0; Pd.viewprep_in_flags = vif; LAUNCH(1, k_dynamics<false>, dyn_blocks, 64, st, Pd, 0); }          // (the main envs: no touching car<->car pair)
-    hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_side, P, (int)W_BEGIN, -1);
-    if (cc && !P.fuse_collide) LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), h->s_side, P, 0);     // (W_COL: posted by the chain that follows)
-    if (cc && P.fuse_collide) {
-      // the contact pass of the main envs on the THIRD stream (idle until the dynamics is through), the contact chain — each workgroup with its
-      // env's own contact pass in front — on the side stream from the step's begin: the chain, the step's critical path when cars pile up, no
-      // longer waits for the 4096-env launch
-      hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_BEGIN, -1);
-      LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), h->s_defer, P, 0);
-      hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_COL);
-    }
-    P.split = 0;
-    P.role = 2;
-    { McrParams Pc = P; Pc.list_envs_per_block = 1; LAUNCH_LDS(5, k_list_chain<true>, lg_con, 64, col::lds_bytes(N), h->s_side, Pc, Pc, 0, lg_con); }   // ONE contact env per wavefront: the uniform contact sweeps (k_dynamics.h)
-    // (the chains' bookkeeping: workgroups of its own inside the chain's raster launch when there is one, a list launch otherwise)
-    // (beyond four cars per env the lists hold thousands of cars — ~315 contact envs x 8 at N = 8 — and a few 256-thread workgroups
-    // would take them in many rounds at the end of the contact chain, the critical path there; measured N = 2 15.37 -> 15.65 M
-    // env-steps/s, N = 4 11.00 -> 11.07, N = 8 5.47 -> 5.44)
-    const int fiv = (view_flags && draw && N <= 8) ? (N <= 2 ? 8 : 64) : 0;
-    // (the contact list's raster and bookkeeping workgroups: sized by the LAST step's list — the lists change slowly — so that a long list,
-    // a policy that drives: ~90 envs of 4096, takes one round of workgroups instead of two or three behind the chain, the step's critical path)
-    const int fiv_c = fiv ? std::min(512, std::max(fiv, (prev_contacts * (N + 1) + 3) / 4 + 2)) : 0;
-    const int vg_c = std::min(2048, prev_contacts * N + prev_contacts * N / 4 + 8);
-    if (view_flags && !fiv) hipLaunchKernelGGL(k_flags_list, dim3(lg_flags), dim3(64), 0, h->s_side, P);
-    if (draw) { McrParams Pv = P; Pv.flags_blocks = fiv_c; launch_view(h, 6, P.term_cnt ? 2 * B : B, h->s_side, Pv, 0, nullptr, vg_c); }
-    hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_side, P, (int)W_SIDE);
-    P.role = 1;
-    P.viewprep_in_flags = vif;
-    const bool flags_on_caller = view_flags && draw && !P.viewprep_in_flags && N <= 7;   // (N = 8: the raster would share the machine with the bookkeeping: 6.70 -> 6.49 M env-steps/s, round 5)
-    P.role = 3;
-    {
-      const int ga = std::min(lg_dyn, MCR_LIST_GRID / 2), gb = P.auto_reset ? lg_col : 0;
-      McrParams Pr = P; Pr.role = 4; Pr.list_envs_per_block = 1;
-      LAUNCH_LDS(7, k_list_chain<false>, ga + gb, 64, col::lds_bytes(N), st, P, Pr, 0, ga);
-      if (view_flags && !fiv) hipLaunchKernelGGL(k_flags_list, dim3(lg_flags), dim3(64), 0, st, P);
-      // Beyond three cars per env the third stream's chain (bookkeeping of B*N cars, then B*N views) is the longer one and the caller's
-      // has slack: the main envs' bookkeeping — which the raster does not depend on — moves here, between the resume chain and its raster
-      if (flags_on_caller) { McrParams Pm = P; Pm.role = 1; hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, st, Pm); }
-      if (draw) { McrParams Pv = P; Pv.role = P.auto_reset ? 5 : 3; Pv.await_tail = 1; Pv.flags_blocks = fiv; launch_view(h, 7, P.term_cnt ? 2 * B : B, st, Pv, 0); }     // ... and the step's join (+ the terminal entries' frames and count)
-    }
-    P.role = 1;
-    hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_DYN, (cc && !P.fuse_collide) ? (int)W_COL : -1);
-    if (P.viewprep_in_flags) hipLaunchKernelGGL(k_flags_viewprep, dim3(dyn_blocks + B * N), dim3(64), 0, h->s_defer, P, dyn_blocks);      // view records + bookkeeping: one launch
-    else if (view_flags && !flags_on_caller) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, h->s_defer, P);
-    P.use_vorder = 1;
-    if (draw) launch_view(h, 2, B, h->s_defer, P, 0);
-    P.use_vorder = 0;
-    hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_MAIN);
-    if (!draw) hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, st, P, (int)W_SIDE, (int)W_MAIN);
-    return;
+  P.split = 0;
+  P.role = 2;
+  { McrParams Pc = P; Pc.list_envs_per_block = 1; LAUNCH_LDS(5, k_list_chain<true>, lg_con, 64, col::lds_bytes(N), h->s_side, Pc, Pc, 0, lg_con); }   // ONE contact env per wavefront: the uniform contact sweeps (k_dynamics.h)
+  // (the chains' bookkeeping: workgroups of its own inside the chain's raster launch when there is one, a list launch otherwise)
+  // (beyond four cars per env the lists hold thousands of cars — ~315 contact envs x 8 at N = 8 — and a few 256-thread workgroups
+  // would take them in many rounds at the end of the contact chain, the critical path there; measured N = 2 15.37 -> 15.65 M
+  // env-steps/s, N = 4 11.00 -> 11.07, N = 8 5.47 -> 5.44)
+  const int fiv = (view_flags && draw && N <= 8) ? (N <= 2 ? 8 : 64) : 0;
+  // (the contact list's raster and bookkeeping workgroups: sized by the LAST step's list — the lists change slowly — so that a long list,
+  // a policy that drives: ~90 envs of 4096, takes one round of workgroups instead of two or three behind the chain, the step's critical path)
+  const int fiv_c = fiv ? std::min(512, std::max(fiv, (prev_contacts * (N + 1) + 3) / 4 + 2)) : 0;
+  const int vg_c = std::min(2048, prev_contacts * N + prev_contacts * N / 4 + 8);
+  if (view_flags && !fiv) hipLaunchKernelGGL(k_flags_list, dim3(lg_flags), dim3(64), 0, h->s_side, P);
+  if (draw) { McrParams Pv = P; Pv.flags_blocks = fiv_c; launch_view(h, 6, P.term_cnt ? 2 * B : B, h->s_side, Pv, 0, nullptr, vg_c); }
+  hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_side, P, (int)W_SIDE);
+  P.viewprep_in_flags = vif;
+  const bool flags_on_caller = view_flags && draw && !P.viewprep_in_flags && N <= 7;   // (N = 8: the raster would share the machine with the bookkeeping: 6.70 -> 6.49 M env-steps/s, round 5)
+  P.role = 3;
+  {
+    const int ga = std::min({(B + MCR_SIDE_ENVS_PER_WAVE - 1) / MCR_SIDE_ENVS_PER_WAVE, h->chain_grid, MCR_LIST_GRID / 2}), gb = P.auto_reset ? std::min(B, MCR_LIST_GRID) : 0;
+    McrParams Pr = P; Pr.role = 4; Pr.list_envs_per_block = 1;
+    LAUNCH_LDS(7, k_list_chain<false>, ga + gb, 64, col::lds_bytes(N), st, P, Pr, 0, ga);
+    if (view_flags && !fiv) hipLaunchKernelGGL(k_flags_list, dim3(lg_flags), dim3(64), 0, st, P);
+    // Beyond three cars per env the third stream's chain (bookkeeping of B*N cars, then B*N views) is the longer one and the caller's
+    // has slack: the main envs' bookkeeping — which the raster does not depend on — moves here, between the resume chain and its raster
+    if (flags_on_caller) { McrParams Pm = P; Pm.role = 1; hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, st, Pm); }
+    if (draw) { McrParams Pv = P; Pv.role = P.auto_reset ? 5 : 3; Pv.await_tail = 1; Pv.flags_blocks = fiv; launch_view(h, 7, P.term_cnt ? 2 * B : B, st, Pv, 0); }     // ... and the step's join (+ the terminal entries' frames and count)
   }
-  // Events: where the kernel an event marks is known, the launch completes the event itself (hipExtLaunchKernelGGL's stop event:
-  // the dispatch packet's own completion signal).  A hipEventRecord is a marker packet BEHIND the kernel: +3 us before the next
-  // kernel of the same stream, 11 instead of 7.5 us for a dependent kernel on another stream (tools/ubench/event_gap.hip), and the
-  // step has four of them on its critical path.  Not inside a graph capture (plain records there).
-  const bool sev = h->stop_events && h->use_graph <= 0 && capturing == hipStreamCaptureStatusNone;
+  P.role = 1;
+  hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_DYN, -1);
+  if (P.viewprep_in_flags) hipLaunchKernelGGL(k_flags_viewprep, dim3(dyn_blocks + B * N), dim3(64), 0, h->s_defer, P, dyn_blocks);      // view records + bookkeeping: one launch
+  else if (view_flags && !flags_on_caller) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, h->s_defer, P);
+  P.use_vorder = 1;
+  if (draw) launch_view(h, 2, B, h->s_defer, P, 0);
+  P.use_vorder = 0;
+  hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_MAIN);
+  if (!draw) hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, st, P, (int)W_SIDE, (int)W_MAIN);
+}
+
+// The three chains ordered by events:
+//   st      : -+-> dynamics(main envs, 3 position sweeps) -+-> chain(resume the deferred envs || reset pass of the re-spawned envs) -> their raster -+
+//   s_side  :  +-> collide(all) -> chain(contact envs) -> their raster ---------------------------------------------------------------------------+
+//   s_defer :                                              +-> view records, bookkeeping(main envs) -> raster(main envs) -------------------------+
+// Where the kernel an event marks is known, the launch completes the event itself (hipExtLaunchKernelGGL's stop event:
+// the dispatch packet's own completion signal).  A hipEventRecord is a marker packet BEHIND the kernel: +3 us before the next
+// kernel of the same stream, 11 instead of 7.5 us for a dependent kernel on another stream (tools/ubench/event_gap.hip), and the
+// step has four of them on its critical path.  Not inside a graph capture (plain records there).
+static void step_events(mcr_env* h, McrParams P, hipStream_t st, int view_flags) {
+  const int B = P.B, N = P.N, dyn_blocks = (B * P.G + 63) / 64;
+  const int lg_con = std::min(B, 2 * h->chain_grid);             // the contact chain (a list launch): one env per wavefront
+  const int prev_contacts = std::min(B, (int)((volatile uint32_t*)h->status_host)[MCR_STATUS_WORDS + HC_CONTACT_ENVS]);   // (mapped host word: no synchronisation)
+  const bool draw = P.obs != nullptr, cc = P.cc_mode != 0;
+  const bool sev = h->use_graph <= 0 && !capturing(st);
 #define STOP(ev) (sev ? (ev) : (hipEvent_t) nullptr)
 #define RECORD_UNLESS_STOP(ev, stream) do { if (!sev) (void)hipEventRecord(ev, stream); } while (0)
   if (!cc) LAUNCH_LDS_STOP(0, k_collide, B, 64, col::lds_bytes(N), st, STOP(h->ev_col), P, 0);
@@ -585,20 +555,19 @@ static void launch_step(mcr_env* h, McrParams P, hipStream_t st, int view_flags)
   // round 3).  The longer chain is the resume chain (85-150 us beside the raster + its own raster, 25-70 us) — not bookkeeping + main
   // raster (40 + 100 us): it keeps the caller's stream and gets its wavefronts placed before the raster starts (a chain that starts
   // beside a raster that fills every CU runs 2-3x slower); the main envs' bookkeeping + raster take the hop to the third stream.
-  hipStream_t s_resume = st, s_mainview = h->s_defer;
   (void)hipStreamWaitEvent(h->s_defer, h->ev_fork2, 0);
-  (void)hipStreamWaitEvent(s_resume, h->ev_col, 0);              // the resume chain reads the contact pass's results of its envs (a deferred env never got to the main dynamics' in-kernel wait)
+  (void)hipStreamWaitEvent(st, h->ev_col, 0);              // the resume chain reads the contact pass's results of its envs (a deferred env never got to the main dynamics' in-kernel wait)
   if (!draw) (void)hipStreamWaitEvent(h->s_side, h->ev_fork2, 0);
   P.role = 3;
-  const hipEvent_t resume_done = nullptr;     // (the caller's stream needs no event for its own chain)
   {
     // the resume chain and — same launch, workgroups of their own — the reset pass (:408, ~50 us of serial solver work) of the
     // envs the main dynamics re-spawned; then, in one list launch, the deferred envs' frames and the re-spawned envs' first observations
-    const int ga = std::min(lg_dyn, MCR_LIST_GRID / 2), gb = P.auto_reset ? lg_col : 0;
+    // (the caller's stream needs no event for its own chain)
+    const int ga = std::min({(B + MCR_SIDE_ENVS_PER_WAVE - 1) / MCR_SIDE_ENVS_PER_WAVE, h->chain_grid, MCR_LIST_GRID / 2}), gb = P.auto_reset ? std::min(B, MCR_LIST_GRID) : 0;
     McrParams Pr = P; Pr.role = 4; Pr.list_envs_per_block = 1;     // one re-spawned env per workgroup: they run side by side
-    LAUNCH_LDS_STOP(7, k_list_chain<false>, ga + gb, 64, col::lds_bytes(N), s_resume, STOP((!draw && !flags_list) ? resume_done : nullptr), P, Pr, fuse_flags, ga);
-    if (flags_list) hipExtLaunchKernelGGL(k_flags_list, dim3(lg_flags), dim3(64), 0, s_resume, nullptr, STOP(!draw ? resume_done : nullptr), 0, P);
-    if (draw) { McrParams Pv = P; Pv.role = P.auto_reset ? 5 : 3; launch_view(h, 7, P.term_cnt ? 2 * B : B, s_resume, Pv, 0, STOP(resume_done)); }
+    LAUNCH_LDS(7, k_list_chain<false>, ga + gb, 64, col::lds_bytes(N), st, P, Pr, fuse_flags, ga);
+    if (flags_list) hipLaunchKernelGGL(k_flags_list, dim3(lg_flags), dim3(64), 0, st, P);
+    if (draw) { McrParams Pv = P; Pv.role = P.auto_reset ? 5 : 3; launch_view(h, 7, P.term_cnt ? 2 * B : B, st, Pv, 0); }
   }
   P.role = 1;
   RECORD_UNLESS_STOP(h->ev_join, h->s_side);
@@ -607,11 +576,11 @@ static void launch_step(mcr_env* h, McrParams P, hipStream_t st, int view_flags)
   // wavefronts placed: a chain that starts beside a raster that already fills every CU runs 2-3x slower (measured).
   // (k_viewprep in front of it, in-stream: the side stream may be held by a long contact chain, and a further stream slows every queue)
   const hipEvent_t main_done = h->ev_join2;
-  if (P.viewprep_in_flags) hipLaunchKernelGGL(k_viewprep, dim3(dyn_blocks), dim3(64), 0, s_mainview, P);
-  if (view_flags) hipExtLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, s_mainview, nullptr, STOP(!draw ? main_done : nullptr), 0, P);
-  (void)hipStreamWaitEvent(s_mainview, h->ev_col, 0);              // the raster reads the tiles' recolour flags (long done)
+  if (P.viewprep_in_flags) hipLaunchKernelGGL(k_viewprep, dim3(dyn_blocks), dim3(64), 0, h->s_defer, P);
+  if (view_flags) hipExtLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, h->s_defer, nullptr, STOP(!draw ? main_done : nullptr), 0, P);
+  (void)hipStreamWaitEvent(h->s_defer, h->ev_col, 0);              // the raster reads the tiles' recolour flags (long done)
   P.use_vorder = 1;
-  if (draw) launch_view(h, 2, B, s_mainview, P, 0, STOP(main_done));
+  if (draw) launch_view(h, 2, B, h->s_defer, P, 0, STOP(main_done));
   P.use_vorder = 0;
   // the join: the caller's stream waits for the other two (waiting for them one behind the other — one wait on the caller's
   // stream — costs a second hop: 23 vs 18.5 us after the later of the two, tools/ubench/event_gap.hip)
@@ -621,6 +590,35 @@ static void launch_step(mcr_env* h, McrParams P, hipStream_t st, int view_flags)
   if (P.term_cnt) hipLaunchKernelGGL(k_term_finish, dim3(1), dim3(256), 0, st, P);     // (the phase-word path: the join's workgroup does it)
 #undef STOP
 #undef RECORD_UNLESS_STOP
+}
+
+// step(): collide -> dynamics [-> auto-reset pass] -> view on the caller's stream `st`; with num_streams == 2 the step forks into three
+// chains that meet again at the end, ordered by phase words (step_phase_words) or by events (step_events); grids are sized for the worst
+// case, surplus workgroups exit on their first load.  Contact envs: a wavefront holding a touching car<->car pair takes 2-4x as long as
+// the others.  Deferred envs: the few whose position loop is still iterating after 3 sweeps (a slow marginal crawl that would hold the
+// whole main launch for up to 60).  Re-spawned envs (auto-reset, ~B/1000 per step): their reset pass would hold the raster of everybody
+// else (they are not in the main raster's list, see k_dynamics).  An env of the contact or deferred list that ended its episode in this
+// step (rare) takes its reset pass inside its own chain.
+static void launch_step(mcr_env* h, McrParams P, hipStream_t st, int view_flags) {
+  step_prologue(h, P, st);
+  if (!h->split) { step_single_stream(h, P, st, view_flags); return; }
+  P.defer_after = MCR_DEFER_AFTER; P.respawn_list = P.auto_reset ? 1 : 0; P.list_envs_per_block = MCR_SIDE_ENVS_PER_WAVE;
+  // The contact pass runs on another stream BESIDE the main dynamics (cc_mode, mcr_kernels.h): nothing the solver needs
+  // comes from it (Car.step reads the wheels' tile bits of the PREVIOUS pass; which envs are the contact chain's follows
+  // from the entry poses), only the step's bookkeeping at the end of the dynamics kernel does, and that waits for
+  // k_collide's per-env "done" word.  24 us + a kernel boundary off the critical path.
+  // Where kernels of different streams do not overlap (mcr_create probes it: counter-collecting profilers, debuggers) the
+  // contact pass simply runs first, on the caller's stream.
+  P.cc_mode = cc_active(h) ? 1 : 0; P.epoch = h->step_count; P.epoch_ptr = nullptr;
+  P.fuse_collide = fused_collide(h, st) ? 1 : 0;
+  if (h->use_graph > 0) {
+    // a replayed graph has constant arguments: the epoch lives in a device-side counter that the first node of the step advances
+    // (before the fork: the contact pass and the dynamics read the same value)
+    hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, st, h->dev_step_ctr);
+    P.epoch = 0; P.epoch_ptr = h->dev_step_ctr;
+  }
+  if (phase_words(h, st)) step_phase_words(h, P, st, view_flags);
+  else step_events(h, P, st, view_flags);
 }
 
 // The kernels report conditions that make results wrong in mapped host memory (mcr_kernels.h: ST_*); read here without
@@ -670,8 +668,7 @@ extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, doub
   if (h->use_graph <= 0) {
     // a step captured by the CALLER cannot be replayed: its launches carry this step's epoch and list parity as constants.  The supported
     // way to replay a step is mcr_set_step_graph (the handle captures both parities itself and keeps the epoch in device memory).
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) { g_err = "mcr_step inside a stream capture: use mcr_set_step_graph for graph replay"; return MCR_ERR_STATE; }
+    if (capturing(st)) { g_err = "mcr_step inside a stream capture: use mcr_set_step_graph for graph replay"; return MCR_ERR_STATE; }
   }
   McrParams P = h->P;
   P.actions = d_actions; P.obs = h->cfg.obs_enabled ? d_obs : nullptr;
@@ -740,9 +737,7 @@ extern "C" int mcr_bind_stream(mcr_env* h, void* stream) {
   for (const auto& b : h->bound) if (b.first == st) return MCR_OK;
   bool ok = false;
   if (h->split && h->soft_sync) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &cap);
-    if (cap != hipStreamCaptureStatusNone) { g_err = "mcr_bind_stream on a capturing stream"; return MCR_ERR_STATE; }
+    if (capturing(st)) { g_err = "mcr_bind_stream on a capturing stream"; return MCR_ERR_STATE; }
     HIPCHK(hipSetDevice(h->cfg.device));
     ok = kernels_overlap(h->s_side, st) && kernels_overlap(h->s_defer, st);
     // ... and of every other phase-word handle of the device: their awaits must not sit in front of this stream's posts either
@@ -1284,7 +1279,7 @@ extern "C" int mcr_debug_read_counters8(mcr_env* h, uint64_t* out8) {
 extern "C" int mcr_concurrent_collide(const mcr_env* h) { return (h && h->split && h->concurrent_collide) ? 1 : 0; }
 extern "C" int mcr_step_ordering(const mcr_env* h) {
   if (!h || !h->split) return 0;
-  return ((h->soft_sync && h->use_graph <= 0) ? 1 : 0) | (h->stop_events ? 2 : 0) | (h->soft_denied ? 4 : 0);
+  return ((h->soft_sync && h->use_graph <= 0) ? 1 : 0) | 2 | (h->soft_denied ? 4 : 0);     // (bit 1: the event path always lets the launches complete the events, outside a capture)
 }
 extern "C" int mcr_step_ordering_for(const mcr_env* h, void* stream) {
   if (!h || !h->split) return 0;

@@ -55,8 +55,6 @@ struct McrParams {
                                 // of events (marker and barrier packets that the command processor evaluates: 4-17 us each on the critical path)
   int32_t flags_blocks;         // list raster launches: the last `flags_blocks` workgroups of the grid do the bookkeeping (k_flags.h) of the list's cars, a
                                 // wavefront per car, beside the workgroups that draw them — a launch of its own for them sat between a chain and its raster
-  int32_t post_dyn;             // soft_sync, main dynamics: the LAST workgroup to finish posts W_DYN itself (a release fence per workgroup + one counter) instead of the
-                                // first thread of the kernel behind it in the stream (3-4 us later, after the dynamics' drain)
   int32_t await_tail;           // soft_sync, list raster at the tail of the caller's stream: its first workgroup ends by awaiting W_SIDE and W_MAIN — the
                                 // launch completes when the whole step has (a kernel of its own for that costs 5-7 us beside the main raster)
   int32_t cc_mode;              // 1: the main k_dynamics runs CONCURRENTLY with k_collide pass 0 (three-chain step): it finds the envs whose
@@ -141,9 +139,11 @@ __device__ __forceinline__ void mcr_raise(const McrParams& p, int w) {
 // ---- soft_sync: ordering between the step's streams without command-processor packets (tools/ubench/event_gap.hip: a
 // hipEventRecord costs the next kernel of its stream 3 us; a hipStreamWaitEvent 3 us when its event completed long ago, 7.5-11 us
 // when it completes last, and 17 us when it completed a few microseconds before the packet's turn — the queue had been parked on it).
-// A phase word holds the epoch (the handle's step counter) of the last step that reached the phase.  It is POSTED either by a
-// one-thread kernel behind the kernels of the phase, in their stream, or by the first thread of the kernel that follows them in
-// their stream: both run after the end-of-kernel release of everything before them.  It is AWAITED by a one-wavefront kernel in
+// A phase word holds the epoch (the handle's step counter) of the last step that reached the phase.  It is POSTED by a one-thread
+// kernel behind the kernels of the phase, in their stream, or by the first thread of the kernel that follows them in their stream:
+// both run after the end-of-kernel release of everything before them.  W_DYN alone is posted from inside the kernel of its phase:
+// by the last workgroup of the main dynamics to finish (k_dynamics: a release fence per workgroup, one counter, an acquire fence in
+// the last one), 3-4 us before the first thread of a kernel behind it could.  It is AWAITED by a one-wavefront kernel in
 // front of the dependent kernels, in their stream (the kernels behind it start with the usual acquire), or — k_list_chain — by a
 // kernel's prologue (poll, then one agent-scope acquire).  Waits are bounded and a give-up is reported like the contact
 // pass's (ST_SPIN_GIVEUP: mcr_step fails, the handle goes back to events).
@@ -152,11 +152,11 @@ __device__ __forceinline__ void mcr_raise(const McrParams& p, int w) {
 // memory side, not by an L2 of another XCD); the release / acquire pair the model asks for writes the XCD's dirty L2 back per post
 // (+12 us per step, measured).  include/mcr.h says so.
 enum { W_BEGIN = 0,    // the caller's stream reached this step's main dynamics (everything it held before is complete)
-       W_COL = 1,      // the contact pass (k_collide pass 0, side stream) is complete
+       W_COL = 1,      // the contact pass of the main envs (k_collide pass 0, third stream) is complete
        W_DYN = 2,      // the main dynamics is complete
        W_SIDE = 3,     // the side stream's part of the step is complete
        W_MAIN = 4,     // the third stream's part of the step is complete
-       W_DYN_COUNT = 5,// (not a phase word: workgroups of the main dynamics that are through — post_dyn)
+       W_DYN_COUNT = 5,// (not a phase word: workgroups of the main dynamics that are through, for the post of W_DYN)
        MCR_SYNC_WORDS = 8 };
 __device__ __forceinline__ void mcr_post(const McrParams& p, int w) {
   __hip_atomic_store(&p.sync_words[w * 16], mcr_epoch(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

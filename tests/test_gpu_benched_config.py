@@ -195,23 +195,29 @@ def test_physics_only_b4096_sampled_oracles(torch_cuda, oracle):
     assert n_contacts > 0, "no sampled env ever held a car<->car contact"
 
 
-@pytest.mark.parametrize("knobs, ordering", [({}, 1), ({"MCR_UNFUSED_COLLIDE": "1", "MCR_POST_DYN": "0"}, 1), ({"MCR_SOFT_SYNC": "0"}, 2), ({"MCR_SOFT_SYNC": "0", "MCR_STOP_EVENTS": "0"}, 0)])
+@pytest.mark.parametrize("knobs, ordering", [({}, 1), ({"MCR_SEQUENTIAL_COLLIDE": "1"}, 1), ({"MCR_SOFT_SYNC": "0"}, 2)])
 def test_every_stream_ordering_of_the_step_matches_the_oracle(torch_cuda, oracle, monkeypatch, knobs, ordering):
     """The three-chain step orders its streams through phase words in device memory (default where kernels overlap) or through
-    events (profilers that serialise kernels, a wait that gave up, graph capture) — completed by the launches they mark or recorded
-    behind them; with phase words the contact chain runs its envs' contact pass itself (default) or waits for the all-env pass
-    (MCR_UNFUSED_COLLIDE=1): every variant is the same computation — rear-end collisions, TimeLimit resets and refills included."""
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
+    events (profilers that serialise kernels, a wait that gave up, graph capture); with phase words the contact pass runs beside
+    the dynamics, the contact chain running its envs' own (default), or in front of it (MCR_SEQUENTIAL_COLLIDE=1, otherwise only
+    reached at large B*N): every variant is the same computation — rear-end collisions, TimeLimit resets and refills included."""
     import gc
     from multi_car_racing_amd.vec_env import VecMultiCarRacing
     gc.collect()                                             # (one phase-word handle per device at a time: no stale ones from earlier tests)
+    # whether kernels overlap here: probed before the knobs are set (MCR_SEQUENTIAL_COLLIDE=1 turns the concurrent contact pass off anyway)
     probe = VecMultiCarRacing(64, 2, seed=1, auto_reset=True, car_contacts=True, streams=2)
-    mode, overlap = probe.L.mcr_step_ordering(probe.h), probe.L.mcr_concurrent_collide(probe.h)
+    overlap = probe.L.mcr_concurrent_collide(probe.h)
+    probe.close()
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    probe = VecMultiCarRacing(64, 2, seed=1, auto_reset=True, car_contacts=True, streams=2)
+    mode, concurrent = probe.L.mcr_step_ordering(probe.h), probe.L.mcr_concurrent_collide(probe.h)
     probe.close()
     if ordering == 1 and not overlap:
         pytest.skip("kernels of different streams do not overlap here: the phase-word path is off")
     assert (mode & 1) == (ordering & 1) and (ordering == 1 or (mode & 2) == (ordering & 2)), (mode, ordering)
+    if "MCR_SEQUENTIAL_COLLIDE" in knobs:
+        assert concurrent == 0
     hot = _contact_envs(torch_cuda, 1024, 2, 33, 200, 90, True)
     n_resets, n_contacts, frozen = _run_sampled(torch_cuda, oracle, B=1024, N=2, seed=33, steps=200, n_sample=48,
                                                 max_steps=90, state_every=30, car1_floors=True, prefer=hot, masked_reset_at=(77,))
