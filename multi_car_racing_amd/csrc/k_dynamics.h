@@ -18,6 +18,7 @@
 #pragma once
 #include "mcr_kernels.h"
 #include "k_carcontacts.h"
+#include "k_carview.h"
 #include <type_traits>
 
 namespace dyn {
@@ -283,8 +284,6 @@ __device__ __forceinline__ bool joint_position(const Joint& J, Body& A, Body& B,
   A.cx = cAx; A.cy = cAy; A.a = aA; B.cx = cBx; B.cy = cBy; B.a = aB;
   return positionError <= __int_as_float(0x37d1b718) && angularError <= B2_ANGULAR_SLOP;
 }
-
-__device__ __forceinline__ double np_sign(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0); }
 
 // ---------------------------------------------------------------------------------------------------------
 // car<->car contact constraints, executed by the env's leader lane on LDS-resident body state.
@@ -705,7 +704,71 @@ __device__ __forceinline__ float cc_position_bl(const CcMass& S, const uint32_t*
   return minSep;
 }
 
+// ---- the car's solver state <-> registers: bodies, the joints' accumulated impulses and limit bits, wheel spin / stripe phase, controls.
+// car_load is every launch's prologue, the resume launch's included.  car_store is the park of a deferred env and the common part of the
+// write-back: every field car_load reads that the step has changed by the time an env is parked (the sleep timers and CU_ONROAD still hold
+// what the main launch loaded).  What only the write-back stores — sleep timers, CU_ONROAD, the reward fields — stays with it.
+__device__ __forceinline__ void car_load(const McrParams& p, const int ci, Body* b, Joint* J, double* omega, double* phase, double* gas, double& steer, double& brake,
+                                         float* sleepT, uint32_t& onroad) {
+  const int BN = p.BN;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    b[k].cx = p.carf[(CF_CX + k) * BN + ci]; b[k].cy = p.carf[(CF_CY + k) * BN + ci]; b[k].a = p.carf[(CF_A + k) * BN + ci];
+    b[k].vx = p.carf[(CF_VX + k) * BN + ci]; b[k].vy = p.carf[(CF_VY + k) * BN + ci]; b[k].w = p.carf[(CF_W + k) * BN + ci];
+    sleepT[k] = p.carf[(CF_SLEEP + k) * BN + ci];
+  }
+  const uint32_t lim = p.caru[CU_LIMIT * BN + ci];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    J[k].ix = p.carf[(CF_JIX + k) * BN + ci]; J[k].iy = p.carf[(CF_JIY + k) * BN + ci];
+    J[k].iz = p.carf[(CF_JIZ + k) * BN + ci]; J[k].im = p.carf[(CF_JM + k) * BN + ci];
+    J[k].limit = (lim >> (2 * k)) & 3;
+    omega[k] = p.card[(CD_OMEGA + k) * BN + ci]; phase[k] = p.card[(CD_PHASE + k) * BN + ci];
+  }
+  gas[0] = p.card[(CD_GAS + 0) * BN + ci]; gas[1] = p.card[(CD_GAS + 1) * BN + ci];
+  steer = p.card[CD_STEER * BN + ci]; brake = p.card[CD_BRAKE * BN + ci];
+  onroad = p.caru[CU_ONROAD * BN + ci];
+}
+__device__ __forceinline__ void car_store(const McrParams& p, const int ci, const Body* b, const Joint* J, const double* omega, const double* phase, const double* gas, const double steer, const double brake) {
+  const int BN = p.BN;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    p.carf[(CF_CX + k) * BN + ci] = b[k].cx; p.carf[(CF_CY + k) * BN + ci] = b[k].cy; p.carf[(CF_A + k) * BN + ci] = b[k].a;
+    p.carf[(CF_VX + k) * BN + ci] = b[k].vx; p.carf[(CF_VY + k) * BN + ci] = b[k].vy; p.carf[(CF_W + k) * BN + ci] = b[k].w;
+  }
+  uint32_t lim = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    p.carf[(CF_JIX + k) * BN + ci] = J[k].ix; p.carf[(CF_JIY + k) * BN + ci] = J[k].iy;
+    p.carf[(CF_JIZ + k) * BN + ci] = J[k].iz; p.carf[(CF_JM + k) * BN + ci] = J[k].im;
+    lim |= (uint32_t)J[k].limit << (2 * k);
+    p.card[(CD_OMEGA + k) * BN + ci] = omega[k]; p.card[(CD_PHASE + k) * BN + ci] = phase[k];
+  }
+  p.caru[CU_LIMIT * BN + ci] = lim;
+  p.card[(CD_GAS + 0) * BN + ci] = gas[0]; p.card[(CD_GAS + 1) * BN + ci] = gas[1];
+  p.card[CD_STEER * BN + ci] = steer; p.card[CD_BRAKE * BN + ci] = brake;
+}
+// what the view record and a terminal entry need of it
+__device__ __forceinline__ CarPose pose_of(const Body* b, const double* omega, const double* phase) {
+  CarPose c;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) { c.cx[k] = b[k].cx; c.cy[k] = b[k].cy; c.a[k] = b[k].a; }
+  c.hvx = b[0].vx; c.hvy = b[0].vy; c.hw = b[0].w;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { c.omega[k] = omega[k]; c.phase[k] = phase[k]; }
+  return c;
+}
+
 }  // namespace dyn
+
+// Car(world, angle, x, y) (multi_car_racing.py:366-406) from a slot header's spawn[agent] = (angle, x, y): the hull at the pose, the wheels at
+// UNROTATED offsets with the same angle `a`, `q = rot_of(a)`; everything else of a fresh car is zero.  Body k's sweep centre.
+__device__ __forceinline__ V2 spawn_centre(const double* sp, const Rot q, const int k, const V2 hull_lc) {
+  const double sx = sp[1], sy = sp[2];
+  Xf xf; xf.q = q;
+  xf.p = (k == 0) ? v2((float)sx, (float)sy) : v2((float)(sx + (k == 1 || k == 3 ? -55 : 55) * MCR_SIZE), (float)(sy + (k <= 2 ? 80 : -82) * MCR_SIZE));
+  return xmul(xf, (k == 0) ? hull_lc : v2(0.0f, 0.0f));
+}
 
 // mode 0: regular step (bookkeeping, TimeLimit, auto-reset install)
 // mode 1: the action-less step of reset() (:408) for envs whose `resetting` flag is set
@@ -770,26 +833,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
 #pragma unroll
   for (int k = 0; k < 4; ++k) { J[k].ix = J[k].iy = J[k].iz = J[k].im = 0.0f; J[k].limit = 0; J[k].motorSpeed = 0.0f; }
 
-  if (run) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      b[k].cx = p.carf[(CF_CX + k) * BN + ci]; b[k].cy = p.carf[(CF_CY + k) * BN + ci]; b[k].a = p.carf[(CF_A + k) * BN + ci];
-      b[k].vx = p.carf[(CF_VX + k) * BN + ci]; b[k].vy = p.carf[(CF_VY + k) * BN + ci]; b[k].w = p.carf[(CF_W + k) * BN + ci];
-      sleepT[k] = p.carf[(CF_SLEEP + k) * BN + ci];
-    }
-    uint32_t lim = p.caru[CU_LIMIT * BN + ci];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      J[k].ix = p.carf[(CF_JIX + k) * BN + ci]; J[k].iy = p.carf[(CF_JIY + k) * BN + ci];
-      J[k].iz = p.carf[(CF_JIZ + k) * BN + ci]; J[k].im = p.carf[(CF_JM + k) * BN + ci];
-      J[k].limit = (lim >> (2 * k)) & 3;
-      omega[k] = p.card[(CD_OMEGA + k) * BN + ci]; phase[k] = p.card[(CD_PHASE + k) * BN + ci];
-    }
-    gas[0] = p.card[(CD_GAS + 0) * BN + ci]; gas[1] = p.card[(CD_GAS + 1) * BN + ci];
-    steer = p.card[CD_STEER * BN + ci]; brake = p.card[CD_BRAKE * BN + ci];
-    onroad = p.caru[CU_ONROAD * BN + ci];
-
-  }
+  if (run) car_load(p, ci, b, J, omega, phase, gas, steer, brake, sleepT, onroad);
   if (run) {
     if (!resume) {
     // ---- controls (:418-424) — the reference negates the steering input
@@ -1417,23 +1461,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
       if (spin == bound) { atomicAdd(&p.counters[5], 1ull); mcr_raise(p, ST_SPIN_GIVEUP); }
     }
     if (dfr && run) {
-      // park the post-velocity-phase state exactly as the resume launch's prologue reloads it
-#pragma unroll
-      for (int k = 0; k < 5; ++k) {
-        p.carf[(CF_CX + k) * BN + ci] = b[k].cx; p.carf[(CF_CY + k) * BN + ci] = b[k].cy; p.carf[(CF_A + k) * BN + ci] = b[k].a;
-        p.carf[(CF_VX + k) * BN + ci] = b[k].vx; p.carf[(CF_VY + k) * BN + ci] = b[k].vy; p.carf[(CF_W + k) * BN + ci] = b[k].w;
-      }
-      uint32_t lim = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        p.carf[(CF_JIX + k) * BN + ci] = J[k].ix; p.carf[(CF_JIY + k) * BN + ci] = J[k].iy;
-        p.carf[(CF_JIZ + k) * BN + ci] = J[k].iz; p.carf[(CF_JM + k) * BN + ci] = J[k].im;
-        lim |= (uint32_t)J[k].limit << (2 * k);
-        p.card[(CD_OMEGA + k) * BN + ci] = omega[k]; p.card[(CD_PHASE + k) * BN + ci] = phase[k];
-      }
-      p.caru[CU_LIMIT * BN + ci] = lim;
-      p.card[(CD_GAS + 0) * BN + ci] = gas[0]; p.card[(CD_GAS + 1) * BN + ci] = gas[1];
-      p.card[CD_STEER * BN + ci] = steer; p.card[CD_BRAKE * BN + ci] = brake;
+      car_store(p, ci, b, J, omega, phase, gas, steer, brake);        // park the post-velocity-phase state exactly as the resume launch's prologue reloads it
       if (agent == 0) { p.dpart[env] = 1; p.dlist[1 + atomicAdd(&p.dlist[0], 1)] = env; atomicAdd(&p.counters[0], 1ull); }   // the main launches after this one skip it
     }
     if (dfr) { run = false; lane_ok = false; }                            // nothing below is this launch's business
@@ -1550,15 +1578,9 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
     tidx = __shfl(tidx, leader_lane);
     if (respawn && agent == 0) p.term_idx[env] = fin ? tidx : -1;
     if (fin && tidx >= 0) {
-      const int tn = p.term_cap * p.N, tc = tidx * p.N + agent;
-#pragma unroll
-      for (int k = 0; k < 5; ++k) { p.term_carf[(CF_CX + k) * tn + tc] = b[k].cx; p.term_carf[(CF_CY + k) * tn + tc] = b[k].cy; p.term_carf[(CF_A + k) * tn + tc] = b[k].a; }
-      p.term_carf[(CF_VX + 0) * tn + tc] = b[0].vx; p.term_carf[(CF_VY + 0) * tn + tc] = b[0].vy; p.term_carf[(CF_W + 0) * tn + tc] = b[0].w;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { p.term_card[(CD_OMEGA + k) * tn + tc] = omega[k]; p.term_card[(CD_PHASE + k) * tn + tc] = phase[k]; }
-      float* tvp = p.term_viewp + (size_t)tc * MCR_VIEWP_FLOATS;
-      tvp[VP_SCORE] = __int_as_float(mcr_label_value(reward_shown));
-      tvp[VP_OLDFLAGS] = __uint_as_float(flags);
+      const int tc = tidx * p.N + agent;
+      car_pose_store(p.term_carf, p.term_card, p.term_cap * p.N, tc, pose_of(b, omega, phase));       // (term_prepare reads it back)
+      view_score(p.term_viewp + (size_t)tc * MCR_VIEWP_FLOATS, reward_shown, flags);
     }
   }
 
@@ -1601,18 +1623,12 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
 
   if (run || thaw) {
   if (respawn) {
-    // Car(world, angle, x, y): hull at the pose, wheels at UNROTATED offsets with the same angle
-    const McrSlotHeader* H = (const McrSlotHeader*)(p.slots + ((size_t)env * 2 + (es.slot ^ 1)) * MCR_SLOT_BYTES);
-    double sa = H->spawn[agent][0], sx = H->spawn[agent][1], sy = H->spawn[agent][2];
-    float fa = (float)sa;
-    Rot q = rot_of(fa);
+    const double* sp = ((const McrSlotHeader*)(p.slots + ((size_t)env * 2 + (es.slot ^ 1)) * MCR_SLOT_BYTES))->spawn[agent];
+    const float fa = (float)sp[0];
+    const Rot q = rot_of(fa);
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-      float px = (k == 0) ? (float)sx : (float)(sx + (k == 1 || k == 3 ? -55 : 55) * MCR_SIZE);
-      float py = (k == 0) ? (float)sy : (float)(sy + (k <= 2 ? 80 : -82) * MCR_SIZE);
-      Xf xf; xf.p = v2(px, py); xf.q = q;
-      V2 lc = (k == 0) ? v2(lcx, lcy) : v2(0.0f, 0.0f);
-      V2 c = xmul(xf, lc);
+      const V2 c = spawn_centre(sp, q, k, v2(lcx, lcy));
       b[k].cx = c.x; b[k].cy = c.y; b[k].a = fa; b[k].vx = b[k].vy = b[k].w = 0.0f; sleepT[k] = 0.0f;
     }
 #pragma unroll
@@ -1623,163 +1639,28 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
     p.caru[CU_TVC * BN + ci] = 0;
   }
   // ---- write back
+  car_store(p, ci, b, J, omega, phase, gas, steer, brake);
 #pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    p.carf[(CF_CX + k) * BN + ci] = b[k].cx; p.carf[(CF_CY + k) * BN + ci] = b[k].cy; p.carf[(CF_A + k) * BN + ci] = b[k].a;
-    p.carf[(CF_VX + k) * BN + ci] = b[k].vx; p.carf[(CF_VY + k) * BN + ci] = b[k].vy; p.carf[(CF_W + k) * BN + ci] = b[k].w;
-    p.carf[(CF_SLEEP + k) * BN + ci] = sleepT[k];
-  }
-  uint32_t lim = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    p.carf[(CF_JIX + k) * BN + ci] = J[k].ix; p.carf[(CF_JIY + k) * BN + ci] = J[k].iy;
-    p.carf[(CF_JIZ + k) * BN + ci] = J[k].iz; p.carf[(CF_JM + k) * BN + ci] = J[k].im;
-    lim |= (uint32_t)J[k].limit << (2 * k);
-    p.card[(CD_OMEGA + k) * BN + ci] = omega[k]; p.card[(CD_PHASE + k) * BN + ci] = phase[k];
-  }
-  p.caru[CU_LIMIT * BN + ci] = lim;
+  for (int k = 0; k < 5; ++k) p.carf[(CF_SLEEP + k) * BN + ci] = sleepT[k];
   p.caru[CU_ONROAD * BN + ci] = respawn ? 0u : onroad_new;                          // this step's Collide is what the next Car.step sees
-  p.card[(CD_GAS + 0) * BN + ci] = gas[0]; p.card[(CD_GAS + 1) * BN + ci] = gas[1];
-  p.card[CD_STEER * BN + ci] = steer; p.card[CD_BRAKE * BN + ci] = brake;
   if (mode == 0) {
     p.card[CD_REWARD * BN + ci] = reward; p.card[CD_PREV_REWARD * BN + ci] = prev_reward;
     if (p.actions != nullptr || respawn) p.card[CD_EPRET * BN + ci] = epret;
     if (respawn) p.caru[CU_FLAGS * BN + ci] = 0;
   }
-  // ---- per-car view parameters for the rasteriser: one lane per agent view here instead of one redundant
-  // evaluation per raster thread there.  Camera (:540-556): f64 exactly as CPython evaluates it, then the f32
-  // values gym's Transform hands to glTranslatef/glRotatef/glScalef; HUD rectangles (:634-674).
-  float bxl = MCR_MAXFLT, byl = MCR_MAXFLT, bxh = -MCR_MAXFLT, byh = -MCR_MAXFLT;   // world box of the car's draw polygons (= its fixtures)
+  // ---- the car's view record and draw polygons for the rasteriser (k_carview.h), from the registers.  Not here: the main launch of the
+  // three-chain step (k_viewprep produces them from memory, beside the bookkeeping kernel) and the list chains (COOP: viewprep_list_block
+  // right behind this function, on five lanes per car); the two words whose values this kernel holds are written here either way.
+  CarBox box = {MCR_MAXFLT, MCR_MAXFLT, -MCR_MAXFLT, -MCR_MAXFLT};
   bool have_box = false;
-  // (three-chain step, main launch: the record and the polygons are produced by k_viewprep, beside the bookkeeping kernel,
-  // and only the two words this kernel holds are written here)
-  // (... list chains, COOP: by viewprep_list_block right behind this function, on five lanes per car)
   const bool prep_later = (p.viewprep_in_flags && p.role == 1 && mode == 0) || (COOP && mode == 0);
-  if (p.obs != nullptr && !respawn && prep_later) {
+  if (p.obs != nullptr && !respawn) {
     float* vp = p.viewp + (size_t)ci * MCR_VIEWP_FLOATS;
-    vp[VP_SCORE] = __int_as_float(mcr_label_value(reward_shown));
-    vp[VP_OLDFLAGS] = __uint_as_float(flags);
-  }
-  if (p.obs != nullptr && !respawn && !prep_later) {
-    float* vp = p.viewp + (size_t)ci * MCR_VIEWP_FLOATS;
-    const Xf hxf = xf_of(v2(b[0].cx, b[0].cy), b[0].a, v2(lcx, lcy));
-    const double t = es.t + 1.0 / MCR_FPS;
-    const double zoom = 0.1 * MCR_SCALE * fmax(1 - t, 0.0) + MCR_ZOOM * MCR_SCALE * fmin(t, 1.0);
-    const double sx = (double)hxf.p.x, sy = (double)hxf.p.y;
-    double angle = -(double)b[0].a;
-    const double vx = (double)b[0].vx, vy = (double)b[0].vy;
-    const double speed = sqrt(vx * vx + vy * vy);
-    if (speed > 0.5) angle = atan2(vx, vy);
-    double sin_a, cos_a; mcr_sincos_core(angle, &sin_a, &cos_a);     // |angle| is a few turns at most; only pixels depend on it
-    const double ttx = MCR_WINDOW_W / 2 - (sx * zoom * cos_a - sy * zoom * sin_a);
-    const double tty = MCR_WINDOW_H * p.h_ratio - (sx * zoom * sin_a + sy * zoom * cos_a);
-    const float ftx = (float)ttx, fty = (float)tty, fz = (float)zoom;
-    const float fdeg = (float)(57.29577951308232 * angle);
-    const double rad = (double)fdeg * (3.14159265358979323846 / 180.0);
-    double sin_r, cos_r; mcr_sincos_core(rad, &sin_r, &cos_r);
-    const float fcs = (float)cos_r, fsn = (float)sin_r;
-    const float kx = 96.0f / 1000.0f, ky = 96.0f / 800.0f;
-    vp[VP_CAM + 0] = fcs * fz * kx; vp[VP_CAM + 1] = -fsn * fz * kx; vp[VP_CAM + 2] = fsn * fz * ky; vp[VP_CAM + 3] = fcs * fz * ky;
-    vp[VP_CAM + 4] = ftx * kx; vp[VP_CAM + 5] = fty * ky;
-    // pixel centre -> world:  world = R^T (W - t) / zoom,  W = centre * (1000/96, 800/96)
-    const float inv_z = 1.0f / fz;
-    vp[VP_INV + 0] = fcs * (1000.0f / 96.0f) * inv_z; vp[VP_INV + 1] = fsn * (800.0f / 96.0f) * inv_z; vp[VP_INV + 2] = -(fcs * ftx + fsn * fty) * inv_z;
-    vp[VP_INV + 3] = -fsn * (1000.0f / 96.0f) * inv_z; vp[VP_INV + 4] = fcs * (800.0f / 96.0f) * inv_z; vp[VP_INV + 5] = (fsn * ftx - fcs * fty) * inv_z;
-    const double sW = MCR_WINDOW_W / 40.0, hH = MCR_WINDOW_H / 40.0;
-    const double vals[5] = {0.02 * speed, 0.01 * omega[0], 0.01 * omega[1], 0.01 * omega[2], 0.01 * omega[3]};
-    const double places[5] = {5, 7, 8, 9, 10};
-    float hud_top = 12.0f;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {                                   // vertical_ind (:643-648)
-      const float ya = (float)(hH + hH * vals[i]) * ky, yb = (float)hH * ky;
-      vp[VP_IND + i * 4 + 0] = (float)((places[i] + 0) * sW) * kx; vp[VP_IND + i * 4 + 1] = (float)((places[i] + 1) * sW) * kx;
-      vp[VP_IND + i * 4 + 2] = fminf(ya, yb); vp[VP_IND + i * 4 + 3] = fmaxf(ya, yb);
-      hud_top = fmaxf(hud_top, fmaxf(ya, yb) + 1.0f);
+    view_score(vp, reward_shown, flags);
+    if (!prep_later) {
+      box = view_record(S, pose_of(b, omega, phase), es.t + 1.0 / MCR_FPS, p.h_ratio, vp, p.carpoly + (size_t)ci * MCR_CARPOLY_FLOATS, CARVIEW_ALL);
+      have_box = true;
     }
-    const double jang = (double)(b[1].a - b[0].a);
-    const double hv[2] = {-10.0 * jang, -0.8 * (double)b[0].w};
-    const double hp[2] = {20, 30};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {                                   // horiz_ind (:649-654)
-      const float xa = (float)((hp[i] + 0) * sW) * kx, xb = (float)((hp[i] + hv[i]) * sW) * kx;
-      vp[VP_IND + (5 + i) * 4 + 0] = fminf(xa, xb); vp[VP_IND + (5 + i) * 4 + 1] = fmaxf(xa, xb);
-      vp[VP_IND + (5 + i) * 4 + 2] = (float)(2 * hH) * ky; vp[VP_IND + (5 + i) * 4 + 3] = (float)(4 * hH) * ky;
-    }
-    vp[VP_HUDTOP] = hud_top;
-    vp[VP_SCORE] = __int_as_float(mcr_label_value(reward_shown));
-    vp[VP_OLDFLAGS] = __uint_as_float(flags);                       // :669-674 draws the flag from the value the PREVIOUS step computed
-    {
-      // Light grass squares the viewport can see + "is the whole viewport inside the playfield", from the inverse camera at
-      // the four corners of the scene rectangle, in checker units U = world.x / (2k), V = world.y / (2k), k = PLAYFIELD / 20:
-      // the playfield is |U|,|V| <= 10 and light square m covers [m, m + 0.5] (:615-627).  One pixel of slack.
-      const float hk = 0.5f / (float)(MCR_PLAYFIELD / 20.0);
-      const float aU = vp[VP_INV + 0] * hk, bU = vp[VP_INV + 1] * hk, cU = vp[VP_INV + 2] * hk;
-      const float aV = vp[VP_INV + 3] * hk, bV = vp[VP_INV + 4] * hk, cV = vp[VP_INV + 5] * hk;
-      float umin = MCR_MAXFLT, umax = -MCR_MAXFLT, vmin = MCR_MAXFLT, vmax = -MCR_MAXFLT;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float X = (k & 1) ? 96.0f : 0.0f, Y = (k & 2) ? 96.0f : 12.0f;
-        const float u = aU * X + bU * Y + cU, v = aV * X + bV * Y + cV;
-        umin = fminf(umin, u); umax = fmaxf(umax, u); vmin = fminf(vmin, v); vmax = fmaxf(vmax, v);
-      }
-      const float mu = fabsf(aU) + fabsf(bU) + 1e-3f, mv = fabsf(aV) + fabsf(bV) + 1e-3f;
-      const bool inside_field = umin - mu >= -10.0f && umax + mu <= 10.0f && vmin - mv >= -10.0f && vmax + mv <= 10.0f;
-      int a0 = (int)ceilf(umin - mu - 0.5f), a1 = (int)floorf(umax + mu), b0 = (int)ceilf(vmin - mv - 0.5f), b1 = (int)floorf(vmax + mv);
-      a0 = max(a0, -10); a1 = min(a1, 9); b0 = max(b0, -10); b1 = min(b1, 9);
-      vp[VP_GRASS + 0] = __int_as_float(a0); vp[VP_GRASS + 1] = __int_as_float(max(a1 - a0 + 1, 0));
-      vp[VP_GRASS + 2] = __int_as_float(b0); vp[VP_GRASS + 3] = __int_as_float(max(b1 - b0 + 1, 0));
-      vp[VP_GRASS + 4] = __int_as_float(inside_field ? 1 : 0);
-    }
-    // world-space vertices of the 12 Car.draw polygons (trans*v in f32, as pybox2d hands them to the viewer).
-    // The record is AoS on purpose (the raster reads a car's 832 bytes as one run); every lane writes it with
-    // 16-byte stores — a polygon is 4 of them — and each distinct vertex is transformed once (padding repeats the last).
-    float4* cp4 = (float4*)(p.carpoly + (size_t)ci * MCR_CARPOLY_FLOATS);
-    int counts[12];
-    have_box = true;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const Xf wxf = xf_of(v2(b[k + 1].cx, b[k + 1].cy), b[k + 1].a, v2(0.0f, 0.0f));
-      V2 w[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { w[i] = xmul(wxf, v2(S.wheel.vx[i], S.wheel.vy[i])); bxl = mcr_min(bxl, w[i].x); bxh = mcr_max(bxh, w[i].x); byl = mcr_min(byl, w[i].y); byh = mcr_max(byh, w[i].y); }
-      float4* box = cp4 + (2 * k) * 4;
-      box[0] = make_float4(w[0].x, w[0].y, w[1].x, w[1].y); box[1] = make_float4(w[2].x, w[2].y, w[3].x, w[3].y);
-      box[2] = make_float4(w[3].x, w[3].y, w[3].x, w[3].y); box[3] = box[2];
-      counts[2 * k] = S.wheel.n;
-      const double a1 = phase[k], a2 = phase[k] + 1.2;
-      double s1, s2, c1, c2; mcr_sincos_core(a1, &s1, &c1); mcr_sincos_core(a2, &s2, &c2);   // phases stay far below the core's 1.6e6 rad range
-      int ns = 0;
-      if (!(s1 > 0 && s2 > 0)) {
-        if (s1 > 0) c1 = np_sign(c1);
-        if (s2 > 0) c2 = np_sign(c2);
-        ns = 4;
-        const float lx[4] = {(float)(-MCR_WHEEL_W * MCR_SIZE), (float)(+MCR_WHEEL_W * MCR_SIZE), (float)(+MCR_WHEEL_W * MCR_SIZE), (float)(-MCR_WHEEL_W * MCR_SIZE)};
-        const float ly[4] = {(float)(+MCR_WHEEL_R * c1 * MCR_SIZE), (float)(+MCR_WHEEL_R * c1 * MCR_SIZE), (float)(+MCR_WHEEL_R * c2 * MCR_SIZE), (float)(+MCR_WHEEL_R * c2 * MCR_SIZE)};
-        V2 u[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) u[i] = xmul(wxf, v2(lx[i], ly[i]));
-        float4* stripe = cp4 + (2 * k + 1) * 4;
-        stripe[0] = make_float4(u[0].x, u[0].y, u[1].x, u[1].y); stripe[1] = make_float4(u[2].x, u[2].y, u[3].x, u[3].y);
-        stripe[2] = make_float4(u[3].x, u[3].y, u[3].x, u[3].y); stripe[3] = stripe[2];
-      }
-      counts[2 * k + 1] = ns;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int n = __builtin_amdgcn_readfirstlane(S.hull[k].n);     // the shape table is the same for every lane: scalar loads
-      V2 w[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { if (i < n) w[i] = xmul(hxf, v2(S.hull[k].vx[i], S.hull[k].vy[i])); else w[i] = w[i - 1 < 0 ? 0 : i - 1]; }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { bxl = mcr_min(bxl, w[i].x); bxh = mcr_max(bxh, w[i].x); byl = mcr_min(byl, w[i].y); byh = mcr_max(byh, w[i].y); }
-      float4* hp = cp4 + (8 + k) * 4;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) hp[i] = make_float4(w[2 * i].x, w[2 * i].y, w[2 * i + 1].x, w[2 * i + 1].y);
-      counts[8 + k] = n;
-    }
-    float4* cn = cp4 + MCR_CARPOLY_NOFF / 4;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) cn[i] = make_float4(__int_as_float(counts[4 * i]), __int_as_float(counts[4 * i + 1]), __int_as_float(counts[4 * i + 2]), __int_as_float(counts[4 * i + 3]));
   }
   // ---- the next step's touch verdict (k_touch.h), cheap half: can ANY fixture pair of two cars of this env touch?  (2: maybe —
   // the bookkeeping kernel runs the exact test; 0: no — that is the verdict.)  A conservative filter: the boxes of the
@@ -1793,8 +1674,8 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
       for (int c = a + 1; c < p.N; ++c) {
         const float ax = __shfl(b[0].cx, lead + a), ay = __shfl(b[0].cy, lead + a), ox = __shfl(b[0].cx, lead + c), oy = __shfl(b[0].cy, lead + c);
         bool nr = (ax - ox) * (ax - ox) + (ay - oy) * (ay - oy) <= r0 * r0;
-        const float a0 = __shfl(bxl, lead + a), a1 = __shfl(byl, lead + a), a2 = __shfl(bxh, lead + a), a3 = __shfl(byh, lead + a);
-        const float c0 = __shfl(bxl, lead + c), c1 = __shfl(byl, lead + c), c2 = __shfl(bxh, lead + c), c3 = __shfl(byh, lead + c);
+        const float a0 = __shfl(box.xl, lead + a), a1 = __shfl(box.yl, lead + a), a2 = __shfl(box.xh, lead + a), a3 = __shfl(box.yh, lead + a);
+        const float c0 = __shfl(box.xl, lead + c), c1 = __shfl(box.yl, lead + c), c2 = __shfl(box.xh, lead + c), c3 = __shfl(box.yh, lead + c);
         const bool boxes = __shfl((int)have_box, lead + a) && __shfl((int)have_box, lead + c);
         if (boxes) nr = nr && !(a0 > c2 + 0.2f || a2 + 0.2f < c0 || a1 > c3 + 0.2f || a3 + 0.2f < c1);
         near = near || nr;
@@ -1856,17 +1737,12 @@ __global__ __launch_bounds__(64) void k_install(McrParams p) {
   if (!es.staged_ready) return;
   const int ci = env * p.N + agent, BN = p.BN;
   const McrShapes& S = *p.shapes;
-  const McrSlotHeader* H = (const McrSlotHeader*)(p.slots + ((size_t)env * 2 + (es.slot ^ 1)) * MCR_SLOT_BYTES);
-  double sa = H->spawn[agent][0], sx = H->spawn[agent][1], sy = H->spawn[agent][2];
-  float fa = (float)sa;
-  Rot q = rot_of(fa);
+  const double* sp = ((const McrSlotHeader*)(p.slots + ((size_t)env * 2 + (es.slot ^ 1)) * MCR_SLOT_BYTES))->spawn[agent];
+  const float fa = (float)sp[0];
+  const Rot q = rot_of(fa);
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
-    float px = (k == 0) ? (float)sx : (float)(sx + (k == 1 || k == 3 ? -55 : 55) * MCR_SIZE);
-    float py = (k == 0) ? (float)sy : (float)(sy + (k <= 2 ? 80 : -82) * MCR_SIZE);
-    Xf xf; xf.p = v2(px, py); xf.q = q;
-    V2 lc = (k == 0) ? v2(S.hull_lcx, S.hull_lcy) : v2(0.0f, 0.0f);
-    V2 c = xmul(xf, lc);
+    const V2 c = spawn_centre(sp, q, k, v2(S.hull_lcx, S.hull_lcy));
     p.carf[(CF_CX + k) * BN + ci] = c.x; p.carf[(CF_CY + k) * BN + ci] = c.y; p.carf[(CF_A + k) * BN + ci] = fa;
     p.carf[(CF_VX + k) * BN + ci] = 0.0f; p.carf[(CF_VY + k) * BN + ci] = 0.0f; p.carf[(CF_W + k) * BN + ci] = 0.0f;
     p.carf[(CF_SLEEP + k) * BN + ci] = 0.0f;

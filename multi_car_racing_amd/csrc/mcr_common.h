@@ -194,6 +194,7 @@ MCR_HD float mcr_min(float a, float b) { return a < b ? a : b; }   // std::min s
 MCR_HD float mcr_max(float a, float b) { return a < b ? b : a; }   // std::max semantics
 MCR_HD float mcr_clamp(float a, float lo, float hi) { return mcr_max(lo, mcr_min(a, hi)); }
 MCR_HD float length(V2 a) { return sqrtf(a.x * a.x + a.y * a.y); }
+MCR_HD double np_sign(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0); }   // numpy.sign
 
 // The coefficients: literals on the host; on the device words of constant memory (not `const`: the compiler must not fold them back into
 // literals) — scalar loads, hoisted out of the sweeps' loops, whose SGPR pairs v_fma_f64 takes as its addend directly.  A 64-bit literal

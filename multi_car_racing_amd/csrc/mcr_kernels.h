@@ -3,7 +3,7 @@
 #include "mcr_common.h"
 
 // Terminal observations (include/mcr.h: mcr_set_terminal_obs).  An env whose episode ends in a step that re-spawns it (auto-reset) gets an
-// ENTRY: the state its cars ended the episode with (the per-car SoA fields k_viewprep reads, at stride term_cap * N), the env's clock and the
+// ENTRY: the state its cars ended the episode with (the per-car SoA fields of a CarPose, k_carview.h, at stride term_cap * N), the env's clock and the
 // episode slot it played in; the reset pass of the env turns that into view records / car polygons and saves the tiles' recolour flags before
 // it clears them; the list raster launch of the env's chain draws the entry's N frames into the caller's buffer.
 struct McrTermEnv { double t; int32_t slot, env, consumed, pad; };

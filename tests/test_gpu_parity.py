@@ -348,7 +348,8 @@ def test_full_size_properties_and_batch_independence(torch_cuda, oracle):
 def test_side_stream_is_bit_identical_to_single_stream(torch_cuda, B, N):
     """The three-chain step only changes WHERE an env's chain runs (list chains for the contact, deferred and re-spawned
     envs, their bookkeeping in list launches; the main envs' view records in the bookkeeping launch for N <= 3, in the dynamics'
-    epilogue beyond): a rollout with auto-resets
+    epilogue beyond) and WHO feeds the one view-record function (csrc/k_carview.h: view_record) — the dynamics from its registers
+    (single stream; N >= 4), k_viewprep / the list chains from the state in memory (N <= 3): a rollout with auto-resets
     (short TimeLimit) and car<->car contacts must give identical rewards, dones, observations and state in both modes."""
     torch = torch_cuda
     seed = 11
