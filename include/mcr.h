@@ -207,7 +207,12 @@ int mcr_get_state(mcr_env* h, float* bodies, float* joints, double* wheels, int3
                   float* sleep);
 int mcr_set_bodies(mcr_env* h, const float* bodies /*[B,N,5,6]*/);
 /* reward [B,N] f64 (self.reward), tile_visited_count [B,N] i32, backward/on_grass [B,N] u8,
- * t [B] f64, tile_flags [B,MCR_TILE_CAP] u16 (bits 0..7 road_visited per agent, bit 8 recoloured) */
+ * t [B] f64, tile_flags [B,MCR_TILE_CAP] u16 (bits 0..7 road_visited per agent, bit 8 recoloured).
+ * backward / on_grass: a completed mcr_step guarantees its observations, rewards, done flags, episode statistics and
+ * terminal frames — not that these two flags of its main envs are already in device memory: on the phase-word path
+ * (N <= 3) their scans run beside the NEXT step's dynamics.  Every call that reads or writes them (this one,
+ * mcr_get_state, mcr_set_bodies, the state blobs, mcr_reset, mcr_render, mcr_destroy, a step that
+ * takes another path) launches the pending scans first: the values returned here are always those of the last step. */
 int mcr_get_env_state(mcr_env* h, double* reward, int32_t* tile_visited_count, uint8_t* backward,
                       uint8_t* on_grass, double* t, uint16_t* tile_flags, int32_t* num_tiles);
 /* hull.position per car [B,N,2] f32 */

@@ -1494,7 +1494,15 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   bool done = false, trunc = false, respawn = false;
   double step_reward = 0.0, reward = 0.0, prev_reward = 0.0, epret = 0.0;
   uint32_t tvc = 0, flags = 0;
-  if (p.cc_mode && mode == 0 && p.role == 1 && run)               // k_collide pass 0 runs beside this launch: wait until it is through with this env
+  // flags_deferred: the last step's bookkeeping of its main envs (k_flags.h) runs at THIS step's begin, on the third stream in front of the
+  // contact pass: it reads the env record, the episode slot and the entry poses and writes CU_FLAGS, which is loaded right below.  The main
+  // launch's envs are behind it by construction (k_collide starts when that launch is complete).  Who does not go through the wait for
+  // collide_epoch[env] waits — same loop — for W_COL, posted behind k_collide with this step's epoch, before it loads the flags and before
+  // it overwrites what the scans read: the contact chain (it runs its envs' contact pass itself; a solver chain of 100 us and more lies
+  // behind it here, the word is long posted) and an env of the main launch that thaws (inactive: the contact pass has no word for it).
+  // The resume chain awaits W_COL in its prologue.
+  const bool col_word = p.flags_deferred && mode == 0 && (p.role == 2 || (p.role == 1 && thaw));
+  if ((p.cc_mode && mode == 0 && p.role == 1 && run) || col_word)   // k_collide pass 0 runs beside this launch: wait until it is through with this env
   {
     // p.epoch is the handle's step counter: no earlier pass can have left the same value behind.  The wait is bounded (~3 s; on the
     // phase-word path this launch is enqueued first and the contact pass after it, on another stream, so the bound also covers the host's
@@ -1504,8 +1512,9 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
     const int bound = (p.debug & 4096) ? (1 << 14) : (1 << 24);
     const int epoch = mcr_epoch(p);
     int spin = 0;
-    if (p.debug & 2048) { for (; spin < bound && __hip_atomic_load(&p.collide_epoch[env], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != epoch; ++spin) __builtin_amdgcn_s_sleep(8); }
-    else { for (; spin < bound && __hip_atomic_load(&p.collide_epoch[env], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch; ++spin) __builtin_amdgcn_s_sleep(8); }
+    const int32_t* word = col_word ? &p.sync_words[W_COL * 16] : &p.collide_epoch[env];
+    if (p.debug & 2048) { for (; spin < bound && __hip_atomic_load(word, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != epoch; ++spin) __builtin_amdgcn_s_sleep(8); }
+    else { for (; spin < bound && __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch; ++spin) __builtin_amdgcn_s_sleep(8); }
     if (spin == bound) { atomicAdd(&p.counters[5], 1ull); mcr_raise(p, ST_SPIN_GIVEUP); }
   }
   const bool cc_wait = p.cc_mode && mode == 0 && p.role == 1;
@@ -1515,9 +1524,11 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
     reward = __longlong_as_double((long long)__hip_atomic_load((unsigned long long*)&p.card[CD_REWARD * BN + ci], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     tvc = __hip_atomic_load(&p.caru[CU_TVC * BN + ci], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     onroad_new = __hip_atomic_load(&p.caru[CU_ONROAD_NEW * BN + ci], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    prev_reward = p.card[CD_PREV_REWARD * BN + ci]; flags = p.caru[CU_FLAGS * BN + ci];
+    prev_reward = p.card[CD_PREV_REWARD * BN + ci];
+    flags = __hip_atomic_load(&p.caru[CU_FLAGS * BN + ci], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (flags_deferred: written by a launch that ran beside this one, before k_collide)
   } else if (run) {
-    reward = p.card[CD_REWARD * BN + ci]; prev_reward = p.card[CD_PREV_REWARD * BN + ci]; tvc = p.caru[CU_TVC * BN + ci]; flags = p.caru[CU_FLAGS * BN + ci];
+    reward = p.card[CD_REWARD * BN + ci]; prev_reward = p.card[CD_PREV_REWARD * BN + ci]; tvc = p.caru[CU_TVC * BN + ci];
+    flags = __hip_atomic_load(&p.caru[CU_FLAGS * BN + ci], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (the contact chain, flags_deferred: as above)
     onroad_new = p.caru[CU_ONROAD_NEW * BN + ci];
   }
   const double reward_shown = reward;      // the score label is drawn (:431) before this step's -0.1 (:437)

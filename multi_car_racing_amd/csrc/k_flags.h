@@ -1,10 +1,21 @@
-// k_flags.h — one wavefront per car: the backward / on-grass bookkeeping of multi_car_racing.py:446-495 on the poses
-// the step just produced.  Its results (`driving_backward`, `driving_on_grass`) have no reward effect (K_BACKWARD = 0,
-// :78); they reach pixels one step later (the HUD flag is drawn from LAST step's value, which k_dynamics hands to the
-// raster in the view record) and the host through mcr_get_env_state.  Round 1 computed them inside the raster kernel;
-// they are a per-car O(T + P) scan with f64 tails (atan2, fmod) that cost the raster registers, barriers and a serial
-// lane — as a kernel of its own the scan is 8,192 independent wavefronts, launched per chain as soon as that chain's
-// dynamics is done (the main envs' launch runs beside the reset pass, before the raster needs the machine).
+// k_flags.h — one wavefront per car: the backward / on-grass bookkeeping of multi_car_racing.py:446-495 on the poses a step ended with.
+// Who needs the results (`driving_backward`, `driving_on_grass`, CU_FLAGS)?  Not the step that produces them: they have no reward effect
+// (K_BACKWARD = 0, :78, :491-495), and they reach pixels one step LATER — the HUD flag of step t + 1 shows step t's value, which the
+// dynamics of step t + 1 loads and hands to the raster in the view record (VP_OLDFLAGS).  The host sees them through mcr_get_env_state, a
+// state blob and the rgb_array render (k_render.h).  Nothing mcr_step(t) hands its caller depends on step t's flags.
+// WHEN the scans run therefore depends on the step's path (mcr_hip.hip):
+//   * the list chains' envs (contact / deferred lists; the re-spawned envs take none): inside their chain's raster launch, a wavefront per car;
+//   * the main envs of the single-stream step, the event path and N > 3: a launch of the step (k_flags / k_flags_viewprep), as before;
+//   * the main envs of the phase-word step at N <= 3 (while the contact list is short): at the NEXT step's begin, on the third stream in front of k_collide, beside the main
+//     dynamics that leaves 7/8 of the machine idle — instead of 8192 wavefronts (one round of the machine, 18 us alone) in front of the main
+//     raster.  The launch scans the envs that were the step's main envs (role 1 with that step's partition marks, which are double-buffered
+//     by step parity) and reads only what stays as the step left it until the next contact pass is through with the env: the per-env
+//     "contact pass done" word holds back the end of the next dynamics (write-back, auto-reset install, parking), and the contact chain and a
+//     thawing env await W_COL (k_dynamics.h: flags_deferred).  The touch verdict of the marked envs is NOT deferred: the next step's partition
+//     needs it (k_list_chain.h: k_viewprep_verdict).  Every other reader or writer of that state flushes the pending launch first
+//     (mcr_hip.hip: flush_flags — state getters / setters, reset, render, a step on another path).
+// The scan itself: round 1 computed the flags inside the raster kernel; they are a per-car O(T + P) scan with f64 tails (atan2, fmod) that cost
+// the raster registers, barriers and a serial lane — as a kernel of its own the scan is 8,192 independent wavefronts.
 //   nearest track point (:465-467, np.linalg.norm + argmin = first minimum): f32 distances of all tiles, wave minimum,
 //     exact f64 distance for the tiles within the rounding band of that minimum, lowest index among exact ties;
 //   on grass (:470-472, shapely Point.within = strict interior): f32 bbox prefilter, exact f64 test on the polygon the

@@ -103,6 +103,18 @@ __global__ void k_await(McrParams p, int w0, int w1) {
   if (threadIdx.x == 0) { if (w0 >= 0) (void)mcr_await(p, w0); if (w1 >= 0) (void)mcr_await(p, w1); }
 }
 
+// The main envs' view records alone, and — workgroups [vp_blocks, vp_blocks + nenv), a wavefront per env — the touch verdict of the envs the
+// main dynamics marked (part_next == 2: hulls close enough for the exact test), which the NEXT step's partition needs before it begins; the
+// other wavefronts leave on their first load.  (Cars spawn side by side: with two cars per env a third of the envs is marked for hundreds of
+// steps, and 64 envs per wavefront — some twenty verdicts one after the other — took 95 us.)  What the phase-word step launches in front of
+// the main raster when it leaves the flag scans to the next step's begin (mcr_hip.hip: step_phase_words).
+__global__ __launch_bounds__(64) void k_viewprep_verdict(McrParams p, const int vp_blocks) {
+  if ((int)blockIdx.x < vp_blocks) { viewprep_block(p, (int)blockIdx.x); return; }
+  if (p.part_next == nullptr) return;
+  const int env = mcr_env_of_slot(p, (int)blockIdx.x - vp_blocks);      // (role 1: the list chains settle their envs' verdicts themselves)
+  if (env >= p.env0 + p.nenv || p.part_next[env] != 2) return;
+  verdict_block(p, env);
+}
 // The main envs' view records (k_viewprep.h, one lane per car: workgroups [0, vp_blocks)) and bookkeeping (k_flags.h, one wavefront
 // per car: the rest) in ONE launch: neither reads what the other writes, and one after the other they were 18 + 23 us in front of
 // the main raster.  Within k_flags' 64 VGPRs, so that its 8192 wavefronts still fit the chip in one round.

@@ -81,8 +81,12 @@ struct mcr_env {
   bool obs_gray = false;      // mcr_set_obs_format: the raster's GRAY instantiations ...
   McrObsRing ring{nullptr, 1, 0};   // ... and where their frames go (ring.j: set per launch)
   uint64_t obs_draws = 0;     // drawing steps enqueued (mcr_step with an observation buffer): the ring head is obs_draws mod k
+  bool flags_pending = false; // the last step left the bookkeeping of its main envs (k_flags.h) to its successor (step_phase_words): flags_P launches it
+  McrParams flags_P;          // ... the launch's parameters: role 1 with that step's partition marks (its parity's part / dpart buffers), no touch verdicts
 };
 
+static void flush_flags(mcr_env* h, hipStream_t st);
+static hipError_t sync_state(mcr_env* h);
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // Does the three-chain step run the contact pass BESIDE the main dynamics?  Only where kernels of different streams overlap
 // (probed at create), up to 7 cars per env (measured), and only for batches whose main dynamics launch puts at most one of its
@@ -205,7 +209,7 @@ extern "C" int mcr_create(const mcr_config* cfg, mcr_env** out) {
   const size_t o_ccstamp = carve(sizeof(uint32_t) * (size_t)B * mcr_cc_stamp_words(N));
   const size_t o_bpstamp = carve(sizeof(uint32_t) * (size_t)B * MCR_TILE_CAP * 4 * N);
   const size_t o_part = carve(2 * (size_t)B);                 // x2: the touch verdicts of a step live in the buffer of its parity
-  const size_t o_dpart = carve(B);
+  const size_t o_dpart = carve(2 * (size_t)B);                // x2, like part: the next step's deferred bookkeeping launch reads this step's
   const size_t o_epoch = carve(sizeof(int32_t) * ((size_t)B + 1));
   const size_t o_sync = carve(sizeof(int32_t) * 16 * MCR_SYNC_WORDS);
   const size_t o_dlist = carve(sizeof(int32_t) * 2 * ((size_t)B + 1));      // x2: the lists of a step live in the buffers of its parity
@@ -277,7 +281,7 @@ extern "C" int mcr_destroy(mcr_env* h) {
   (void)mcr_refill_stop(h);
   if (h->soft_token) { std::lock_guard<std::mutex> lk(g_soft_mu); g_soft_list.erase(std::remove(g_soft_list.begin(), g_soft_list.end(), h), g_soft_list.end()); }
   (void)hipSetDevice(h->cfg.device);
-  (void)hipDeviceSynchronize();
+  (void)sync_state(h);
   for (auto& g : h->sg) if (g.valid) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); g.valid = false; }
   for (auto& t : h->pending) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto e : h->free_events) (void)hipEventDestroy(e);
@@ -368,6 +372,23 @@ static void launch_view(mcr_env* h, int kid, int slots, hipStream_t st, const Mc
   if (tm) { if (!own_ts) (void)hipEventRecord(tl.b, st); h->pending.push_back(tl); }
 }
 
+// The bookkeeping a phase-word step left to its successor (step_phase_words), for everybody who is not that successor: whoever reads or writes what
+// the scans read or write (CU_FLAGS, poses, env records, episode slots) launches them first, on the stream its own work goes to — every state
+// getter / setter, reset, render, and a step that takes another path than the last one.  The scans depend on nothing a later call changes:
+// the poses, env records and episode slots are the ones the step ended with until the next step's dynamics writes back.
+static void flush_flags(mcr_env* h, hipStream_t st) {
+  if (!h->flags_pending) return;
+  h->flags_pending = false;
+  if (h->P.debug & (1 << 20)) return;     // debug bit 20 (tests): the pending launch is DROPPED — stale flags show that the results came through it
+  hipLaunchKernelGGL(k_flags, dim3(h->flags_P.B * h->flags_P.N), dim3(64), 0, st, h->flags_P);
+}
+// the synchronous calls (state getters / setters): the device's work is complete and so is the pending bookkeeping (null stream, waited for)
+static hipError_t sync_state(mcr_env* h) {
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess && h->flags_pending) { flush_flags(h, nullptr); e = hipDeviceSynchronize(); }
+  return e;
+}
+
 // reset(): install -> collide(1) -> dynamics(1) -> view, in order on one stream
 static void launch_reset(mcr_env* h, McrParams P, hipStream_t st) {
   const int B = P.B, N = P.N;
@@ -409,7 +430,7 @@ static void step_prologue(mcr_env* h, McrParams& P, hipStream_t st) {
   P.clist = h->P.clist + par * (B + 1); P.clist_next = h->P.clist + oth * (B + 1);
   P.dlist = h->P.dlist + par * (B + 1); P.rlist = h->P.rlist + par * (B + 1);
   P.vcount = h->P.vcount + par * (B + 2); P.vorder = P.vcount + 2;
-  P.part = h->P.part + par * B; P.part_next = cc_active(h) ? h->P.part + oth * B : nullptr;
+  P.part = h->P.part + par * B; P.part_next = cc_active(h) ? h->P.part + oth * B : nullptr; P.dpart = h->P.dpart + par * B;
   P.next_counts[0] = h->P.dlist + oth * (B + 1); P.next_counts[1] = h->P.rlist + oth * (B + 1);
   P.next_counts[2] = h->P.vcount + oth * (B + 2); P.next_counts[3] = P.next_counts[2] + 1;
   if (h->term_slab && P.obs && P.actions) { P.term_cnt = h->term_cnt2 + par * 4; P.term_cnt_next = h->term_cnt2 + oth * 4; P.term_list = h->term_list2 + par * 2 * (size_t)P.term_cap; }
@@ -448,7 +469,13 @@ static void step_single_stream(mcr_env* h, McrParams P, hipStream_t st, int view
 // beside the dynamics, cc_active; (...): without it):
 //   s_side  : await(BEGIN) -> chain(contact envs [, each with its own contact pass in front]) -> raster -> post(SIDE)
 //   st      : (collide(all) ->) dynamics(main envs: posts BEGIN, then DYN) -> [await(COL)] chain(resume + re-spawned envs) -> raster -> await(SIDE, MAIN)
-//   s_defer : [await(BEGIN) -> collide(main envs) -> post(COL) ->] await(DYN) -> view records, bookkeeping(main envs) -> raster(main envs) -> post(MAIN)
+//   s_defer : [await(BEGIN) -> {bookkeeping(the LAST step's main envs)} -> collide(main envs) -> post(COL) ->] await(DYN) -> view records, bookkeeping(main envs) -> raster(main envs) -> post(MAIN)
+// {...}: N <= 3, drawn steps with actions and the contact pass beside the dynamics.  Nothing mcr_step hands its caller depends on the step's own
+// backward / on-grass flags (k_flags.h), so the main envs' scans — 8192 wavefronts, the longest part of the launch in front of the main raster —
+// are left to the NEXT step's begin, where the main dynamics keeps one wavefront per SIMD busy and the rest of the machine idles; in front of the
+// main raster stay the view records and the touch verdicts of the marked envs (k_viewprep_verdict).  In-stream in front of k_collide: the
+// per-env "contact pass done" word that holds back the end of the dynamics (write-back, auto-reset install, parking) then also covers the scans'
+// reads, and W_COL also means "the last step's flags are written" (k_dynamics.h: flags_deferred).  Anybody else who needs them: flush_flags.
 // (kernel trace, round 3: the resume chain starts 3 us after the dynamics instead of 11-21, the next step's dynamics 0-1 us after
 // the step's last kernel instead of 20-32; the chains' bookkeeping: list launches behind the chains; N > 3: the main envs'
 // bookkeeping on the caller's stream)
@@ -464,6 +491,14 @@ static void step_phase_words(mcr_env* h, McrParams P, hipStream_t st, int view_f
   // (BEGIN from its first thread), so the order of enqueueing across the streams is free — and behind a host synchronisation (an RL loop
   // reads its observations every step) the seven launches that used to precede it cost the step their enqueue time, ~45 us.
   const int vif = (view_flags && draw && h->viewprep_in_flags) ? 1 : 0;
+  // (not with a long contact list — a policy that drives: the contact chain, which fills the machine from the step's begin, is the step's critical
+  // path then, the raster's chain has slack, and 8192 wavefronts beside the chain's first sweeps cost `--actions drive` 1.3 %, measured.  The
+  // bound is an ABSOLUTE count found at B = 4096, N = 2 (random actions: ~15 contact envs, drive: ~1000) and not verified at other batch sizes;
+  // it comes from a mapped host word read without synchronisation, so WHICH steps defer can differ between runs — results do not depend on it)
+  const bool defer_flags = vif && cc && prev_contacts <= 64 && !(P.debug & (1 << 19));     // (debug bit 19: the scans stay in their step — A/B runs)
+  if (h->flags_pending && !cc) flush_flags(h, st);                   // (mcr_step flushes for every step that cannot take the scans in: not reached)
+  const bool take_flags = h->flags_pending;
+  P.flags_deferred = take_flags ? 1 : 0;
   { McrParams Pd = P; Pd.split = 0; Pd.role = 1; Pd.viewprep_in_flags = vif; LAUNCH(1, k_dynamics<false>, dyn_blocks, 64, st, Pd, 0); }          // (the main envs: no touching car<->car pair)
   hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_side, P, (int)W_BEGIN, -1);
   if (cc) {
@@ -471,6 +506,7 @@ static void step_phase_words(mcr_env* h, McrParams P, hipStream_t st, int view_f
     // env's own contact pass in front (fuse_collide) — on the side stream from the step's begin: the chain, the step's critical path when cars
     // pile up, does not wait for the 4096-env launch
     hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_BEGIN, -1);
+    if (take_flags) flush_flags(h, h->s_defer);                      // the last step's main envs' bookkeeping: beside this step's main dynamics
     LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), h->s_defer, P, 0);
     hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_COL);
   }
@@ -504,7 +540,12 @@ static void step_phase_words(mcr_env* h, McrParams P, hipStream_t st, int view_f
   }
   P.role = 1;
   hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_DYN, -1);
-  if (P.viewprep_in_flags) hipLaunchKernelGGL(k_flags_viewprep, dim3(dyn_blocks + B * N), dim3(64), 0, h->s_defer, P, dyn_blocks);      // view records + bookkeeping: one launch
+  if (defer_flags) {
+    // view records + the marked envs' touch verdicts; the flag scans: the next step's begin (or flush_flags)
+    hipLaunchKernelGGL(k_viewprep_verdict, dim3(dyn_blocks + B), dim3(64), 0, h->s_defer, P, dyn_blocks);
+    h->flags_P = P; h->flags_P.part_next = nullptr; h->flags_P.flags_deferred = 0; h->flags_pending = true;
+  }
+  else if (P.viewprep_in_flags) hipLaunchKernelGGL(k_flags_viewprep, dim3(dyn_blocks + B * N), dim3(64), 0, h->s_defer, P, dyn_blocks);      // view records + bookkeeping: one launch
   else if (view_flags && !flags_on_caller) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, h->s_defer, P);
   P.use_vorder = 1;
   if (draw) launch_view(h, 2, B, h->s_defer, P, 0);
@@ -610,7 +651,7 @@ static void launch_step(mcr_env* h, McrParams P, hipStream_t st, int view_flags)
   // Where kernels of different streams do not overlap (mcr_create probes it: counter-collecting profilers, debuggers) the
   // contact pass simply runs first, on the caller's stream.
   P.cc_mode = cc_active(h) ? 1 : 0; P.epoch = h->step_count; P.epoch_ptr = nullptr;
-  P.fuse_collide = fused_collide(h, st) ? 1 : 0;
+  P.fuse_collide = fused_collide(h, st) ? 1 : 0; P.flags_deferred = 0;
   if (h->use_graph > 0) {
     // a replayed graph has constant arguments: the epoch lives in a device-side counter that the first node of the step advances
     // (before the fork: the contact pass and the dynamics read the same value)
@@ -653,6 +694,7 @@ extern "C" int mcr_reset(mcr_env* h, const uint8_t* d_env_mask, uint8_t* d_obs, 
   McrParams P = h->P;
   P.reset_mask = d_env_mask; P.obs = h->cfg.obs_enabled ? d_obs : nullptr; P.actions = nullptr;
   h->ring.j = (int)((h->obs_draws + (uint64_t)h->ring.k - 1u) % (uint64_t)h->ring.k);     // the head of the last drawing step: the window stays put
+  flush_flags(h, st);
   launch_reset(h, P, st);
   HIPCHK(hipGetLastError());
   h->any_reset = true; h->verdict_fresh = false;
@@ -679,6 +721,9 @@ extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, doub
   // with auto_reset, finished envs are re-spawned on the device and take the action-less first step of their
   // new episode inside this call; the view kernel always runs (it also owns the backward/on-grass flags)
   const int vf = d_actions ? 1 : 0;
+  // the bookkeeping the last step left to this one (step_phase_words) runs beside this step's main dynamics if this is a phase-word step with
+  // actions and the contact pass beside the dynamics; for any other step — single stream, events, graph capture or replay, no actions — first
+  if (h->flags_pending && !(vf && h->split && cc_active(h) && phase_words(h, st))) flush_flags(h, st);
   // (the contact list of a fused step is made by the step before it, if that one was fused too: a change of mode — another caller stream, a
   // give-up — is treated like stale verdicts one way, and empties the half-made list the other way)
   const bool fz = fused_collide(h, st);
@@ -735,6 +780,8 @@ extern "C" int mcr_bind_stream(mcr_env* h, void* stream) {
   if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   for (const auto& b : h->bound) if (b.first == st) return MCR_OK;
+  // (a pending bookkeeping launch stays pending: nothing orders `st` behind the stream the last step ran on yet, and the next mcr_step takes
+  // the scans in or flushes them on its own stream, ordered like the step itself)
   bool ok = false;
   if (h->split && h->soft_sync) {
     if (capturing(st)) { g_err = "mcr_bind_stream on a capturing stream"; return MCR_ERR_STATE; }
@@ -843,6 +890,7 @@ extern "C" int mcr_render(mcr_env* h, int env, int width, int height, uint8_t* d
   if (!h->any_reset) { g_err = "render() before reset()"; return MCR_ERR_STATE; }
   if (!h->cfg.obs_enabled) { g_err = "render() needs obs_enabled (the camera and car polygons are produced for the observation path)"; return MCR_ERR_STATE; }
   McrParams P = h->P;
+  flush_flags(h, (hipStream_t)stream);                    // (k_render.h reads CU_FLAGS itself: the frame shows the CURRENT flags)
   const dim3 grid((width + RENDER_TILE - 1) / RENDER_TILE, (height + RENDER_TILE - 1) / RENDER_TILE, P.N);
   hipLaunchKernelGGL(k_render_frame, grid, dim3(256), 0, (hipStream_t)stream, P, env, width, height, d_out);
   HIPCHK(hipGetLastError());
@@ -1061,7 +1109,7 @@ extern "C" long long mcr_refill_generated(mcr_env* h) { return (h && h->svc) ? h
 // ---------------------------------------------------------------------------- state access (synchronous)
 extern "C" int mcr_get_state(mcr_env* h, float* bodies, float* joints, double* wheels, int32_t* limit, uint8_t* on_road, float* sleep) {
   if (!h) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(sync_state(h));
   const size_t BN = h->P.BN;
   std::vector<float> cf(CF_COUNT * BN); std::vector<double> cd(CD_COUNT * BN); std::vector<uint32_t> cu(CU_COUNT * BN);
   HIPCHK(hipMemcpy(cf.data(), h->P.carf, cf.size() * 4, hipMemcpyDeviceToHost));
@@ -1090,7 +1138,7 @@ extern "C" int mcr_get_state(mcr_env* h, float* bodies, float* joints, double* w
 
 extern "C" int mcr_set_bodies(mcr_env* h, const float* bodies) {
   if (!h || !bodies) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(sync_state(h));
   const size_t BN = h->P.BN;
   std::vector<float> cf(30 * BN);
   for (size_t c = 0; c < BN; ++c) for (int k = 0; k < 5; ++k) {
@@ -1106,7 +1154,7 @@ extern "C" int mcr_set_bodies(mcr_env* h, const float* bodies) {
 extern "C" int mcr_get_env_state(mcr_env* h, double* reward, int32_t* tvc, uint8_t* backward, uint8_t* on_grass, double* t,
                                  uint16_t* tile_flags, int32_t* num_tiles) {
   if (!h) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(sync_state(h));
   const size_t BN = h->P.BN; const int B = h->P.B;
   std::vector<double> r(BN); std::vector<uint32_t> cu(CU_COUNT * BN); std::vector<McrEnvState> es(B);
   HIPCHK(hipMemcpy(r.data(), h->P.card + CD_REWARD * BN, BN * 8, hipMemcpyDeviceToHost));
@@ -1160,7 +1208,7 @@ extern "C" int mcr_get_state_blob(mcr_env* h, int env, void* blob_out) {
   if (!h || !blob_out) { g_err = "null argument"; return MCR_ERR_ARG; }
   if (env < 0 || env >= h->P.B) { g_err = "env out of range"; return MCR_ERR_ARG; }
   if (!h->any_reset) { g_err = "state snapshot before reset()"; return MCR_ERR_STATE; }
-  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(sync_state(h));
   const McrParams& P = h->P; const int N = P.N; const size_t BN = P.BN;
   const BlobLayout L = blob_layout(N, P.particles != nullptr);
   uint8_t* b = (uint8_t*)blob_out;
@@ -1199,7 +1247,7 @@ extern "C" int mcr_set_state_blob(mcr_env* h, int env, const void* blob) {
   const BlobLayout L = blob_layout(N, P.particles != nullptr);
   if (((const uint32_t*)b)[0] != BLOB_MAGIC || ((const uint32_t*)b)[1] != (uint32_t)N) { g_err = "not a state blob of this build and num_agents"; return MCR_ERR_ARG; }
   if (((const uint32_t*)b)[2] != ((P.particles ? 1u : 0u) | (P.pid_tab ? 2u : 0u)) || ((const uint32_t*)b)[3] != (uint32_t)L.total) { g_err = "state blob was taken from a handle with another skid_particles or fresh_world setting"; return MCR_ERR_ARG; }
-  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(sync_state(h));
   HIPCHK(hipMemcpy2D(P.carf + (size_t)env * N, sizeof(float) * BN, b + L.carf, sizeof(float) * N, sizeof(float) * N, CF_COUNT, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy2D(P.card + (size_t)env * N, sizeof(double) * BN, b + L.card, sizeof(double) * N, sizeof(double) * N, CD_COUNT, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy2D(P.caru + (size_t)env * N, sizeof(uint32_t) * BN, b + L.caru, sizeof(uint32_t) * N, sizeof(uint32_t) * N, CU_COUNT, hipMemcpyHostToDevice));
@@ -1305,10 +1353,11 @@ extern "C" int mcr_debug_read_partition(mcr_env* h, uint8_t* part_out, int32_t* 
 extern "C" int mcr_debug_next_verdicts(mcr_env* h, int fill_value, uint8_t* out_or_null) {
   if (!h) return MCR_ERR_ARG;
   if (!out_or_null && (fill_value & 0x100)) {     // (no synchronisation: the fill is enqueued on the null stream, in front of a step launched there)
+    flush_flags(h, nullptr);                      // (the pending bookkeeping reads that buffer as the last step's partition)
     HIPCHK(hipMemsetAsync(h->P.part + (size_t)(h->step_parity ^ 1) * h->cfg.num_envs, fill_value & 0xff, h->cfg.num_envs, 0));
     return MCR_OK;
   }
-  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(sync_state(h));
   const size_t B = h->cfg.num_envs;
   if (out_or_null) { HIPCHK(hipMemcpy(out_or_null, h->P.part + (size_t)h->step_parity * B, B, hipMemcpyDeviceToHost)); }       // (after a step: the parity has flipped)
   else { HIPCHK(hipMemset(h->P.part + (size_t)(h->step_parity ^ 1) * B, fill_value, B)); }

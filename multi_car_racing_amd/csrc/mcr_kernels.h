@@ -60,7 +60,8 @@ struct McrParams {
   int32_t cc_mode;              // 1: the main k_dynamics runs CONCURRENTLY with k_collide pass 0 (three-chain step): it finds the envs whose
                                 // car boxes overlap by itself (they are the contact chain's), and waits for collide_epoch[env] before it reads
                                 // what the collide pass produces for the step's bookkeeping (reward, tile count, wheel/tile bits)
-  uint8_t* dpart;               // [B] 1: the main k_dynamics deferred this env in this step (written for every env it handles)
+  uint8_t* dpart;               // [B] 1: the main k_dynamics deferred this env in this step (written for every env it handles); two buffers, by step parity
+                                // (the next step's deferred bookkeeping launch asks which envs were this step's main envs)
   uint32_t* particles;          // [B*N][MCR_PART_WORDS] skid particles of gym Car.step / _create_particle (drawn by render('rgb_array') only); null: not tracked
   int32_t respawn_list;         // the host runs the main envs' reset pass as a list launch (role 4)
   int32_t list_envs_per_block;  // list launches: envs a workgroup (= a wavefront) takes at a time, 1 .. MCR_SIDE_ENVS_PER_WAVE
@@ -73,6 +74,8 @@ struct McrParams {
                                 // workgroup needs to start loading); the workgroup that draws it resets it to -1
   int32_t* vcount;              // [2] number of heavy / other envs in vorder (zeroed by the previous step's main k_dynamics)
   int32_t viewprep_in_flags;    // the main envs' view records / car polygons are produced by k_viewprep (beside the bookkeeping kernel), not by the main k_dynamics' epilogue
+  int32_t flags_deferred;       // the bookkeeping of the LAST step's main envs (k_flags.h) runs at this step's begin, on the third stream in front of k_collide
+                                // (step_phase_words): W_COL and collide_epoch[env] then also mean "last step's flags are written" (k_dynamics.h awaits them)
   int32_t split_views;          // list raster launches: one workgroup per VIEW of a listed env instead of one per env
   int32_t use_vorder;           // k_view maps workgroups to envs through vorder (step path, roles 0/1)
   int32_t role;                 // 0: every env; 1: main stream (skips part envs); 2: contact envs (clist); 3: deferred envs (dlist); 4: both lists
@@ -152,7 +155,8 @@ __device__ __forceinline__ void mcr_raise(const McrParams& p, int w) {
 // memory side, not by an L2 of another XCD); the release / acquire pair the model asks for writes the XCD's dirty L2 back per post
 // (+12 us per step, measured).  include/mcr.h says so.
 enum { W_BEGIN = 0,    // the caller's stream reached this step's main dynamics (everything it held before is complete)
-       W_COL = 1,      // the contact pass of the main envs (k_collide pass 0, third stream) is complete
+       W_COL = 1,      // the contact pass of the main envs (k_collide pass 0, third stream) is complete — and so is what runs in front of it in
+                       // that stream: the bookkeeping the last step left to this one (flags_deferred)
        W_DYN = 2,      // the main dynamics is complete
        W_SIDE = 3,     // the side stream's part of the step is complete
        W_MAIN = 4,     // the third stream's part of the step is complete
