@@ -247,13 +247,9 @@ void mcr_synth_actions_host(float* out, int num_envs, int num_agents, uint64_t s
  * the auto-reset pass, 5/6 = dynamics/view of the contact side stream, 7 = its reset pass (255 = all, 0 = off).
  * mcr_timing_read synchronises the device and drains accumulated milliseconds + launch counts. */
 int mcr_timing_enable(mcr_env* h, int mask);
-/* Profiling switches, 0 in production.  Bits 0-4, 6, 7, 9, 10 are ABLATIONS (results are WRONG when set):
- *   raster: 0 skip flags block, 1 skip road shading, 2 skip cars, 3 skip write-out, 4 skip binning/cull;
- *   dynamics: 6 cap the position loops at 2 sweeps, 7 cap the velocity sweeps of contact waves at 2,
- *             9 skip the contact velocity solve, 10 skip the LDS body exchange of contact waves.
- *             14 solve car<->car contacts and joints in rounds 1-3's defined order instead of b2World::Solve's island order.
- * Bits 5, 8 and 15 only add clock stamps (raster / dynamics / contact-pass phases; 16 with 8: the velocity sweeps in a build with
- * MCR_POSLOOP_PROFILE) and leave the results untouched.  11-13: memory-ordering / starvation experiments of the tests (mcr_kernels.h). */
+/* Debug switches, 0 in production; some make the results WRONG on purpose.  Bits 5-20: enum McrDebugBit in
+ * multi_car_racing_amd/csrc/mcr_kernels.h is the one table (what each bit does, who reads it, whether results change).
+ * Bits 0-4 are ablations of the raster (results WRONG): 0 skip flags block, 1 skip road shading, 2 skip cars, 3 skip write-out, 4 skip binning/cull. */
 int mcr_debug_set(mcr_env* h, int value);
 /* debug bit 5 (32): the raster kernel stamps s_memtime per phase; read the 64-float tail of a view's scratch */
 int mcr_debug_read_view_scratch(mcr_env* h, int view, void* out, int nbytes);

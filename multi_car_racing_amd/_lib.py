@@ -11,6 +11,25 @@ QUAD_CAP = 768
 MT_WORDS = 625
 OBS_RGB, OBS_GRAY, OBS_STACK_MAX = 0, 1, 8
 
+# mcr_debug_set bits: the mirror of enum McrDebugBit (csrc/mcr_kernels.h, which says what each one does; tests/test_abi.py compares the two)
+DEBUG_VIEW_CLOCKS = 1 << 5
+DEBUG_POS_ITERS_2 = 1 << 6
+DEBUG_VEL_ITERS_2 = 1 << 7
+DEBUG_DYN_CLOCKS = 1 << 8
+DEBUG_NO_CC_VELOCITY = 1 << 9
+DEBUG_NO_CC_EXCHANGE = 1 << 10
+DEBUG_EPOCH_ACQ_REL = 1 << 11
+DEBUG_STARVED_COLLIDE = 1 << 12
+DEBUG_SHORT_AWAIT = DEBUG_SHORT_EPOCH_WAIT = DEBUG_WITHHOLD_ENV0_EPOCH = DEBUG_STARVED_COLLIDE
+DEBUG_NO_SIDE_POST = 1 << 13
+DEBUG_OLD_SOLVE_ORDER = 1 << 14
+DEBUG_COLLIDE_CLOCKS = 1 << 15
+DEBUG_DYN_CLOCKS_VEL = 1 << 16
+DEBUG_TRACE = 1 << 17
+DEBUG_SLOW_COLLIDE = 1 << 18
+DEBUG_FLAGS_IN_STEP = 1 << 19
+DEBUG_DROP_PENDING_FLAGS = 1 << 20
+
 _vp, _i, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
 
 

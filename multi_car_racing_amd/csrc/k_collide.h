@@ -89,8 +89,8 @@ __device__ __forceinline__ uint32_t wave_or(uint32_t x) {
 }  // namespace col
 
 // pass 0: every active env.  pass 1: only envs with `resetting` set (their per-tile state is cleared first).
-// debug bit 15: clock of lane 0 at the phase boundaries of the step's contact pass (tools/collide_phases.py)
-#define COL_STAMP(i) do { if ((p.debug & 32768) && pass == 0 && threadIdx.x == 0) p.dbg_stamps[(size_t)env * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
+// DEBUG_COLLIDE_CLOCKS: clock of lane 0 at the phase boundaries of the step's contact pass (tools/collide_phases.py)
+#define COL_STAMP(i) do { if ((p.debug & DEBUG_COLLIDE_CLOCKS) && pass == 0 && threadIdx.x == 0) p.dbg_stamps[(size_t)env * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
 __device__ __forceinline__ void collide_block(const McrParams& p, const int pass, const int blk) {
   using namespace col;
   const int env = mcr_env_of_slot(p, blk), lane = threadIdx.x;
@@ -113,7 +113,7 @@ __device__ __forceinline__ void collide_block(const McrParams& p, const int pass
     for (int i = 0; i < 8; ++i) { pvx[i] = P.vx[i]; pvy[i] = P.vy[i]; pnx[i] = P.nx[i]; pny[i] = P.ny[i]; }      // (all eight: no load waits for the count)
   }
   const McrEnvState es = p.env[env];
-  if (pass == 0 && p.fuse_collide && p.role < 2 && p.part[env]) return;      // a contact env: its chain's workgroup runs this pass itself (k_list_chain.h)
+  if (pass == 0 && p.fuse_collide && mcr_is_main_role(p.role) && p.part[env]) return;      // a contact env: its chain's workgroup runs this pass itself (k_list_chain.h)
   if (!es.active) {
     // contact pass in front (single stream, N > 4, serialised kernels): this pass owns the contact chain's marks — an env
     // that froze while its cars were touching must not keep a stale one (it would be skipped by every main launch)
@@ -612,7 +612,7 @@ __device__ __forceinline__ void collide_block(const McrParams& p, const int pass
           }
         }
       }
-      if (p.debug & 16384) {                                              // debug bit 14 (timing experiments): rounds 1-3's order — contacts ascending, joints 3,2,1,0
+      if (p.debug & DEBUG_OLD_SOLVE_ORDER) {                                 // (timing experiments): rounds 1-3's order — contacts ascending, joints 3,2,1,0
         for (int i = 0; i < nn; ++i) dord[i] = (uint8_t)i;
         jo = 0x1b1b1b1b1b1b1b1bull;
       }
@@ -627,7 +627,7 @@ __device__ __forceinline__ void collide_block(const McrParams& p, const int pass
   // side-stream partition: envs whose dynamics chain is going to be long (a touching car<->car pair).  cc_mode: the verdict
   // the main launches go by (p.part: mcr_touch_verdict, evaluated by last step's bookkeeping on the same poses) must
   // agree — counters[4] counts disagreements (tests and bench assert 0).
-  if (pass == 0 && lane == 0) MCR_TRACE(p, env, p.role == 2 ? 3 : 4, nn_final);                                  // (contact pass by the chain / by k_collide)
+  if (pass == 0 && lane == 0) MCR_TRACE(p, env, p.role == ROLE_CONTACT ? 3 : 4, nn_final);                                  // (contact pass by the chain / by k_collide)
   if (pass == 0 && (p.split || p.fuse_collide) && lane == 0) {
     if (nn_final > 0) { if (!p.fuse_collide) p.clist[1 + atomicAdd(&p.clist[0], 1)] = env; atomicAdd(&p.counters[2], 1ull); }     // (fuse_collide: the list was made with the verdicts)
     if (!p.cc_mode) p.part[env] = nn_final > 0 ? 1 : 0;         // the contact pass runs first: it is the one that marks the contact chain's envs
@@ -637,13 +637,13 @@ __device__ __forceinline__ void collide_block(const McrParams& p, const int pass
       p.counters[7] = (unsigned long long)(uint32_t)mcr_epoch(p);
     }
   }
-  if (pass == 0 && p.cc_mode && !((p.debug & 4096) && env == p.env0)) {     // the main dynamics, running beside this launch, may read this env's results now
-    // (debug bit 12: env 0's word is withheld — what a starved contact pass looks like to the dynamics; tests)
+  if (pass == 0 && p.cc_mode && !((p.debug & DEBUG_WITHHOLD_ENV0_EPOCH) && env == p.env0)) {     // the main dynamics, running beside this launch, may read this env's results now
+    // (DEBUG_WITHHOLD_ENV0_EPOCH: env 0's word is withheld — what a starved contact pass looks like to the dynamics; tests)
     // The three result words above left as write-through device-scope stores; "s_waitcnt vmcnt(0)" (all a workgroup-scope release
     // fence costs) holds the epoch word back until they are acknowledged by the memory side, which for write-through stores is the
     // device's coherence point.  An agent-scope RELEASE would in addition write this XCD's whole dirty L2 back (4096 times per
-    // launch: 24 -> 146 us, measured) to publish lines nobody reads across XCDs; debug bit 11 selects it for measurements.
-    if (p.debug & 2048) {
+    // launch: 24 -> 146 us, measured) to publish lines nobody reads across XCDs; DEBUG_EPOCH_ACQ_REL selects it for measurements.
+    if (p.debug & DEBUG_EPOCH_ACQ_REL) {
       __syncthreads();
       if (lane == 0) __hip_atomic_store(&p.collide_epoch[env], mcr_epoch(p), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     } else {
@@ -654,10 +654,10 @@ __device__ __forceinline__ void collide_block(const McrParams& p, const int pass
   }
 }
 
-// one workgroup per env (the list launches of roles >= 2 call collide_block from k_list_chain.h)
+// one workgroup per env (the list launches call collide_block from k_list_chain.h)
 // (4 wavefronts per SIMD = 16 per CU: with one wavefront per env the 4096 envs of the bench are resident in ONE round; LDS: see lds_bytes)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_collide(McrParams p, int pass) {
-  if ((p.debug & (1 << 18)) && pass == 0 && p.cc_mode) {                  // debug bit 18 (tests): a contact pass that is held up — every workgroup idles ~400 us first
+  if ((p.debug & DEBUG_SLOW_COLLIDE) && pass == 0 && p.cc_mode) {           // (tests): a contact pass that is held up — every workgroup idles ~400 us first
     const unsigned long long t0 = wall_clock64();
     while (wall_clock64() - t0 < 40000ull) __builtin_amdgcn_s_sleep(64);
   }

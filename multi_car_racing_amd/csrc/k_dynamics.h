@@ -10,7 +10,7 @@
 // State lives in registers for the whole step (256 VGPRs, one wavefront per SIMD): the 180x4 joint iterations are
 // a serial dependency chain, so the kernel is bound by the VALU issue of a single wave, not by HBM; loads/stores are
 // one coalesced 4- or 8-byte access per SoA field per lane.  The launch lasts as long as its slowest wavefront,
-// which is why envs with car<->car contacts (role 2) and envs with a crawling position loop (deferral, role 3)
+// which is why envs with car<->car contacts (ROLE_CONTACT) and envs with a crawling position loop (deferral, ROLE_DEFERRED)
 // run in launches of their own on other streams (mcr_hip.hip: launch_step).
 // dynamics_block<CC>: CC = false is the build without any car<->car contact code (main launch of the three-chain step, resume chain);
 // CC = true adds the contact solver (sequential Gauss-Seidel over the env's manifolds by its leader lane, bodies exchanged through LDS,
@@ -541,7 +541,7 @@ __device__ inline float cc_position(const CcMass& S, const uint32_t* rec, int le
 
 
 // ---------------------------------------------------------------------------------------------------------
-// The contact chain's form of the two solvers above (UNI): ONE env per wavefront (k_list_chain, role 2), so everything about a manifold —
+// The contact chain's form of the two solvers above (UNI): ONE env per wavefront (k_list_chain, ROLE_CONTACT), so everything about a manifold —
 // which bodies touch, the constraint record — is wave-uniform, and the wavefront's idle lanes are put to use: for the contact phase of a
 // sweep the env's bodies are laid out ONE BODY PER LANE (lane car * 5 + row holds that body's three values; the car lanes transpose their
 // registers through LDS once per sweep, in and out).  A manifold's two bodies are then read with v_readlane at a SCALAR lane index — the
@@ -772,16 +772,16 @@ __device__ __forceinline__ V2 spawn_centre(const double* sp, const Rot q, const 
 
 // mode 0: regular step (bookkeeping, TimeLimit, auto-reset install)
 // mode 1: the action-less step of reset() (:408) for envs whose `resetting` flag is set
-// debug bit 8 (256): lane 0 of every wavefront stamps the clock per phase (0 start, 1 state loaded + Car.step +
-// velocity integration, 2 velocity sweeps done, 3 position loop done, 4 end) into p.dbg_stamps[block][8] (main launch, then the launches of roles 2, 3, 4)
+// DEBUG_DYN_CLOCKS: lane 0 of every wavefront stamps the clock per phase (0 start, 1 state loaded + Car.step +
+// velocity integration, 2 velocity sweeps done, 3 position loop done, 4 end) into p.dbg_stamps[block][8] (main launch, then the launches of ROLE_CONTACT, ROLE_DEFERRED, ROLE_RESPAWN)
 #ifndef MCR_NO_PARK_WAIT
 #define MCR_NO_PARK_WAIT 0            // (1: the missing wait of rounds 3-4, to see tests/test_gpu_parity.py::test_a_late_contact_pass... fail)
 #endif
 #define UNI_I(x) __builtin_amdgcn_readfirstlane(x)
-#define DYN_STAMP(i) do { if ((p.debug & 256) && mode == 0 && threadIdx.x == 0) p.dbg_stamps[((p.role >= 2 ? (p.B * p.G + 63) / 64 + (p.role - 2) * ((p.B + 1) / 2) : 0) + blk) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
+#define DYN_STAMP(i) do { if ((p.debug & DEBUG_DYN_CLOCKS) && mode == 0 && threadIdx.x == 0) p.dbg_stamps[((mcr_is_list_role(p.role) ? mcr_dyn_blocks(p.B, p.G) + (p.role - ROLE_CONTACT) * ((p.B + 1) / 2) : 0) + blk) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
 // CC = false: a launch that cannot hold an env with touching car<->car contacts (the main launch of the three-chain step; contacts off;
 // N = 1) — none of the contact code is compiled in, and the contact-free loops keep the registers and the schedule they get alone
-// UNI (with CC): the launch holds ONE env per wavefront (the contact chain, role 2): the contact sweeps run in the uniform form above
+// UNI (with CC): the launch holds ONE env per wavefront (the contact chain, ROLE_CONTACT): the contact sweeps run in the uniform form above
 template <bool CC, bool UNI = false, bool COOP = false>
 __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mode, const int blk) {
   static_assert(CC || !UNI, "the uniform contact sweeps are part of the contact build");
@@ -800,12 +800,12 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   bool lane_ok = env < env_end && agent < p.N;
   const int ci = lane_ok ? env * p.N + agent : 0;
   const int BN = p.BN;
-  // Deferral (contact side stream configuration): the main launch (role 1) gives the position loop p.defer_after
+  // Deferral (contact side stream configuration): the main launch (ROLE_MAIN) gives the position loop p.defer_after
   // sweeps; an env with a car that is still iterating then (a slow marginal crawl, ~0.06 % of the env-steps, which
   // would otherwise hold the whole launch for up to 60 sweeps) parks its state and goes on the deferred list; the
-  // resume launch (role 3, own stream) reloads it, runs the remaining sweeps and the whole tail of the step.
-  const bool resume = p.role == 3 && mode == 0;
-  const int defer_cap = (p.role == 1 && mode == 0) ? p.defer_after : 0;
+  // resume launch (ROLE_DEFERRED, own stream) reloads it, runs the remaining sweeps and the whole tail of the step.
+  const bool resume = p.role == ROLE_DEFERRED && mode == 0;
+  const int defer_cap = (p.role == ROLE_MAIN && mode == 0) ? p.defer_after : 0;
   McrEnvState es;
   if (env < env_end) es = p.env[env]; else { es.active = 0; es.resetting = 0; }
   bool run = lane_ok && es.active;
@@ -813,7 +813,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   // Thaw: an env that finished while the host had not staged its next episode yet was frozen (inactive, zero
   // outputs).  As soon as the staged slot is filled, the next step's main launch re-spawns it exactly like the
   // auto-reset of a `done` step does (install -> reset pass -> first observation); reward/done of that step are 0.
-  const bool frozen_now = lane_ok && mode == 0 && p.role <= 1 && !es.active && es.frozen && p.auto_reset;
+  const bool frozen_now = lane_ok && mode == 0 && mcr_is_main_role(p.role) && !es.active && es.frozen && p.auto_reset;
   const bool thaw = frozen_now && es.staged_ready;
   if (frozen_now && agent == 0) atomicAdd(&p.counters[3], 1ull);          // env-steps that produced nothing
 
@@ -919,7 +919,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   // (cc_mode: the main launch's envs are those whose verdict — mcr_touch_verdict, evaluated by last step's bookkeeping on the
   // same poses with the same arithmetic — says that no car<->car fixture pair touches: k_collide, running beside this
   // launch, finds none either; its store[0] is not read)
-  if (CC && run && p.car_contacts && p.N > 1 && !(p.cc_mode && mode == 0 && p.role == 1)) ccn = (int)store[0];
+  if (CC && run && p.car_contacts && p.N > 1 && !(p.cc_mode && mode == 0 && p.role == ROLE_MAIN)) ccn = (int)store[0];
   const bool wave_cc = CC && __any(ccn > 0) != 0;
   DYN_STAMP(1);
   int pool_base = 0;
@@ -1093,7 +1093,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
       }
     }
   } else {
-    const int vel_iters = (p.debug & 128) ? 2 : 180;          // debug bit 7: timing experiments only
+    const int vel_iters = (p.debug & DEBUG_VEL_ITERS_2) ? 2 : 180;          // timing experiments only
 #ifdef MCR_POSLOOP_PROFILE
     unsigned long long vt[4] = {0, 0, 0, 0}, vt0 = 0;
 #define VP_MARK(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); vt[i] += now_ - vt0; vt0 = now_; } while (0)
@@ -1176,24 +1176,24 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
         for (int q = 3; q >= 0; --q) joint_velocity_scalar(J[q], b[0], b[q + 1], mH, iH, mW, iW, maxImpulse);
       }
       VP_MARK(0);
-      if (ccn > 0 && !(p.debug & 1024)) {
+      if (ccn > 0 && !(p.debug & DEBUG_NO_CC_EXCHANGE)) {
 #pragma unroll
         for (int k = 0; k < 5; ++k) { xv[0 * 5 + k][lane] = b[k].vx; xv[1 * 5 + k][lane] = b[k].vy; xv[2 * 5 + k][lane] = b[k].w; }
       }
       __syncthreads();
       VP_MARK(1);
-      if (ccn > 0 && agent == 0 && !(p.debug & 512)) for (int i = 0; i < ccn; ++i) cc_velocity(CM, vcpool[pool_base + i], xv);
+      if (ccn > 0 && agent == 0 && !(p.debug & DEBUG_NO_CC_VELOCITY)) for (int i = 0; i < ccn; ++i) cc_velocity(CM, vcpool[pool_base + i], xv);
       __syncthreads();
       VP_MARK(2);
-      if (ccn > 0 && !(p.debug & 1024)) {
+      if (ccn > 0 && !(p.debug & DEBUG_NO_CC_EXCHANGE)) {
 #pragma unroll
         for (int k = 0; k < 5; ++k) { b[k].vx = xv[0 * 5 + k][lane]; b[k].vy = xv[1 * 5 + k][lane]; b[k].w = xv[2 * 5 + k][lane]; }
       }
       VP_MARK(3);
     }
 #ifdef MCR_POSLOOP_PROFILE
-    if ((p.debug & 256) && (p.debug & 65536) && mode == 0 && threadIdx.x == 0 && p.role == 2) {
-      unsigned long long* o = p.dbg_stamps + ((size_t)((p.B * p.G + 63) / 64) + blk) * 8;
+    if ((p.debug & DEBUG_DYN_CLOCKS) && (p.debug & DEBUG_DYN_CLOCKS_VEL) && mode == 0 && threadIdx.x == 0 && p.role == ROLE_CONTACT) {
+      unsigned long long* o = p.dbg_stamps + ((size_t)mcr_dyn_blocks(p.B, p.G) + blk) * 8;
       o[5] = vt[0] | (vt[1] << 32); o[6] = vt[2] | (vt[3] << 32); o[7] = (unsigned long long)ccn;
     }
 #endif
@@ -1226,7 +1226,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   bool unfinished = false;                // deferral: this lane used up the main launch's sweeps without an outcome
   if (!wave_cc) {
     if (run) {
-      int it0 = 0, pos_iters = (p.debug & 64) ? 2 : 60;       // debug bit 6: cap the position iterations (timing experiments only)
+      int it0 = 0, pos_iters = (p.debug & DEBUG_POS_ITERS_2) ? 2 : 60;       // cap the position iterations (timing experiments only)
       if (defer_cap > 0 && defer_cap < pos_iters) pos_iters = defer_cap;
       bool stuck = false;
       if (resume) {
@@ -1295,7 +1295,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
       if (wave_perm) { jax[q] = pick4(wq[q], S.anchor_x[0], S.anchor_x[1], S.anchor_x[2], S.anchor_x[3]); jay[q] = pick4(wq[q], S.anchor_y[0], S.anchor_y[1], S.anchor_y[2], S.anchor_y[3]); }
       asm volatile("" : "+v"(jax[q]), "+v"(jay[q]));
     }
-    const int pos_iters_cc = (p.debug & 64) ? 2 : 60;
+    const int pos_iters_cc = (p.debug & DEBUG_POS_ITERS_2) ? 2 : 60;
 #ifdef MCR_POSLOOP_PROFILE        // build-time diagnostic (MCR_EXTRA_CFLAGS=-DMCR_POSLOOP_PROFILE, tools/posloop_profile.py): where a contact position sweep goes
     unsigned long long pt[5] = {0, 0, 0, 0, 0}, pt0 = 0; int pn = 0;
 #define PP_MARK(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); pt[i] += now_ - pt0; pt0 = now_; } while (0)
@@ -1436,8 +1436,8 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
     }
     }   // !UNI
 #ifdef MCR_POSLOOP_PROFILE
-    if ((p.debug & 256) && !(p.debug & 65536) && mode == 0 && threadIdx.x == 0 && p.role == 2) {
-      unsigned long long* o = p.dbg_stamps + ((size_t)((p.B * p.G + 63) / 64) + blk) * 8;
+    if ((p.debug & DEBUG_DYN_CLOCKS) && !(p.debug & DEBUG_DYN_CLOCKS_VEL) && mode == 0 && threadIdx.x == 0 && p.role == ROLE_CONTACT) {
+      unsigned long long* o = p.dbg_stamps + ((size_t)mcr_dyn_blocks(p.B, p.G) + blk) * 8;
       o[5] = pt[0] | ((unsigned long long)pn << 48); o[6] = pt[1] | (pt[2] << 32); o[7] = pt[3] | ((unsigned long long)ccn << 48);
     }
 #endif
@@ -1450,11 +1450,11 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
     int dfr = unfinished ? 1 : 0;
     for (int o = 1; o < p.G; o <<= 1) dfr |= __shfl_xor(dfr, o);          // env-wide: its cars finish the step together
     if (!dfr && lane_ok && agent == 0) p.dpart[env] = 0;                  // (the mark of an earlier step's deferral)
-    if (dfr && run && p.cc_mode && mode == 0 && p.role == 1 && !MCR_NO_PARK_WAIT) {
+    if (dfr && run && p.cc_mode && mode == 0 && p.role == ROLE_MAIN && !MCR_NO_PARK_WAIT) {
       // Parking overwrites the env's ENTRY poses, which the contact pass — running beside this launch — reads: not before it is through with
       // the env.  (It nearly always is by now, 90 us into this kernel; a contact pass held up for longer — a machine full of other work — is
       // not: found in round 5 as rollouts that diverged when the contact chain filled every SIMD at the step's begin.)
-      const int bound = (p.debug & 4096) ? (1 << 14) : (1 << 24);
+      const int bound = (p.debug & DEBUG_SHORT_EPOCH_WAIT) ? (1 << 14) : (1 << 24);
       const int epoch = mcr_epoch(p);
       int spin = 0;
       for (; spin < bound && __hip_atomic_load(&p.collide_epoch[env], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch; ++spin) __builtin_amdgcn_s_sleep(8);
@@ -1501,23 +1501,23 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   // it overwrites what the scans read: the contact chain (it runs its envs' contact pass itself; a solver chain of 100 us and more lies
   // behind it here, the word is long posted) and an env of the main launch that thaws (inactive: the contact pass has no word for it).
   // The resume chain awaits W_COL in its prologue.
-  const bool col_word = p.flags_deferred && mode == 0 && (p.role == 2 || (p.role == 1 && thaw));
-  if ((p.cc_mode && mode == 0 && p.role == 1 && run) || col_word)   // k_collide pass 0 runs beside this launch: wait until it is through with this env
+  const bool col_word = p.flags_deferred && mode == 0 && (p.role == ROLE_CONTACT || (p.role == ROLE_MAIN && thaw));
+  if ((p.cc_mode && mode == 0 && p.role == ROLE_MAIN && run) || col_word)   // k_collide pass 0 runs beside this launch: wait until it is through with this env
   {
     // p.epoch is the handle's step counter: no earlier pass can have left the same value behind.  The wait is bounded (~3 s; on the
     // phase-word path this launch is enqueued first and the contact pass after it, on another stream, so the bound also covers the host's
     // delay before the k_collide launch; the pass takes ~25 us and — mcr_hip.hip gates cc_mode on it — always finds room beside this launch's one
     // wavefront per SIMD); a give-up is REPORTED (status word -> mcr_step fails, the handle falls back to the contact pass in front),
-    // never silent.  debug bit 12 shortens the bound (tests).
-    const int bound = (p.debug & 4096) ? (1 << 14) : (1 << 24);
+    // never silent.  DEBUG_SHORT_EPOCH_WAIT shortens the bound (tests).
+    const int bound = (p.debug & DEBUG_SHORT_EPOCH_WAIT) ? (1 << 14) : (1 << 24);
     const int epoch = mcr_epoch(p);
     int spin = 0;
     const int32_t* word = col_word ? &p.sync_words[W_COL * 16] : &p.collide_epoch[env];
-    if (p.debug & 2048) { for (; spin < bound && __hip_atomic_load(word, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != epoch; ++spin) __builtin_amdgcn_s_sleep(8); }
+    if (p.debug & DEBUG_EPOCH_ACQ_REL) { for (; spin < bound && __hip_atomic_load(word, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != epoch; ++spin) __builtin_amdgcn_s_sleep(8); }
     else { for (; spin < bound && __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch; ++spin) __builtin_amdgcn_s_sleep(8); }
     if (spin == bound) { atomicAdd(&p.counters[5], 1ull); mcr_raise(p, ST_SPIN_GIVEUP); }
   }
-  const bool cc_wait = p.cc_mode && mode == 0 && p.role == 1;
+  const bool cc_wait = p.cc_mode && mode == 0 && p.role == ROLE_MAIN;
   uint32_t onroad_new = 0;
   if (run && cc_wait) {                                           // k_collide's three words of this car: device-scope loads (see k_collide)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -1579,7 +1579,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
     if (fin && agent == 0) {
       tidx = atomicAdd(&p.term_cnt[0], 1);
       if (tidx < p.term_cap) {
-        const int chain = p.role == 2 ? 1 : 0;
+        const int chain = p.role == ROLE_CONTACT ? 1 : 0;
         p.term_list[chain * p.term_cap + atomicAdd(&p.term_cnt[1 + chain], 1)] = tidx;
         p.term_ids[tidx] = env;
         McrTermEnv te; te.t = es.t + 1.0 / MCR_FPS; te.slot = es.slot; te.env = env; te.consumed = es.consumed + 1; te.pad = 0;
@@ -1616,9 +1616,9 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
       // (only the main launch fills the list: envs of the contact / resume launches are drawn by launches of their own, and
       // an append from those streams would race with the main raster launch that is reading the counts)
       // A re-spawned env of the main launch: with respawn_list its reset pass and first observation are list launches
-      // (role 4) of their own, beside the main raster
-      if (p.role < 2 && respawn && p.respawn_list) p.rlist[1 + atomicAdd(&p.rlist[0], 1)] = env;
-      else if (p.role < 2 && (respawn || !(done && p.auto_reset))) {
+      // (ROLE_RESPAWN) of their own, beside the main raster
+      if (mcr_is_main_role(p.role) && respawn && p.respawn_list) p.rlist[1 + atomicAdd(&p.rlist[0], 1)] = env;
+      else if (mcr_is_main_role(p.role) && (respawn || !(done && p.auto_reset))) {
         const bool heavy = respawn || es.t + 1.0 / MCR_FPS < 1.0;
         const int vslot = respawn ? (es.slot ^ 1) : es.slot;
         const int vP = ((const McrSlotHeader*)(p.slots + ((size_t)env * 2 + vslot) * MCR_SLOT_BYTES))->P;
@@ -1664,7 +1664,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   // right behind this function, on five lanes per car); the two words whose values this kernel holds are written here either way.
   CarBox box = {MCR_MAXFLT, MCR_MAXFLT, -MCR_MAXFLT, -MCR_MAXFLT};
   bool have_box = false;
-  const bool prep_later = (p.viewprep_in_flags && p.role == 1 && mode == 0) || (COOP && mode == 0);
+  const bool prep_later = (p.viewprep_in_flags && p.role == ROLE_MAIN && mode == 0) || (COOP && mode == 0);
   if (p.obs != nullptr && !respawn) {
     float* vp = p.viewp + (size_t)ci * MCR_VIEWP_FLOATS;
     view_score(vp, reward_shown, flags);
@@ -1677,7 +1677,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   // the bookkeeping kernel runs the exact test; 0: no — that is the verdict.)  A conservative filter: the boxes of the
   // draw polygons (the fixtures' own vertices) with 0.2 of slack, or — no observations, or a fresh spawn — the hull discs of
   // mcr_touch_verdict's first exit.
-  if (mode == 0 && p.role == 1 && p.part_next && p.car_contacts && p.N > 1) {
+  if (mode == 0 && p.role == ROLE_MAIN && p.part_next && p.car_contacts && p.N > 1) {
     const int lead = (int)threadIdx.x - agent;
     const float r0 = 2.0f * (fmaxf(S.pad[0], 2.5f + S.pad[1]) + 0.1f);
     bool near = false;
@@ -1691,32 +1691,32 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
         if (boxes) nr = nr && !(a0 > c2 + 0.2f || a2 + 0.2f < c0 || a1 > c3 + 0.2f || a3 + 0.2f < c1);
         near = near || nr;
       }
-    // (an env re-spawned in this step whose reset pass is a list launch of its own, role 4: that launch settles the verdict on
+    // (an env re-spawned in this step whose reset pass is a list launch of its own, ROLE_RESPAWN: that launch settles the verdict on
     // the poses it ends with — the bookkeeping kernel of the main envs, which may run beside it, must leave the env alone)
     if (agent == 0) p.part_next[env] = (near && !(respawn && p.respawn_list)) ? 2 : 0;
   }
   }   // run
   DYN_STAMP(4);
-  if (mode == 0 && lane_ok && agent == 0 && (run || thaw)) MCR_TRACE(p, env, p.role == 2 ? 0 : 1, p.role);   // (slot 0: stepped by the contact chain, 1: by anybody else)
+  if (mode == 0 && lane_ok && agent == 0 && (run || thaw)) MCR_TRACE(p, env, p.role == ROLE_CONTACT ? 0 : 1, p.role);   // (slot 0: stepped by the contact chain, 1: by anybody else)
 
 }
 
-// main launches (roles 0 / 1): 64 / G envs per wavefront (the list launches of roles >= 2 call dynamics_block from k_list_chain.h)
+// main launches (ROLE_ALL / ROLE_MAIN): 64 / G envs per wavefront (the list launches call dynamics_block from k_list_chain.h)
 template <bool CC>
 __global__ __launch_bounds__(64) void k_dynamics(McrParams p, int mode) {
   // one wavefront per SIMD whose serial chain IS the step's critical path: it goes before the wavefronts of the kernels that run beside it
   // on the same SIMDs (k_collide's 4096, the raster's tail) whenever both can issue
   __builtin_amdgcn_s_setprio(3);
   if (mode == 0 && blockIdx.x == 0 && threadIdx.x == 0) {         // the next step's lists: every reader of these buffers finished last step
-    if (p.soft_sync && p.role == 1) mcr_post(p, W_BEGIN);         // the caller's stream is here: the side stream may start this step
+    if (p.soft_sync && p.role == ROLE_MAIN) mcr_post(p, W_BEGIN);         // the caller's stream is here: the side stream may start this step
     // (fuse_collide: the next step's contact list is filled DURING this step, by verdict writers that may run while this kernel — whose
     // stores sit in its XCD's L2 until it ends — is still going: that list is emptied a step earlier, by the side stream's last kernel)
-    if (p.role == 1 && !p.fuse_collide) p.clist_next[0] = 0;
+    if (p.role == ROLE_MAIN && !p.fuse_collide) p.clist_next[0] = 0;
     for (int i = 0; i < 4; ++i) if (p.next_counts[i]) *p.next_counts[i] = 0;
     if (p.term_cnt_next) { p.term_cnt_next[0] = 0; p.term_cnt_next[1] = 0; p.term_cnt_next[2] = 0; }
   }
   dynamics_block<CC>(p, mode, (int)blockIdx.x);
-  if (mode == 0 && p.soft_sync && p.role == 1) {
+  if (mode == 0 && p.soft_sync && p.role == ROLE_MAIN) {
     // W_DYN from inside the kernel (the phase-word step's main dynamics): every workgroup (= wavefront) releases what it stored (agent scope:
     // its XCD's L2 is written back), then counts itself; the last one acquires what the others released (fence-fence synchronisation through
     // the counter's RMWs: every workgroup's stores happen before the post) and posts.  The consumer's kernels behind k_await start with the

@@ -8,7 +8,7 @@
 //   * the main envs of the single-stream step, the event path and N > 3: a launch of the step (k_flags / k_flags_viewprep), as before;
 //   * the main envs of the phase-word step at N <= 3 (while the contact list is short): at the NEXT step's begin, on the third stream in front of k_collide, beside the main
 //     dynamics that leaves 7/8 of the machine idle — instead of 8192 wavefronts (one round of the machine, 18 us alone) in front of the main
-//     raster.  The launch scans the envs that were the step's main envs (role 1 with that step's partition marks, which are double-buffered
+//     raster.  The launch scans the envs that were the step's main envs (ROLE_MAIN with that step's partition marks, which are double-buffered
 //     by step parity) and reads only what stays as the step left it until the next contact pass is through with the env: the per-env
 //     "contact pass done" word holds back the end of the next dynamics (write-back, auto-reset install, parking), and the contact chain and a
 //     thawing env await W_COL (k_dynamics.h: flags_deferred).  The touch verdict of the marked envs is NOT deferred: the next step's partition
@@ -37,7 +37,7 @@ __device__ __forceinline__ void verdict_block(const McrParams& p, const int env)
 __device__ __forceinline__ void flags_block(const McrParams& p, const int blk, const int env_of_list = -1, const bool verdict_elsewhere = false) {
   const int lane = threadIdx.x & 63;
   const int N = p.N, BN = p.BN;
-  // roles as in the other step kernels: 0 every env, 1 the main launch's envs, 2 / 3 the contact / deferred lists
+  // roles as in the other step kernels (mcr_kernels.h: McrRole)
   const int env = env_of_list >= 0 ? env_of_list : mcr_env_of_slot(p, blk / N);
   if (env >= p.env0 + p.nenv) return;
   const int ci = env * N + (env_of_list >= 0 ? blk : blk % N);
@@ -48,7 +48,7 @@ __device__ __forceinline__ void flags_block(const McrParams& p, const int blk, c
   // The mark is requested here and looked at when the scan below is done (its latency is off the wavefront's chain).
   const bool vwave = p.part_next != nullptr && !verdict_elsewhere && (env_of_list >= 0 ? blk : blk % N) == 0;
   uint32_t vmark = 0;
-  if (vwave) vmark = p.role == 1 ? (uint32_t)p.part_next[env] : 2u;
+  if (vwave) vmark = p.role == ROLE_MAIN ? (uint32_t)p.part_next[env] : 2u;
   auto settle_verdict = [&]() {
     if (vwave && vmark == 2u) {
       const bool v = mcr_touch_verdict(p, env);
@@ -163,7 +163,7 @@ __device__ __forceinline__ void flags_block(const McrParams& p, const int blk, c
   p.caru[CU_FLAGS * BN + ci] = f;
 }
 
-// one wavefront per car (the list launches of roles >= 2 call flags_block from k_list_chain.h)
+// one wavefront per car (the list launches call flags_block from k_list_chain.h)
 // 8192 wavefronts = one round on 1024 SIMDs at 8 wavefronts each: the kernel must stay within 64 VGPRs
 #ifndef MCR_DEVICE_FUNCTIONS_ONLY
 __global__ __launch_bounds__(64, 8) void k_flags(McrParams p) { flags_block(p, (int)blockIdx.x); }

@@ -1,4 +1,4 @@
-// k_list_chain.h — the step of the LIST envs (roles 2 / 3 / 4: the contact envs, the envs the main dynamics deferred, the
+// k_list_chain.h — the step of the LIST envs (ROLE_CONTACT / ROLE_DEFERRED / ROLE_RESPAWN: the contact envs, the envs the main dynamics deferred, the
 // envs it re-spawned) in as few launches as possible.  These are a handful of envs per step whose work is a serial chain
 // of solver iterations; every launch of such a chain that has to start beside the main raster — which fills every CU —
 // queues for registers and LDS and then runs 2-4x slower than alone (measured), so the chain's kernels are fused and
@@ -22,16 +22,16 @@ __device__ __forceinline__ void list_reset_pass(const McrParams& p, const int bl
   __syncthreads();
 }
 
-// roles 2 / 3: dynamics (for role 3: the rest of it) -> reset pass if the episode ended -> bookkeeping (k_flags.h).
+// ROLE_CONTACT / ROLE_DEFERRED: dynamics (for ROLE_DEFERRED: the rest of it) -> reset pass if the episode ended -> bookkeeping (k_flags.h).
 // The launch can carry a SECOND list with its own parameter block: workgroups [ga, gridDim) run the reset pass of the envs the
-// main dynamics re-spawned (role 4, what k_reset_list does) beside the chain of the first list — one launch, so that neither
+// main dynamics re-spawned (ROLE_RESPAWN, what k_reset_list does) beside the chain of the first list — one launch, so that neither
 // waits for the other in a stream (the re-spawned envs used to queue behind the contact chain, which is long in 1 step of 6).
-// CC = false: the first list holds no env with touching car<->car contacts (role 3: the deferred envs) — its dynamics are the contact-free build
+// CC = false: the first list holds no env with touching car<->car contacts (ROLE_DEFERRED: the deferred envs) — its dynamics are the contact-free build
 template <bool CC>
 __global__ __launch_bounds__(64) void k_list_chain(McrParams pa, McrParams pb, const int with_flags, const int ga) {
   __builtin_amdgcn_s_setprio(3);
-  if (pa.role == 2 && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&pa.host_counts[HC_CONTACT_ENVS], (uint32_t)pa.clist[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (the contact pass is complete: the list is)
-  if (pa.soft_sync && pa.role == 3 && pa.cc_mode) {
+  if (pa.role == ROLE_CONTACT && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&pa.host_counts[HC_CONTACT_ENVS], (uint32_t)pa.clist[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (the contact pass is complete: the list is)
+  if (pa.soft_sync && pa.role == ROLE_DEFERRED && pa.cc_mode) {
     // soft_sync (mcr_kernels.h), the resume chain: its envs read what the contact pass of the third stream left for them (a deferred env never
     // got to the main dynamics' in-kernel wait)
     if (threadIdx.x == 0) (void)mcr_await(pa, W_COL);
@@ -92,12 +92,12 @@ __global__ void k_term_finish(McrParams p) { term_finish(p); }
 __global__ __launch_bounds__(64) void k_term_prep(McrParams p) { term_prepare(p, p.env0 + (int)blockIdx.x); }
 
 // soft_sync's one-thread kernels (see mcr_post / mcr_await)
-// (debug bit 13: the side stream's completion is never posted — what a stalled stream looks like to the step's join; tests)
+// (DEBUG_NO_SIDE_POST: the side stream's completion is never posted — what a stalled stream looks like to the step's join; tests)
 // (fuse_collide, side stream: this step's contact list has had its last reader — the chain and its raster — and is the list the NEXT step's
 // verdict writers fill: emptied here, a kernel boundary and a whole step ahead of the first append)
 __global__ void k_post(McrParams p, int w) {
   if (threadIdx.x == 0 && w == W_SIDE && p.fuse_collide) p.clist[0] = 0;
-  if (threadIdx.x == 0 && !((p.debug & 8192) && w == W_SIDE)) mcr_post(p, w);
+  if (threadIdx.x == 0 && !((p.debug & DEBUG_NO_SIDE_POST) && w == W_SIDE)) mcr_post(p, w);
 }
 __global__ void k_await(McrParams p, int w0, int w1) {
   if (threadIdx.x == 0) { if (w0 >= 0) (void)mcr_await(p, w0); if (w1 >= 0) (void)mcr_await(p, w1); }
@@ -111,7 +111,7 @@ __global__ void k_await(McrParams p, int w0, int w1) {
 __global__ __launch_bounds__(64) void k_viewprep_verdict(McrParams p, const int vp_blocks) {
   if ((int)blockIdx.x < vp_blocks) { viewprep_block(p, (int)blockIdx.x); return; }
   if (p.part_next == nullptr) return;
-  const int env = mcr_env_of_slot(p, (int)blockIdx.x - vp_blocks);      // (role 1: the list chains settle their envs' verdicts themselves)
+  const int env = mcr_env_of_slot(p, (int)blockIdx.x - vp_blocks);      // (ROLE_MAIN: the list chains settle their envs' verdicts themselves)
   if (env >= p.env0 + p.nenv || p.part_next[env] != 2) return;
   verdict_block(p, env);
 }

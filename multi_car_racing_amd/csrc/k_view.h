@@ -236,7 +236,7 @@ __device__ __forceinline__ void hud_store(const HudState& H, uint32_t* __restric
 
 }  // namespace view
 
-// per-phase clock accumulators of thread 0 (the PHASES instantiation, launched when debug bit 32 is set): [view][16] u64,
+// per-phase clock accumulators of thread 0 (the PHASES instantiation, launched when DEBUG_VIEW_CLOCKS is set): [view][16] u64,
 // summed over the rounds of the view.  A separate instantiation: the accumulators cost registers the kernel does not have.
 #define PHASE_ACC(i) do { if constexpr (PHASES) { const unsigned long long now_ = __builtin_readcyclecounter(); pacc[i] += now_ - tprev; tprev = now_; } } while (0)
 
@@ -264,14 +264,14 @@ __global__ __launch_bounds__(VIEW_THREADS, LIST ? 3 : 4) void k_view(McrParams p
   // host sizes the grid so that 64 lanes cover the list), and what the next env needs from HBM — header, tile flags,
   // view record, visible-block list, first candidates — is requested while the current one is drawn.
   // Whose business is a work slot?
-  //   role >= 2 (side streams): the envs of the contact / deferred lists;  use_vorder (step path): the order k_dynamics
-  //   recorded, heavy (zoomed-out) envs first;  role 1: not the envs the side streams draw;  only_just_reset: reset().
+  //   list roles (mcr_kernels.h: McrRole): the envs of their lists;  use_vorder (step path): the order k_dynamics
+  //   recorded, heavy (zoomed-out) envs first;  ROLE_MAIN: not the envs the side streams draw;  only_just_reset: reset().
   if (LIST) __builtin_amdgcn_s_setprio(3);                                  // a few envs beside the main launch that fills every CU: they go first
   const int vgrid = (int)gridDim.x - (LIST ? p.flags_blocks : 0);           // workgroups that draw; the rest: the list's bookkeeping
   if (LIST && (int)blockIdx.x >= vgrid) {
     // the bookkeeping of the list's cars (k_flags.h: backward / on-grass flags, the env's touch verdict for the next step), one wavefront
-    // per car.  Contact list for the contact chain's raster, deferred list otherwise (the re-spawned envs' cars take none in this step).
-    const int32_t* __restrict__ L = p.role == 2 ? p.clist : p.dlist;
+    // per car.
+    const int32_t* __restrict__ L = mcr_flags_list_of(p);
     const int ncars = L[0] * N, per_round = p.flags_blocks * (VIEW_THREADS / 64);
     // (work items: the cars' flag scans, then one touch verdict per env — on different wavefronts, side by side)
     const int nverd = (p.part_next != nullptr && N > 1) ? L[0] : 0;
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(VIEW_THREADS, LIST ? 3 : 4) void k_view(McrParams p
     int e = -1;
     bool ojr = only_just_reset != 0;
     int term_i = -1;                                                       // position in the chain's list of terminal entries
-    if (p.role == 5) {
+    if (p.role == ROLE_DEFERRED_RESPAWN) {
       // the tail of the caller's stream: the deferred envs, then the envs the main dynamics re-spawned (their first observation), then the
       // terminal entries of the caller-side chains — one launch
       const int idx = split_views ? s / N : s, nd = p.dlist[0], nr = p.rlist[0];
@@ -302,11 +302,11 @@ __global__ __launch_bounds__(VIEW_THREADS, LIST ? 3 : 4) void k_view(McrParams p
       else if (p.term_cnt != nullptr && idx - nd - nr < p.term_cnt[1]) term_i = idx - nd - nr;
       my_agent = split_views ? s % N : 0;
     }
-    else if (p.role == 6) { const int idx = split_views ? s / N : s; if (p.term_cnt != nullptr && idx < p.term_cnt[1]) term_i = idx; my_agent = split_views ? s % N : 0; }   // single-stream step: the terminal entries alone
-    else if (p.role >= 2) {
+    else if (p.role == ROLE_TERMINAL) { const int idx = split_views ? s / N : s; if (p.term_cnt != nullptr && idx < p.term_cnt[1]) term_i = idx; my_agent = split_views ? s % N : 0; }   // single-stream step: the terminal entries alone
+    else if (mcr_is_list_role(p.role)) {
       const int idx = split_views ? s / N : s, nl = mcr_list_len(p);
       e = mcr_env_of_slot(p, idx); if (e >= p.env0 + p.nenv) e = -1; my_agent = split_views ? s % N : 0;
-      if (p.role == 2 && p.term_cnt != nullptr && idx >= nl && idx - nl < p.term_cnt[2]) term_i = p.term_cap + idx - nl;      // the contact chain's entries
+      if (p.role == ROLE_CONTACT && p.term_cnt != nullptr && idx >= nl && idx - nl < p.term_cnt[2]) term_i = p.term_cap + idx - nl;      // the contact chain's entries
     }
     else if (p.use_vorder) {
       // one load instead of a chain of four (list counts -> list entry -> env record -> slot header): the entry k_dynamics left
@@ -317,12 +317,12 @@ __global__ __launch_bounds__(VIEW_THREADS, LIST ? 3 : 4) void k_view(McrParams p
     }
     else if (s < p.nenv) e = p.env0 + s;
     if (e >= 0 && !p.use_vorder) {
-      if (p.role == 1 && (p.part[e] || p.dpart[e])) e = -1;
+      if (p.role == ROLE_MAIN && (p.part[e] || p.dpart[e])) e = -1;
     }
-    if (e >= 0 && (!p.use_vorder || p.role >= 2)) {
+    if (e >= 0 && (!p.use_vorder || mcr_is_list_role(p.role))) {
       const McrEnvState es = p.env[e];
       // side-stream raster: a contact env re-spawned by this step's dynamics is drawn after its reset pass
-      if (!es.active || (ojr && !es.just_reset) || (p.role >= 2 && !ojr && es.resetting)) e = -1;
+      if (!es.active || (ojr && !es.just_reset) || (mcr_is_list_role(p.role) && !ojr && es.resetting)) e = -1;
       my_slot = es.slot;
     }
     my_env = e; my_benv = e;

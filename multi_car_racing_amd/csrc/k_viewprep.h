@@ -13,7 +13,7 @@ __device__ __forceinline__ void viewprep_car(const McrShapes& S, const float* __
   view_record(S, car_pose_load(carf, card, stride, ci, parts), t_now, h_ratio, viewp + (size_t)ci * MCR_VIEWP_FLOATS, carpoly + (size_t)ci * MCR_CARPOLY_FLOATS, parts);
 }
 
-// one lane per car of the main launch's envs (role 1 semantics: not the contact chain's, not the deferred, not the re-spawned ones)
+// one lane per car of the main launch's envs (ROLE_MAIN semantics: not the contact chain's, not the deferred, not the re-spawned ones)
 __device__ __forceinline__ void viewprep_block(const McrParams& p, const int blk) {
   const int g = blk * 64 + threadIdx.x;
   const int env = mcr_env_of_slot(p, g / p.G), agent = g % p.G;
@@ -22,7 +22,7 @@ __device__ __forceinline__ void viewprep_block(const McrParams& p, const int blk
   if (!es.active || es.just_reset) return;
   viewprep_car(*p.shapes, p.carf, p.card, p.BN, env * p.N + agent, p.viewp, p.carpoly, p.h_ratio, es.t);
 }
-// The view records and car polygons of a list chain's envs (roles 2 / 3, k_list_chain.h), right behind their dynamics: the chain is the
+// The view records and car polygons of a list chain's envs (ROLE_CONTACT / ROLE_DEFERRED, k_list_chain.h), right behind their dynamics: the chain is the
 // step's critical path and its wavefront holds a handful of cars — a car's record is ten f64 sincos on ONE lane (13 us) when the car's lane
 // computes it; here FIVE lanes share it (view_record's `parts`: camera + HUD + hull | wheel 0..3), reading the state the car lanes have just
 // written back.

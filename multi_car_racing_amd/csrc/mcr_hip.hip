@@ -52,7 +52,7 @@ struct mcr_env {
   int32_t* stage_ids;         // [B] device scratch of mcr_stage_episodes
   hipStream_t s_side, s_defer; // internal streams: the contact envs' chain, the deferred envs' chain
   hipEvent_t ev_fork, ev_join, ev_fork2, ev_join2, ev_col;
-  unsigned long long* view_stamps;   // [BN][16] phase clocks of the rasteriser (debug bit 5)
+  unsigned long long* view_stamps;   // [BN][16] phase clocks of the rasteriser (DEBUG_VIEW_CLOCKS)
   // hipGraph of one step (mcr_set_step_graph): one per contact-list parity, re-captured when any argument changes
   struct StepGraph { bool valid; McrParams P; hipStream_t st; int view_flags; hipGraph_t graph; hipGraphExec_t exec; };
   StepGraph sg[2 * MCR_OBS_STACK_MAX];   // [ring head j][parity] (mcr_set_obs_format: the raster's launches carry j)
@@ -82,7 +82,7 @@ struct mcr_env {
   McrObsRing ring{nullptr, 1, 0};   // ... and where their frames go (ring.j: set per launch)
   uint64_t obs_draws = 0;     // drawing steps enqueued (mcr_step with an observation buffer): the ring head is obs_draws mod k
   bool flags_pending = false; // the last step left the bookkeeping of its main envs (k_flags.h) to its successor (step_phase_words): flags_P launches it
-  McrParams flags_P;          // ... the launch's parameters: role 1 with that step's partition marks (its parity's part / dpart buffers), no touch verdicts
+  McrParams flags_P;          // ... the launch's parameters: ROLE_MAIN with that step's partition marks (its parity's part / dpart buffers), no touch verdicts
 };
 
 static void flush_flags(mcr_env* h, hipStream_t st);
@@ -171,7 +171,7 @@ static void select_step_ordering(mcr_env* h) {
   // contact chain itself — 585 us for its slowest wavefront, a sequential Gauss-Seidel over the contacts between the joint sweeps)
   // (round 3, phase-word path, contact pass beside / in front of the dynamics: N = 5 8.99 / 8.50 M env-steps/s, N = 6 7.87 / 7.49,
   // N = 7 7.16 / 6.80, N = 8 4.90 / 5.47 — up to seven cars per env it runs beside)
-  h->concurrent_collide = N <= 8 && !getenv("MCR_SEQUENTIAL_COLLIDE") && (B * G + 63) / 64 <= h->simd_count && kernels_overlap(h->s_defer, h->s_side);
+  h->concurrent_collide = N <= 8 && !getenv("MCR_SEQUENTIAL_COLLIDE") && mcr_dyn_blocks(B, G) <= h->simd_count && kernels_overlap(h->s_defer, h->s_side);
   h->split = true;
   (void)hipGetLastError();
 }
@@ -220,7 +220,7 @@ extern "C" int mcr_create(const mcr_config* cfg, mcr_env** out) {
   const size_t o_stage_ids = carve(sizeof(int32_t) * (size_t)B);
   const size_t o_stats = carve(sizeof(double) * 2);
   const size_t o_vorder = carve(sizeof(int32_t) * 2 * ((size_t)B + 2));
-  const size_t o_stamps = carve(sizeof(unsigned long long) * 8 * ((((size_t)B * G + 63) / 64) + 2 * (size_t)B));
+  const size_t o_stamps = carve(sizeof(unsigned long long) * 8 * ((size_t)mcr_dyn_blocks(B, G) + 2 * (size_t)B));
   const size_t o_clist = carve(sizeof(int32_t) * 2 * ((size_t)B + 1));
   const size_t o_shapes = carve(sizeof(McrShapes));
   const size_t o_viewp = carve(sizeof(float) * MCR_VIEWP_FLOATS * BN);
@@ -267,7 +267,7 @@ extern "C" int mcr_create(const mcr_config* cfg, mcr_env** out) {
   memset(h->status_host, 0, sizeof(uint32_t) * (MCR_STATUS_WORDS + MCR_HOST_COUNTS));
   (void)hipHostGetDevicePointer(&dptr, h->status_host, 0);
   P.status = (uint32_t*)dptr; P.host_counts = P.status + MCR_STATUS_WORDS;
-  P.env0 = 0; P.nenv = B; P.split = 0; P.role = 0;
+  P.env0 = 0; P.nenv = B; P.split = 0; P.role = ROLE_ALL;
   h->split = false; h->step_parity = 0;
   if (cfg->num_streams == 2) select_step_ordering(h);
   (void)hipDeviceSynchronize();
@@ -353,7 +353,7 @@ static hipEvent_t get_event(mcr_env* h) {
 
 void mcr_view_launch(int variant, int grid, hipStream_t st, const McrParams& P, unsigned long long* stamps, int only_just_reset, hipEvent_t stop, hipEvent_t start,
                      bool gray, const McrObsRing& ring);   // mcr_view.hip
-// raster launch (k_view.h).  Main launches: one workgroup per work slot.  List launches (role >= 2): MCR_LIST_GRID
+// raster launch (k_view.h).  Main launches: one workgroup per work slot.  List launches (mcr_is_list_role): MCR_LIST_GRID
 // persistent workgroups that walk the list (lane k of a wavefront holds a workgroup's k-th env, so never fewer than
 // slots / 64 workgroups).
 static int list_grid(int slots, int want) { return std::min(slots, std::max(want, (slots + 63) / 64)); }
@@ -367,8 +367,8 @@ static void launch_view(mcr_env* h, int kid, int slots, hipStream_t st, const Mc
   if (tm) { tl.id = kid; tl.a = get_event(h); tl.b = get_event(h); if (own_ts) { start = tl.a; stop = tl.b; } else (void)hipEventRecord(tl.a, st); }
   // (list launches: with more than two cars per env the contact list is long — N = 8: ~340 envs x 8 views per step — and 128
   // workgroups would draw ~20 views each, one after the other, at the end of the side stream's chain)
-  if (P.role >= 2) { McrParams Q = P; Q.split_views = 1; mcr_view_launch(2, list_grid(slots * (Q.split_views ? P.N : 1), std::max(h->list_view_grid, want_grid)) + Q.flags_blocks, st, Q, h->view_stamps, only_just_reset, stop, start, h->obs_gray, h->ring); }
-  else mcr_view_launch((P.debug & 32) ? 1 : 0, slots, st, P, h->view_stamps, only_just_reset, stop, start, h->obs_gray, h->ring);
+  if (mcr_is_list_role(P.role)) { McrParams Q = P; Q.split_views = 1; mcr_view_launch(2, list_grid(slots * (Q.split_views ? P.N : 1), std::max(h->list_view_grid, want_grid)) + Q.flags_blocks, st, Q, h->view_stamps, only_just_reset, stop, start, h->obs_gray, h->ring); }
+  else mcr_view_launch((P.debug & DEBUG_VIEW_CLOCKS) ? 1 : 0, slots, st, P, h->view_stamps, only_just_reset, stop, start, h->obs_gray, h->ring);
   if (tm) { if (!own_ts) (void)hipEventRecord(tl.b, st); h->pending.push_back(tl); }
 }
 
@@ -379,7 +379,7 @@ static void launch_view(mcr_env* h, int kid, int slots, hipStream_t st, const Mc
 static void flush_flags(mcr_env* h, hipStream_t st) {
   if (!h->flags_pending) return;
   h->flags_pending = false;
-  if (h->P.debug & (1 << 20)) return;     // debug bit 20 (tests): the pending launch is DROPPED — stale flags show that the results came through it
+  if (h->P.debug & DEBUG_DROP_PENDING_FLAGS) return;     // (tests): the pending launch is DROPPED — stale flags show that the results came through it
   hipLaunchKernelGGL(k_flags, dim3(h->flags_P.B * h->flags_P.N), dim3(64), 0, st, h->flags_P);
 }
 // the synchronous calls (state getters / setters): the device's work is complete and so is the pending bookkeeping (null stream, waited for)
@@ -392,8 +392,8 @@ static hipError_t sync_state(mcr_env* h) {
 // reset(): install -> collide(1) -> dynamics(1) -> view, in order on one stream
 static void launch_reset(mcr_env* h, McrParams P, hipStream_t st) {
   const int B = P.B, N = P.N;
-  const int dyn_blocks = (B * P.G + 63) / 64;
-  P.split = 0; P.role = 0; P.use_vorder = 0;
+  const int dyn_blocks = mcr_dyn_blocks(B, P.G);
+  P.split = 0; P.role = ROLE_ALL; P.use_vorder = 0;
   hipLaunchKernelGGL(k_install, dim3(dyn_blocks), dim3(64), 0, st, P);
   LAUNCH_LDS(3, k_collide, B, 64, col::lds_bytes(N), st, P, 1);
   LAUNCH_DYN(4, P.car_contacts && N > 1, dyn_blocks, st, P, 1);
@@ -424,7 +424,7 @@ static void step_prologue(mcr_env* h, McrParams& P, hipStream_t st) {
   // drawing — mcr_step without an observation buffer on a handle that has one — left it unconsumed: wipe it before its next use)
   if (h->vorder_dirty[h->step_parity]) { (void)hipMemsetAsync(h->P.vcount + (size_t)h->step_parity * (B + 2) + 2, 0xff, sizeof(int32_t) * (size_t)B, st); h->vorder_dirty[h->step_parity] = false; }
   if (!P.obs && h->cfg.obs_enabled) h->vorder_dirty[h->step_parity] = true;
-  P.role = 0; P.split = h->split ? 1 : 0; P.defer_after = 0; P.respawn_list = 0;
+  P.role = ROLE_ALL; P.split = h->split ? 1 : 0; P.defer_after = 0; P.respawn_list = 0;
   // the device-side lists of a step are double-buffered by step parity: no memset, and nobody zeroes a list somebody reads
   const size_t par = (size_t)h->step_parity, oth = par ^ 1;
   P.clist = h->P.clist + par * (B + 1); P.clist_next = h->P.clist + oth * (B + 1);
@@ -447,9 +447,19 @@ static void step_prologue(mcr_env* h, McrParams& P, hipStream_t st) {
   h->step_parity ^= 1;
 }
 
+// The argument block of ONE launch: the path's block `p` with the launch's role and the fields its line names — nothing else differs
+static McrParams with(McrParams p, McrRole role) { p.role = role; return p; }
+template <class F> static McrParams with(McrParams p, McrRole role, F&& edit) { p.role = role; edit(p); return p; }
+
 // single stream: collide -> dynamics -> reset pass of the re-spawned envs (:408) -> raster -> bookkeeping, all envs
-static void step_single_stream(mcr_env* h, McrParams P, hipStream_t st, int view_flags) {
-  const int B = P.B, N = P.N, dyn_blocks = (B * P.G + 63) / 64;
+//   launch (all on st)                      grid         block: P (the prologue's: ROLE_ALL, split 0) with
+//   k_collide pass 0, k_dynamics            B, dyn       -
+//   auto_reset: k_term_prep, k_collide pass 1, k_dynamics mode 1     B, B, dyn    -
+//   raster 2                                B            use_vorder 1
+//   terminal entries: raster 7 (list), k_term_finish     B (slots), 1   ROLE_TERMINAL; -
+//   k_flags                                 B * N        -
+static void step_single_stream(mcr_env* h, const McrParams& P, hipStream_t st, int view_flags) {
+  const int B = P.B, N = P.N, dyn_blocks = mcr_dyn_blocks(B, P.G);
   const bool draw = P.obs != nullptr;
   LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), st, P, 0);
   LAUNCH_DYN(1, P.car_contacts && N > 1, dyn_blocks, st, P, 0);
@@ -458,11 +468,32 @@ static void step_single_stream(mcr_env* h, McrParams P, hipStream_t st, int view
     LAUNCH_LDS(3, k_collide, B, 64, col::lds_bytes(N), st, P, 1);
     LAUNCH_DYN(4, P.car_contacts && N > 1, dyn_blocks, st, P, 1);
   }
-  P.use_vorder = 1;
-  if (draw) launch_view(h, 2, B, st, P, 0);
-  P.use_vorder = 0;
-  if (P.term_cnt) { McrParams Pt = P; Pt.role = 6; launch_view(h, 7, B, st, Pt, 0); hipLaunchKernelGGL(k_term_finish, dim3(1), dim3(256), 0, st, P); }
+  if (draw) launch_view(h, 2, B, st, with(P, ROLE_ALL, [](McrParams& q) { q.use_vorder = 1; }), 0);
+  if (P.term_cnt) { launch_view(h, 7, B, st, with(P, ROLE_TERMINAL), 0); hipLaunchKernelGGL(k_term_finish, dim3(1), dim3(256), 0, st, P); }
   if (view_flags) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, st, P);
+}
+
+// Grid sizes of the three-chain step, whichever way its streams are ordered (launch_step computes them once)
+struct StepGrids {
+  int dyn_blocks;      // the main dynamics
+  int lg_con;          // the contact chain (a list launch): one env per wavefront
+  int prev_contacts;   // the length of the LAST step's contact list (mapped host word: no synchronisation)
+  int lg_flags;        // the bookkeeping of a chain's cars as a list launch of its own
+  int ga, gb;          // the caller's chain: workgroups that resume the deferred envs, workgroups for the reset pass of the re-spawned ones
+  int vg_con;          // the contact raster's grid wish: sized by the LAST step's list — the lists change slowly — so that a long list, a policy that
+                       // drives: ~90 envs of 4096, takes one round of workgroups instead of two or three behind the chain, the step's critical path
+};
+static StepGrids step_grids(const mcr_env* h, const McrParams& P) {
+  const int B = P.B, N = P.N;
+  StepGrids g;
+  g.dyn_blocks = mcr_dyn_blocks(B, P.G);
+  g.lg_con = std::min(B, 2 * h->chain_grid);
+  g.prev_contacts = std::min(B, (int)((volatile uint32_t*)h->status_host)[MCR_STATUS_WORDS + HC_CONTACT_ENVS]);
+  g.lg_flags = std::min(B * N, (N <= 2 ? 4 : 32) * MCR_LIST_GRID);
+  g.ga = std::min({(B + MCR_SIDE_ENVS_PER_WAVE - 1) / MCR_SIDE_ENVS_PER_WAVE, h->chain_grid, MCR_LIST_GRID / 2});
+  g.gb = P.auto_reset ? std::min(B, MCR_LIST_GRID) : 0;
+  g.vg_con = std::min(2048, g.prev_contacts * N + g.prev_contacts * N / 4 + 8);
+  return g;
 }
 
 // The three chains ordered by phase words (mcr_kernels.h: soft_sync) — no marker / barrier packets on any stream ([...]: with the contact pass
@@ -479,79 +510,90 @@ static void step_single_stream(mcr_env* h, McrParams P, hipStream_t st, int view
 // (kernel trace, round 3: the resume chain starts 3 us after the dynamics instead of 11-21, the next step's dynamics 0-1 us after
 // the step's last kernel instead of 20-32; the chains' bookkeeping: list launches behind the chains; N > 3: the main envs'
 // bookkeeping on the caller's stream)
-static void step_phase_words(mcr_env* h, McrParams P, hipStream_t st, int view_flags) {
-  const int B = P.B, N = P.N, dyn_blocks = (B * P.G + 63) / 64;
-  const int lg_con = std::min(B, 2 * h->chain_grid);             // the contact chain (a list launch): one env per wavefront
-  const int prev_contacts = std::min(B, (int)((volatile uint32_t*)h->status_host)[MCR_STATUS_WORDS + HC_CONTACT_ENVS]);   // (mapped host word: no synchronisation)
-  const bool draw = P.obs != nullptr, cc = P.cc_mode != 0;
-  P.soft_sync = 1;
-  const int lg_flags = std::min(B * N, (N <= 2 ? 4 : 32) * MCR_LIST_GRID);
-  if (!cc) LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), st, P, 0);
-  // The step's critical kernel goes out FIRST (round 6): everything the other two streams run in this step waits for a word the dynamics posts
-  // (BEGIN from its first thread), so the order of enqueueing across the streams is free — and behind a host synchronisation (an RL loop
-  // reads its observations every step) the seven launches that used to precede it cost the step their enqueue time, ~45 us.
+// The launches in enqueue order.  P: launch_step's block with soft_sync 1, flags_deferred (the last step's scans run in this one), split 0,
+// viewprep_in_flags vif.  Pbegin (what opens the step): P with ROLE_ALL, split 1, viewprep_in_flags 0.  Pside (the side stream): P with
+// ROLE_CONTACT, viewprep_in_flags 0.
+//   launch                               stream    grid                     block
+//   (k_collide pass 0)                   st        B                        Pbegin
+//   (the pending k_flags, flush_flags)   st        B * N                    h->flags_P
+//   k_dynamics<false>                    st        dyn_blocks               P, ROLE_MAIN
+//   k_await(BEGIN)                       s_side    1                        Pbegin
+//   [k_await(BEGIN)]                     s_defer   1                        Pbegin
+//   [{the pending k_flags}]              s_defer   B * N                    h->flags_P
+//   [k_collide pass 0, k_post(COL)]      s_defer   B, 1                     Pbegin
+//   k_list_chain<true>                   s_side    lg_con                   Pside, list_envs_per_block 1 (both lists)
+//   k_flags_list (no fiv)                s_side    lg_flags                 Pside
+//   raster 6 (list)                      s_side    B or 2B slots, vg_con    Pside, flags_blocks fiv_c
+//   k_post(SIDE)                         s_side    1                        Pside
+//   k_list_chain<false>                  st        ga + gb                  P, ROLE_DEFERRED; P, ROLE_RESPAWN, list_envs_per_block 1
+//   k_flags_list (no fiv)                st        lg_flags                 P, ROLE_DEFERRED
+//   k_flags (flags_on_caller)            st        B * N                    P, ROLE_MAIN
+//   raster 7 (list)                      st        B or 2B slots            P, ROLE_DEFERRED_RESPAWN (no auto_reset: ROLE_DEFERRED), await_tail 1, flags_blocks fiv
+//   k_await(DYN)                         s_defer   1                        P, ROLE_MAIN
+//   k_viewprep_verdict (defer_flags) | k_flags_viewprep (vif) | k_flags     s_defer   dyn_blocks + B | dyn_blocks + B * N | B * N     P, ROLE_MAIN
+//   raster 2                             s_defer   B                        P, ROLE_MAIN, use_vorder 1
+//   k_post(MAIN)                         s_defer   1                        P, ROLE_MAIN
+//   not drawn: k_await(SIDE, MAIN)       st        1                        P, ROLE_MAIN
+//   h->flags_P (defer_flags: launched by the next step or flush_flags): P, ROLE_MAIN, part_next null, flags_deferred 0
+static void step_phase_words(mcr_env* h, const McrParams& Pin, const StepGrids& g, hipStream_t st, int view_flags) {
+  const int B = Pin.B, N = Pin.N, dyn_blocks = g.dyn_blocks;
+  const bool draw = Pin.obs != nullptr, cc = Pin.cc_mode != 0;
   const int vif = (view_flags && draw && h->viewprep_in_flags) ? 1 : 0;
   // (not with a long contact list — a policy that drives: the contact chain, which fills the machine from the step's begin, is the step's critical
   // path then, the raster's chain has slack, and 8192 wavefronts beside the chain's first sweeps cost `--actions drive` 1.3 %, measured.  The
   // bound is an ABSOLUTE count found at B = 4096, N = 2 (random actions: ~15 contact envs, drive: ~1000) and not verified at other batch sizes;
   // it comes from a mapped host word read without synchronisation, so WHICH steps defer can differ between runs — results do not depend on it)
-  const bool defer_flags = vif && cc && prev_contacts <= 64 && !(P.debug & (1 << 19));     // (debug bit 19: the scans stay in their step — A/B runs)
-  if (h->flags_pending && !cc) flush_flags(h, st);                   // (mcr_step flushes for every step that cannot take the scans in: not reached)
-  const bool take_flags = h->flags_pending;
-  P.flags_deferred = take_flags ? 1 : 0;
-  { McrParams Pd = P; Pd.split = 0; Pd.role = 1; Pd.viewprep_in_flags = vif; LAUNCH(1, k_dynamics<false>, dyn_blocks, 64, st, Pd, 0); }          // (the main envs: no touching car<->car pair)
-  hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_side, P, (int)W_BEGIN, -1);
+  const bool defer_flags = vif && cc && g.prev_contacts <= 64 && !(Pin.debug & DEBUG_FLAGS_IN_STEP);     // (DEBUG_FLAGS_IN_STEP: the scans stay in their step — A/B runs)
+  const bool take_flags = cc && h->flags_pending;                      // (without cc: flushed below — mcr_step flushes for every step that cannot take the scans in: not reached)
+  const McrParams P = with(Pin, ROLE_MAIN, [&](McrParams& q) { q.soft_sync = 1; q.flags_deferred = take_flags ? 1 : 0; q.split = 0; q.viewprep_in_flags = vif; });
+  const McrParams Pbegin = with(P, ROLE_ALL, [](McrParams& q) { q.split = 1; q.viewprep_in_flags = 0; });     // (split: k_collide pass 0 fills part / clist)
+  const McrParams Pside = with(P, ROLE_CONTACT, [](McrParams& q) { q.viewprep_in_flags = 0; });
+  if (!cc) LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), st, Pbegin, 0);
+  // The step's critical kernel goes out FIRST (round 6): everything the other two streams run in this step waits for a word the dynamics posts
+  // (BEGIN from its first thread), so the order of enqueueing across the streams is free — and behind a host synchronisation (an RL loop
+  // reads its observations every step) the seven launches that used to precede it cost the step their enqueue time, ~45 us.
+  if (h->flags_pending && !cc) flush_flags(h, st);
+  LAUNCH(1, k_dynamics<false>, dyn_blocks, 64, st, with(P, ROLE_MAIN), 0);          // (the main envs: no touching car<->car pair)
+  hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_side, Pbegin, (int)W_BEGIN, -1);
   if (cc) {
     // the contact pass of the main envs on the THIRD stream (idle until the dynamics is through), the contact chain — each workgroup with its
     // env's own contact pass in front (fuse_collide) — on the side stream from the step's begin: the chain, the step's critical path when cars
     // pile up, does not wait for the 4096-env launch
-    hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_BEGIN, -1);
+    hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_defer, Pbegin, (int)W_BEGIN, -1);
     if (take_flags) flush_flags(h, h->s_defer);                      // the last step's main envs' bookkeeping: beside this step's main dynamics
-    LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), h->s_defer, P, 0);
-    hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_COL);
+    LAUNCH_LDS(0, k_collide, B, 64, col::lds_bytes(N), h->s_defer, Pbegin, 0);
+    hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_defer, Pbegin, (int)W_COL);
   }
-  P.split = 0;
-  P.role = 2;
-  { McrParams Pc = P; Pc.list_envs_per_block = 1; LAUNCH_LDS(5, k_list_chain<true>, lg_con, 64, col::lds_bytes(N), h->s_side, Pc, Pc, 0, lg_con); }   // ONE contact env per wavefront: the uniform contact sweeps (k_dynamics.h)
+  { const McrParams Pc = with(Pside, ROLE_CONTACT, [](McrParams& q) { q.list_envs_per_block = 1; }); LAUNCH_LDS(5, k_list_chain<true>, g.lg_con, 64, col::lds_bytes(N), h->s_side, Pc, Pc, 0, g.lg_con); }   // ONE contact env per wavefront: the uniform contact sweeps (k_dynamics.h)
   // (the chains' bookkeeping: workgroups of its own inside the chain's raster launch when there is one, a list launch otherwise)
   // (beyond four cars per env the lists hold thousands of cars — ~315 contact envs x 8 at N = 8 — and a few 256-thread workgroups
   // would take them in many rounds at the end of the contact chain, the critical path there; measured N = 2 15.37 -> 15.65 M
   // env-steps/s, N = 4 11.00 -> 11.07, N = 8 5.47 -> 5.44)
   const int fiv = (view_flags && draw && N <= 8) ? (N <= 2 ? 8 : 64) : 0;
-  // (the contact list's raster and bookkeeping workgroups: sized by the LAST step's list — the lists change slowly — so that a long list,
-  // a policy that drives: ~90 envs of 4096, takes one round of workgroups instead of two or three behind the chain, the step's critical path)
-  const int fiv_c = fiv ? std::min(512, std::max(fiv, (prev_contacts * (N + 1) + 3) / 4 + 2)) : 0;
-  const int vg_c = std::min(2048, prev_contacts * N + prev_contacts * N / 4 + 8);
-  if (view_flags && !fiv) hipLaunchKernelGGL(k_flags_list, dim3(lg_flags), dim3(64), 0, h->s_side, P);
-  if (draw) { McrParams Pv = P; Pv.flags_blocks = fiv_c; launch_view(h, 6, P.term_cnt ? 2 * B : B, h->s_side, Pv, 0, nullptr, vg_c); }
-  hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_side, P, (int)W_SIDE);
-  P.viewprep_in_flags = vif;
-  const bool flags_on_caller = view_flags && draw && !P.viewprep_in_flags && N <= 7;   // (N = 8: the raster would share the machine with the bookkeeping: 6.70 -> 6.49 M env-steps/s, round 5)
-  P.role = 3;
-  {
-    const int ga = std::min({(B + MCR_SIDE_ENVS_PER_WAVE - 1) / MCR_SIDE_ENVS_PER_WAVE, h->chain_grid, MCR_LIST_GRID / 2}), gb = P.auto_reset ? std::min(B, MCR_LIST_GRID) : 0;
-    McrParams Pr = P; Pr.role = 4; Pr.list_envs_per_block = 1;
-    LAUNCH_LDS(7, k_list_chain<false>, ga + gb, 64, col::lds_bytes(N), st, P, Pr, 0, ga);
-    if (view_flags && !fiv) hipLaunchKernelGGL(k_flags_list, dim3(lg_flags), dim3(64), 0, st, P);
-    // Beyond three cars per env the third stream's chain (bookkeeping of B*N cars, then B*N views) is the longer one and the caller's
-    // has slack: the main envs' bookkeeping — which the raster does not depend on — moves here, between the resume chain and its raster
-    if (flags_on_caller) { McrParams Pm = P; Pm.role = 1; hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, st, Pm); }
-    if (draw) { McrParams Pv = P; Pv.role = P.auto_reset ? 5 : 3; Pv.await_tail = 1; Pv.flags_blocks = fiv; launch_view(h, 7, P.term_cnt ? 2 * B : B, st, Pv, 0); }     // ... and the step's join (+ the terminal entries' frames and count)
-  }
-  P.role = 1;
-  hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_DYN, -1);
+  // (the contact list's bookkeeping workgroups: sized by the LAST step's list, like the raster's — StepGrids::vg_con)
+  const int fiv_c = fiv ? std::min(512, std::max(fiv, (g.prev_contacts * (N + 1) + 3) / 4 + 2)) : 0;
+  if (view_flags && !fiv) hipLaunchKernelGGL(k_flags_list, dim3(g.lg_flags), dim3(64), 0, h->s_side, Pside);
+  if (draw) launch_view(h, 6, P.term_cnt ? 2 * B : B, h->s_side, with(Pside, ROLE_CONTACT, [&](McrParams& q) { q.flags_blocks = fiv_c; }), 0, nullptr, g.vg_con);
+  hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_side, Pside, (int)W_SIDE);
+  const bool flags_on_caller = view_flags && draw && !vif && N <= 7;   // (N = 8: the raster would share the machine with the bookkeeping: 6.70 -> 6.49 M env-steps/s, round 5)
+  LAUNCH_LDS(7, k_list_chain<false>, g.ga + g.gb, 64, col::lds_bytes(N), st, with(P, ROLE_DEFERRED), with(P, ROLE_RESPAWN, [](McrParams& q) { q.list_envs_per_block = 1; }), 0, g.ga);
+  if (view_flags && !fiv) hipLaunchKernelGGL(k_flags_list, dim3(g.lg_flags), dim3(64), 0, st, with(P, ROLE_DEFERRED));
+  // Beyond three cars per env the third stream's chain (bookkeeping of B*N cars, then B*N views) is the longer one and the caller's
+  // has slack: the main envs' bookkeeping — which the raster does not depend on — moves here, between the resume chain and its raster
+  if (flags_on_caller) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, st, with(P, ROLE_MAIN));
+  // ... and the step's join (+ the terminal entries' frames and count)
+  if (draw) launch_view(h, 7, P.term_cnt ? 2 * B : B, st, with(P, P.auto_reset ? ROLE_DEFERRED_RESPAWN : ROLE_DEFERRED, [&](McrParams& q) { q.await_tail = 1; q.flags_blocks = fiv; }), 0);
+  hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_defer, with(P, ROLE_MAIN), (int)W_DYN, -1);
   if (defer_flags) {
     // view records + the marked envs' touch verdicts; the flag scans: the next step's begin (or flush_flags)
-    hipLaunchKernelGGL(k_viewprep_verdict, dim3(dyn_blocks + B), dim3(64), 0, h->s_defer, P, dyn_blocks);
-    h->flags_P = P; h->flags_P.part_next = nullptr; h->flags_P.flags_deferred = 0; h->flags_pending = true;
+    hipLaunchKernelGGL(k_viewprep_verdict, dim3(dyn_blocks + B), dim3(64), 0, h->s_defer, with(P, ROLE_MAIN), dyn_blocks);
+    h->flags_P = with(P, ROLE_MAIN, [](McrParams& q) { q.part_next = nullptr; q.flags_deferred = 0; }); h->flags_pending = true;
   }
-  else if (P.viewprep_in_flags) hipLaunchKernelGGL(k_flags_viewprep, dim3(dyn_blocks + B * N), dim3(64), 0, h->s_defer, P, dyn_blocks);      // view records + bookkeeping: one launch
-  else if (view_flags && !flags_on_caller) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, h->s_defer, P);
-  P.use_vorder = 1;
-  if (draw) launch_view(h, 2, B, h->s_defer, P, 0);
-  P.use_vorder = 0;
-  hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_defer, P, (int)W_MAIN);
-  if (!draw) hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, st, P, (int)W_SIDE, (int)W_MAIN);
+  else if (vif) hipLaunchKernelGGL(k_flags_viewprep, dim3(dyn_blocks + B * N), dim3(64), 0, h->s_defer, with(P, ROLE_MAIN), dyn_blocks);      // view records + bookkeeping: one launch
+  else if (view_flags && !flags_on_caller) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, h->s_defer, with(P, ROLE_MAIN));
+  if (draw) launch_view(h, 2, B, h->s_defer, with(P, ROLE_MAIN, [](McrParams& q) { q.use_vorder = 1; }), 0);
+  hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_defer, with(P, ROLE_MAIN), (int)W_MAIN);
+  if (!draw) hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, st, with(P, ROLE_MAIN), (int)W_SIDE, (int)W_MAIN);
 }
 
 // The three chains ordered by events:
@@ -562,35 +604,45 @@ static void step_phase_words(mcr_env* h, McrParams P, hipStream_t st, int view_f
 // the dispatch packet's own completion signal).  A hipEventRecord is a marker packet BEHIND the kernel: +3 us before the next
 // kernel of the same stream, 11 instead of 7.5 us for a dependent kernel on another stream (tools/ubench/event_gap.hip), and the
 // step has four of them on its critical path.  Not inside a graph capture (plain records there).
-static void step_events(mcr_env* h, McrParams P, hipStream_t st, int view_flags) {
-  const int B = P.B, N = P.N, dyn_blocks = (B * P.G + 63) / 64;
-  const int lg_con = std::min(B, 2 * h->chain_grid);             // the contact chain (a list launch): one env per wavefront
-  const int prev_contacts = std::min(B, (int)((volatile uint32_t*)h->status_host)[MCR_STATUS_WORDS + HC_CONTACT_ENVS]);   // (mapped host word: no synchronisation)
-  const bool draw = P.obs != nullptr, cc = P.cc_mode != 0;
+// The launches in enqueue order.  P: launch_step's block with split 0 and viewprep_in_flags vif.  Pbegin, Pside: as in step_phase_words.
+//   launch                               stream              grid                     block
+//   k_collide pass 0                     st (cc: s_side)     B                        Pbegin
+//   k_list_chain<true>                   s_side              lg_con                   Pside, list_envs_per_block 1 (both lists)
+//   k_flags_list (flags_list)            s_side              lg_flags                 Pside
+//   raster 6 (list)                      s_side              B or 2B slots, vg_con    Pside
+//   k_dynamics<false>                    st                  dyn_blocks               P, ROLE_MAIN
+//   k_list_chain<false>                  st                  ga + gb                  P, ROLE_DEFERRED; P, ROLE_RESPAWN, list_envs_per_block 1
+//   k_flags_list (flags_list)            st                  lg_flags                 P, ROLE_DEFERRED
+//   raster 7 (list)                      st                  B or 2B slots            P, ROLE_DEFERRED_RESPAWN (no auto_reset: ROLE_DEFERRED)
+//   k_viewprep (vif), k_flags            s_defer             dyn_blocks, B * N        P, ROLE_MAIN
+//   raster 2                             s_defer             B                        P, ROLE_MAIN, use_vorder 1
+//   terminal entries: k_term_finish      st                  1                        P, ROLE_MAIN
+static void step_events(mcr_env* h, const McrParams& Pin, const StepGrids& g, hipStream_t st, int view_flags) {
+  const int B = Pin.B, N = Pin.N, dyn_blocks = g.dyn_blocks;
+  const bool draw = Pin.obs != nullptr, cc = Pin.cc_mode != 0;
   const bool sev = h->use_graph <= 0 && !capturing(st);
+  // the main envs' view records and car polygons: by k_viewprep on the third stream, in front of the bookkeeping kernel, in a drawn step
+  // with actions; otherwise by the dynamics' own epilogue
+  const int vif = (view_flags && draw && h->viewprep_in_flags) ? 1 : 0;
+  const McrParams P = with(Pin, ROLE_MAIN, [&](McrParams& q) { q.split = 0; q.viewprep_in_flags = vif; });
+  const McrParams Pbegin = with(P, ROLE_ALL, [](McrParams& q) { q.split = 1; q.viewprep_in_flags = 0; });     // (split: k_collide pass 0 fills part / clist)
+  const McrParams Pside = with(P, ROLE_CONTACT, [](McrParams& q) { q.viewprep_in_flags = 0; });
 #define STOP(ev) (sev ? (ev) : (hipEvent_t) nullptr)
 #define RECORD_UNLESS_STOP(ev, stream) do { if (!sev) (void)hipEventRecord(ev, stream); } while (0)
-  if (!cc) LAUNCH_LDS_STOP(0, k_collide, B, 64, col::lds_bytes(N), st, STOP(h->ev_col), P, 0);
+  if (!cc) LAUNCH_LDS_STOP(0, k_collide, B, 64, col::lds_bytes(N), st, STOP(h->ev_col), Pbegin, 0);
   (void)hipEventRecord(h->ev_fork, st);
   (void)hipStreamWaitEvent(h->s_side, h->ev_fork, 0);
-  if (cc) LAUNCH_LDS_STOP(0, k_collide, B, 64, col::lds_bytes(N), h->s_side, STOP(h->ev_col), P, 0);
+  if (cc) LAUNCH_LDS_STOP(0, k_collide, B, 64, col::lds_bytes(N), h->s_side, STOP(h->ev_col), Pbegin, 0);
   RECORD_UNLESS_STOP(h->ev_col, cc ? h->s_side : st);
-  P.split = 0;
   // bookkeeping of a chain's cars: fused into the chain for N <= 2 (2 envs x N cars take their turns on one wavefront),
   // a list launch of its own beyond that
   const int fuse_flags = (view_flags && N <= 2) ? 1 : 0;
-  const int lg_flags = std::min(B * N, (N <= 2 ? 4 : 32) * MCR_LIST_GRID);
   const bool flags_list = view_flags && !fuse_flags;
-  P.role = 2;
   // (the side stream's last kernel completes ev_join; which one that is depends on the step's shape)
-  { McrParams Pc = P; Pc.list_envs_per_block = 1; LAUNCH_LDS_STOP(5, k_list_chain<true>, lg_con, 64, col::lds_bytes(N), h->s_side, STOP((!draw && !flags_list) ? h->ev_join : nullptr), Pc, Pc, fuse_flags, lg_con); }
-  if (flags_list) hipExtLaunchKernelGGL(k_flags_list, dim3(lg_flags), dim3(64), 0, h->s_side, nullptr, STOP(!draw ? h->ev_join : nullptr), 0, P);
-  if (draw) launch_view(h, 6, P.term_cnt ? 2 * B : B, h->s_side, P, 0, STOP(h->ev_join), std::min(2048, prev_contacts * N + prev_contacts * N / 4 + 8));
-  P.role = 1;
-  // the main envs' view records and car polygons: by k_viewprep on the side stream, beside the bookkeeping kernel, in a drawn step
-  // with actions; otherwise by the dynamics' own epilogue
-  P.viewprep_in_flags = (view_flags && draw && h->viewprep_in_flags) ? 1 : 0;
-  LAUNCH_LDS_STOP(1, k_dynamics<false>, dyn_blocks, 64, 0, st, STOP(h->ev_fork2), P, 0);
+  { const McrParams Pc = with(Pside, ROLE_CONTACT, [](McrParams& q) { q.list_envs_per_block = 1; }); LAUNCH_LDS_STOP(5, k_list_chain<true>, g.lg_con, 64, col::lds_bytes(N), h->s_side, STOP((!draw && !flags_list) ? h->ev_join : nullptr), Pc, Pc, fuse_flags, g.lg_con); }
+  if (flags_list) hipExtLaunchKernelGGL(k_flags_list, dim3(g.lg_flags), dim3(64), 0, h->s_side, nullptr, STOP(!draw ? h->ev_join : nullptr), 0, Pside);
+  if (draw) launch_view(h, 6, P.term_cnt ? 2 * B : B, h->s_side, Pside, 0, STOP(h->ev_join), g.vg_con);
+  LAUNCH_LDS_STOP(1, k_dynamics<false>, dyn_blocks, 64, 0, st, STOP(h->ev_fork2), with(P, ROLE_MAIN), 0);
   RECORD_UNLESS_STOP(h->ev_fork2, st);
   // The chain that follows the dynamics IN-STREAM starts ~2 us after it, one that has to hop to another stream ~8 us (kernel trace,
   // round 3).  The longer chain is the resume chain (85-150 us beside the raster + its own raster, 25-70 us) — not bookkeeping + main
@@ -599,36 +651,28 @@ static void step_events(mcr_env* h, McrParams P, hipStream_t st, int view_flags)
   (void)hipStreamWaitEvent(h->s_defer, h->ev_fork2, 0);
   (void)hipStreamWaitEvent(st, h->ev_col, 0);              // the resume chain reads the contact pass's results of its envs (a deferred env never got to the main dynamics' in-kernel wait)
   if (!draw) (void)hipStreamWaitEvent(h->s_side, h->ev_fork2, 0);
-  P.role = 3;
-  {
-    // the resume chain and — same launch, workgroups of their own — the reset pass (:408, ~50 us of serial solver work) of the
-    // envs the main dynamics re-spawned; then, in one list launch, the deferred envs' frames and the re-spawned envs' first observations
-    // (the caller's stream needs no event for its own chain)
-    const int ga = std::min({(B + MCR_SIDE_ENVS_PER_WAVE - 1) / MCR_SIDE_ENVS_PER_WAVE, h->chain_grid, MCR_LIST_GRID / 2}), gb = P.auto_reset ? std::min(B, MCR_LIST_GRID) : 0;
-    McrParams Pr = P; Pr.role = 4; Pr.list_envs_per_block = 1;     // one re-spawned env per workgroup: they run side by side
-    LAUNCH_LDS(7, k_list_chain<false>, ga + gb, 64, col::lds_bytes(N), st, P, Pr, fuse_flags, ga);
-    if (flags_list) hipLaunchKernelGGL(k_flags_list, dim3(lg_flags), dim3(64), 0, st, P);
-    if (draw) { McrParams Pv = P; Pv.role = P.auto_reset ? 5 : 3; launch_view(h, 7, P.term_cnt ? 2 * B : B, st, Pv, 0); }
-  }
-  P.role = 1;
+  // the resume chain and — same launch, workgroups of their own — the reset pass (:408, ~50 us of serial solver work) of the
+  // envs the main dynamics re-spawned (one per workgroup: they run side by side); then, in one list launch, the deferred envs' frames and
+  // the re-spawned envs' first observations (the caller's stream needs no event for its own chain)
+  LAUNCH_LDS(7, k_list_chain<false>, g.ga + g.gb, 64, col::lds_bytes(N), st, with(P, ROLE_DEFERRED), with(P, ROLE_RESPAWN, [](McrParams& q) { q.list_envs_per_block = 1; }), fuse_flags, g.ga);
+  if (flags_list) hipLaunchKernelGGL(k_flags_list, dim3(g.lg_flags), dim3(64), 0, st, with(P, ROLE_DEFERRED));
+  if (draw) launch_view(h, 7, P.term_cnt ? 2 * B : B, st, with(P, P.auto_reset ? ROLE_DEFERRED_RESPAWN : ROLE_DEFERRED), 0);
   RECORD_UNLESS_STOP(h->ev_join, h->s_side);
   // The bookkeeping of the main envs (:446-495; k_flags.h, one wavefront per car) needs the poses only.  It runs right
   // before the raster, and those ~16 us are what the list chains — forked off at the same moment — need to get their
   // wavefronts placed: a chain that starts beside a raster that already fills every CU runs 2-3x slower (measured).
   // (k_viewprep in front of it, in-stream: the side stream may be held by a long contact chain, and a further stream slows every queue)
   const hipEvent_t main_done = h->ev_join2;
-  if (P.viewprep_in_flags) hipLaunchKernelGGL(k_viewprep, dim3(dyn_blocks), dim3(64), 0, h->s_defer, P);
-  if (view_flags) hipExtLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, h->s_defer, nullptr, STOP(!draw ? main_done : nullptr), 0, P);
+  if (vif) hipLaunchKernelGGL(k_viewprep, dim3(dyn_blocks), dim3(64), 0, h->s_defer, with(P, ROLE_MAIN));
+  if (view_flags) hipExtLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, h->s_defer, nullptr, STOP(!draw ? main_done : nullptr), 0, with(P, ROLE_MAIN));
   (void)hipStreamWaitEvent(h->s_defer, h->ev_col, 0);              // the raster reads the tiles' recolour flags (long done)
-  P.use_vorder = 1;
-  if (draw) launch_view(h, 2, B, h->s_defer, P, 0, STOP(main_done));
-  P.use_vorder = 0;
+  if (draw) launch_view(h, 2, B, h->s_defer, with(P, ROLE_MAIN, [](McrParams& q) { q.use_vorder = 1; }), 0, STOP(main_done));
   // the join: the caller's stream waits for the other two (waiting for them one behind the other — one wait on the caller's
   // stream — costs a second hop: 23 vs 18.5 us after the later of the two, tools/ubench/event_gap.hip)
   if (!sev || (!draw && !view_flags)) (void)hipEventRecord(h->ev_join2, h->s_defer);
   (void)hipStreamWaitEvent(st, h->ev_join, 0);
   (void)hipStreamWaitEvent(st, h->ev_join2, 0);
-  if (P.term_cnt) hipLaunchKernelGGL(k_term_finish, dim3(1), dim3(256), 0, st, P);     // (the phase-word path: the join's workgroup does it)
+  if (P.term_cnt) hipLaunchKernelGGL(k_term_finish, dim3(1), dim3(256), 0, st, with(P, ROLE_MAIN));     // (the phase-word path: the join's workgroup does it)
 #undef STOP
 #undef RECORD_UNLESS_STOP
 }
@@ -658,8 +702,9 @@ static void launch_step(mcr_env* h, McrParams P, hipStream_t st, int view_flags)
     hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, st, h->dev_step_ctr);
     P.epoch = 0; P.epoch_ptr = h->dev_step_ctr;
   }
-  if (phase_words(h, st)) step_phase_words(h, P, st, view_flags);
-  else step_events(h, P, st, view_flags);
+  const StepGrids g = step_grids(h, P);
+  if (phase_words(h, st)) step_phase_words(h, P, g, st, view_flags);
+  else step_events(h, P, g, st, view_flags);
 }
 
 // The kernels report conditions that make results wrong in mapped host memory (mcr_kernels.h: ST_*); read here without
@@ -732,7 +777,7 @@ extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, doub
   // which an unfused step's contact pass filled two steps ago and nobody emptied (the next step's chain re-stepped stale envs)
   if (cc_active(h) && fz && !h->last_fused) (void)hipMemsetAsync(h->P.clist + (size_t)(h->step_parity ^ 1) * (P.B + 1), 0, sizeof(int32_t), st);
   if (cc_active(h) && (!h->verdict_fresh || (fz && !h->last_fused))) {   // after reset() / reset_envs() / a state restore / a step without actions: which envs hold a touching car<->car pair?
-    McrParams Pt = P; Pt.role = 0; Pt.part = h->P.part + (size_t)h->step_parity * P.B;
+    McrParams Pt = P; Pt.role = ROLE_ALL; Pt.part = h->P.part + (size_t)h->step_parity * P.B;
     Pt.fuse_collide = fused_collide(h, st) ? 1 : 0; Pt.clist = h->P.clist + (size_t)h->step_parity * (P.B + 1);
     if (Pt.fuse_collide) (void)hipMemsetAsync(Pt.clist, 0, sizeof(int32_t), st);
     hipLaunchKernelGGL(k_touch, dim3(P.B), dim3(64), 0, st, Pt);

@@ -8,6 +8,53 @@
 // it clears them; the list raster launch of the env's chain draws the entry's N frames into the caller's buffer.
 struct McrTermEnv { double t; int32_t slot, env, consumed, pad; };
 
+// Which envs a launch serves (McrParams::role).  The numeric values are part of the diagnostics' formats (DYN_STAMP's rows, MCR_TRACE's tags,
+// counters[6]; tools/ decode them) and stay as they are.  Who accepts which role, and the list it walks:
+//   ROLE_ALL               every env of [env0, env0 + nenv): every kernel; the single-stream step, reset(), k_install, k_touch, k_collide pass 0
+//   ROLE_MAIN              those envs less the contact chain's (part) and — for everybody but the main dynamics, which makes that mark — the
+//                          deferred ones (dpart): k_dynamics, k_flags / k_flags_viewprep / k_viewprep / k_viewprep_verdict, k_view (through
+//                          vorder), k_await / k_post of the three-chain step
+//   ROLE_CONTACT           clist, the envs with a touching car<->car pair: k_list_chain<true> (collide_block, dynamics_block, flags_block),
+//                          k_flags_list, k_view<LIST> (+ the contact chain's terminal entries)
+//   ROLE_DEFERRED          dlist, the envs the main dynamics deferred: k_list_chain<false> (first block), k_flags_list, k_view<LIST>
+//   ROLE_RESPAWN           rlist, the envs the main dynamics re-spawned: k_list_chain<false> (second block: their reset pass)
+//   ROLE_DEFERRED_RESPAWN  dlist, then rlist, then the caller-side chains' terminal entries: k_view<LIST> alone (its bookkeeping workgroups: dlist)
+//   ROLE_TERMINAL          the terminal entries alone: k_view<LIST> alone (single-stream step)
+// mcr_list_len / mcr_env_of_slot / mcr_flags_list_of are the only places that map a role to a list.
+enum McrRole { ROLE_ALL = 0, ROLE_MAIN = 1, ROLE_CONTACT = 2, ROLE_DEFERRED = 3, ROLE_RESPAWN = 4, ROLE_DEFERRED_RESPAWN = 5, ROLE_TERMINAL = 6 };
+// a list launch (a small grid whose workgroups walk a device-side list) or a main launch (ROLE_ALL / ROLE_MAIN: work slot = env index)?
+// (macros: as functions, the calls inside the kernels' short-circuit conditions change the shape the optimiser gives them)
+#define mcr_is_list_role(role) ((role) >= ROLE_CONTACT)
+#define mcr_is_main_role(role) ((role) < ROLE_CONTACT)
+
+// McrParams::debug (mcr_debug_set): 0 in production.  One enumerator per bit in use; multi_car_racing_amd/_lib.py mirrors the table
+// (tests/test_abi.py compares them) and bench.py --debug-bits, tools/ and recorded profiles use the numeric values, which stay.  Classes:
+// CLOCK — results unchanged (a measurement); ABLATION — results WRONG (timing experiments only); FAULT — what tests use to model a
+// starved contact pass, a stalled stream or a lost launch.  (Bits 0-4 are the raster's own ablation switches: include/mcr.h, k_view.h's `dbg`, tools/ablate_view.py.)
+enum McrDebugBit {
+  DEBUG_VIEW_CLOCKS        = 1 << 5,    // CLOCK     launch_view: the main raster runs its PHASES instantiation, per-phase clocks in the view's scratch (mcr_debug_read_view_scratch)
+  DEBUG_POS_ITERS_2        = 1 << 6,    // ABLATION  k_dynamics: the position loops stop after 2 iterations instead of 60
+  DEBUG_VEL_ITERS_2        = 1 << 7,    // ABLATION  k_dynamics: 2 velocity iterations instead of 180
+  DEBUG_DYN_CLOCKS         = 1 << 8,    // CLOCK     k_dynamics (DYN_STAMP): lane 0 of every wavefront stamps the clock per phase into dbg_stamps (mcr_debug_read_dynamics_stamps)
+  DEBUG_NO_CC_VELOCITY     = 1 << 9,    // ABLATION  k_dynamics: the velocity sweeps skip the car<->car contact constraints
+  DEBUG_NO_CC_EXCHANGE     = 1 << 10,   // ABLATION  k_dynamics: ... and the exchange of body velocities through LDS around them
+  DEBUG_EPOCH_ACQ_REL      = 1 << 11,   // CLOCK     k_collide / k_dynamics: collide_epoch[env] is published and polled with release / acquire instead of relaxed + fences (measurements)
+  DEBUG_STARVED_COLLIDE    = 1 << 12,   // FAULT     a starved contact pass and short waits, three readers, named at each site by what they do there:
+  DEBUG_SHORT_AWAIT        = DEBUG_STARVED_COLLIDE,   //   mcr_await: the spin bounds shrink to a few milliseconds
+  DEBUG_SHORT_EPOCH_WAIT   = DEBUG_STARVED_COLLIDE,   //   k_dynamics: so do the bounds of the waits for collide_epoch[env]
+  DEBUG_WITHHOLD_ENV0_EPOCH = DEBUG_STARVED_COLLIDE,  //   k_collide pass 0: the first env's collide_epoch word is never stored
+  DEBUG_NO_SIDE_POST       = 1 << 13,   // FAULT     k_post: W_SIDE is never posted — a stalled side stream as the step's join sees it
+  DEBUG_OLD_SOLVE_ORDER    = 1 << 14,   // ABLATION  k_collide: rounds 1-3's constraint order (contacts ascending, joints 3,2,1,0)
+  DEBUG_COLLIDE_CLOCKS     = 1 << 15,   // CLOCK     k_collide (COL_STAMP): clock of lane 0 at the phase boundaries of the contact pass (tools/collide_phases.py)
+  DEBUG_DYN_CLOCKS_VEL     = 1 << 16,   // CLOCK     k_dynamics, with DEBUG_DYN_CLOCKS in an MCR_POSLOOP_PROFILE build: the contact chain's extra stamps come from the velocity sweeps, not the position loop
+  DEBUG_TRACE              = 1 << 17,   // CLOCK     MCR_TRACE: who touched an env when (diagnostics of the step's ordering)
+  DEBUG_SLOW_COLLIDE       = 1 << 18,   // FAULT     k_collide pass 0 beside the dynamics: every workgroup idles ~400 us first
+  DEBUG_FLAGS_IN_STEP      = 1 << 19,   // FAULT     step_phase_words: the main envs' flag scans stay in their step (tests, A/B runs; results unchanged)
+  DEBUG_DROP_PENDING_FLAGS = 1 << 20,   // FAULT     flush_flags: the pending scans are DROPPED — stale flags show that the results came through them
+};
+// workgroups of a main k_dynamics launch: 64 / G envs per wavefront
+__host__ __device__ __forceinline__ int mcr_dyn_blocks(int B, int G) { return (B * G + 63) / 64; }
+
 struct McrParams {
   int32_t B, N, G;              // envs, agents, lanes per env in the dynamics kernel (pow2 >= N)
   int32_t BN;                   // B*N: stride of every per-car SoA field
@@ -63,7 +110,7 @@ struct McrParams {
   uint8_t* dpart;               // [B] 1: the main k_dynamics deferred this env in this step (written for every env it handles); two buffers, by step parity
                                 // (the next step's deferred bookkeeping launch asks which envs were this step's main envs)
   uint32_t* particles;          // [B*N][MCR_PART_WORDS] skid particles of gym Car.step / _create_particle (drawn by render('rgb_array') only); null: not tracked
-  int32_t respawn_list;         // the host runs the main envs' reset pass as a list launch (role 4)
+  int32_t respawn_list;         // the host runs the main envs' reset pass as a list launch (ROLE_RESPAWN)
   int32_t list_envs_per_block;  // list launches: envs a workgroup (= a wavefront) takes at a time, 1 .. MCR_SIDE_ENVS_PER_WAVE
   uint8_t* defer_state;         // [BN] per car: 0 keep iterating, 1 position loop solved, 2 failed at a fixed point
   double* stats;                // [2] rollout statistics accumulated on the device: episodes finished, sum of their returns over all agents
@@ -77,8 +124,8 @@ struct McrParams {
   int32_t flags_deferred;       // the bookkeeping of the LAST step's main envs (k_flags.h) runs at this step's begin, on the third stream in front of k_collide
                                 // (step_phase_words): W_COL and collide_epoch[env] then also mean "last step's flags are written" (k_dynamics.h awaits them)
   int32_t split_views;          // list raster launches: one workgroup per VIEW of a listed env instead of one per env
-  int32_t use_vorder;           // k_view maps workgroups to envs through vorder (step path, roles 0/1)
-  int32_t role;                 // 0: every env; 1: main stream (skips part envs); 2: contact envs (clist); 3: deferred envs (dlist); 4: both lists
+  int32_t use_vorder;           // k_view maps workgroups to envs through vorder (step path, main roles)
+  int32_t role;                 // McrRole: which envs the launch serves
   // step I/O
   const float* actions;         // [B,N,3] or null
   uint8_t* obs;                 // [B,N,96,96,3] or null
@@ -105,8 +152,8 @@ struct McrParams {
   uint16_t* pid_stack;          // [B][MCR_PID_STACK] free leaf ids of the world's tree, last freed on top
   int32_t* pid_meta;            // [B][4] stack height, fresh leaves issued, tiles of the live episode, spare
   int32_t auto_reset, max_steps, car_contacts, backwards_flag, use_ego_color;
-  int32_t debug;                // ablation switches for profiling (0 in production)
-  unsigned long long* dbg_stamps; // [2][dyn_blocks][8] phase clocks of k_dynamics (debug bit 8)
+  int32_t debug;                // McrDebugBit switches (0 in production)
+  unsigned long long* dbg_stamps; // [2][dyn_blocks][8] phase clocks of k_dynamics (DEBUG_DYN_CLOCKS)
   double h_ratio;
 };
 
@@ -171,13 +218,13 @@ __device__ __forceinline__ void mcr_post(const McrParams& p, int w) {
 // The bound: 2^15 polls 0.2 us apart, then polls 3.4 us apart — 2^24 of them (about a minute) for the words whose wait is enqueued AHEAD
 // of the caller's stream (begin, dynamics done: whatever the caller's stream still holds in front of the step — a long inference kernel,
 // an event wait — is waited out there and must not be mistaken for a stalled stream), 2^20 (3.6 s) for the words that only the step's
-// own internal streams stand between (contact pass, side stream, third stream).  debug bit 12 shortens all of them to a few milliseconds.
+// own internal streams stand between (contact pass, side stream, third stream).  DEBUG_SHORT_AWAIT shortens all of them to a few milliseconds.
 __device__ __forceinline__ bool mcr_behind(const McrParams& p, int w, uint32_t epoch) {
   return (int32_t)((uint32_t)__hip_atomic_load(&p.sync_words[w * 16], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - epoch) < 0;
 }
 __device__ __forceinline__ bool mcr_await(const McrParams& p, int w) {
   const uint32_t epoch = (uint32_t)mcr_epoch(p);
-  const int fast = (p.debug & 4096) ? (1 << 14) : (1 << 15), slow = (p.debug & 4096) ? 0 : (w == W_BEGIN || w == W_DYN) ? (1 << 24) : (1 << 20);
+  const int fast = (p.debug & DEBUG_SHORT_AWAIT) ? (1 << 14) : (1 << 15), slow = (p.debug & DEBUG_SHORT_AWAIT) ? 0 : (w == W_BEGIN || w == W_DYN) ? (1 << 24) : (1 << 20);
   int spin = 0;
   for (; spin < fast && mcr_behind(p, w, epoch); ++spin) __builtin_amdgcn_s_sleep(8);
   if (spin < fast) return true;
@@ -193,8 +240,8 @@ __device__ __forceinline__ void term_finish(const McrParams& p) {
   for (int i = threadIdx.x; i < n; i += blockDim.x) { const McrTermEnv te = p.term_env[i]; p.consumed_host[te.env] = te.consumed; }
   if (threadIdx.x == 0) *p.term_count_out = n;
 }
-// debug bit 17 (diagnostics of the step's ordering): who touched env `env` when — dbg_stamps[(dyn blocks + env) * 8 + slot] = wall clock | tag << 56
-#define MCR_TRACE(p, env, slot, tag) do { if ((p).debug & 131072) (p).dbg_stamps[((size_t)(((p).B * (p).G + 63) / 64) + (size_t)(env)) * 8 + (slot)] = (unsigned long long)__builtin_amdgcn_s_memrealtime() | ((unsigned long long)(tag) << 56); } while (0)
+// DEBUG_TRACE (diagnostics of the step's ordering): who touched env `env` when — dbg_stamps[(dyn blocks + env) * 8 + slot] = wall clock | tag << 56
+#define MCR_TRACE(p, env, slot, tag) do { if ((p).debug & DEBUG_TRACE) (p).dbg_stamps[((size_t)mcr_dyn_blocks((p).B, (p).G) + (size_t)(env)) * 8 + (slot)] = (unsigned long long)__builtin_amdgcn_s_memrealtime() | ((unsigned long long)(tag) << 56); } while (0)
 // the touch verdict of env `env` for the NEXT step (one writer per env and step), and — fuse_collide — its place in the next step's contact list
 __device__ __forceinline__ void mcr_set_verdict(const McrParams& p, const int env, const bool v) {
   p.part_next[env] = v ? 1 : 0;
@@ -218,37 +265,40 @@ __device__ __forceinline__ int mcr_label_value(double reward) { return (reward >
 // 8 vertices (x0 y0 .. x7 y7) and slot header words live in carpoly_n: vertex count (0 = not drawn)
 #define MCR_CARPOLY_FLOATS (12 * 16 + 16)
 #define MCR_CARPOLY_NOFF (12 * 16)
-// Env handled by work slot `s` of a launch (slot = env index for roles 0/1; position in the contact / deferred / re-spawn
-// list for roles 2 / 3 / 4); returns
+// Env handled by work slot `s` of a launch (slot = env index for the main roles; position in the contact / deferred / re-spawn
+// list for ROLE_CONTACT / ROLE_DEFERRED / ROLE_RESPAWN); returns
 // p.env0 + p.nenv ("no env") for slots that are not this launch's business.
 __device__ __forceinline__ int mcr_env_of_slot(const McrParams& p, int s, bool main_dynamics = false) {
   const int end = p.env0 + p.nenv;
   if (s < 0) return end;
-  if (p.role == 2) return s < p.clist[0] ? p.clist[1 + s] : end;
-  if (p.role == 3) return s < p.dlist[0] ? p.dlist[1 + s] : end;
-  if (p.role == 4) return s < p.rlist[0] ? p.rlist[1 + s] : end;
+  if (p.role == ROLE_CONTACT) return s < p.clist[0] ? p.clist[1 + s] : end;
+  if (p.role == ROLE_DEFERRED) return s < p.dlist[0] ? p.dlist[1 + s] : end;
+  if (p.role == ROLE_RESPAWN) return s < p.rlist[0] ? p.rlist[1 + s] : end;
   const int env = p.env0 + s;
   if (env >= end) return end;
-  // role 1 = the main launches: not the contact envs (p.part: the touch verdict of this step's entry poses, written by last
+  // ROLE_MAIN = the main launches: not the contact envs (p.part: the touch verdict of this step's entry poses, written by last
   // step's bookkeeping) and — for everybody but the main dynamics, which sets that mark itself — not the envs the main
   // dynamics deferred
-  return (p.role == 1 && (p.part[env] || (!main_dynamics && p.dpart[env]))) ? end : env;
+  return (p.role == ROLE_MAIN && (p.part[env] || (!main_dynamics && p.dpart[env]))) ? end : env;
 }
-// Work slot of a k_dynamics lane.  Roles 0/1: 64/G consecutive envs per wavefront.  Role 2 (side stream, every env
+// Work slot of a k_dynamics lane.  Main roles: 64/G consecutive envs per wavefront.  ROLE_CONTACT (side stream, every env
 // holds car<->car contacts): MCR_SIDE_ENVS_PER_WAVE envs per wavefront, so that the wavefront's LDS pool of contact
 // constraints (DYN_VC_POOL = MCR_SIDE_ENVS_PER_WAVE * MCR_CC_MAX) can never overflow, however the envs are packed.
 #define MCR_SIDE_ENVS_PER_WAVE 2
 #define MCR_DEFER_AFTER 3          // position sweeps the main dynamics launch grants an env before deferring it (99.86 % need 1; 1 / 2 / 3 / 4 / 6 sweeps: 14.99 / 15.01 / 15.10 / 15.10 / 15.09 M env-steps/s)
 __device__ __forceinline__ int mcr_dyn_slot(const McrParams& p, int blk) {
   const int grp = (int)threadIdx.x / p.G;
-  if (p.role >= 2) return grp < p.list_envs_per_block ? blk * p.list_envs_per_block + grp : -1;
+  if (mcr_is_list_role(p.role)) return grp < p.list_envs_per_block ? blk * p.list_envs_per_block + grp : -1;
   return (blk * 64 + (int)threadIdx.x) / p.G;
 }
-// List launches (role >= 2: the contact / deferred envs, a few per step, how many only the device knows) run a small
+// List launches (mcr_is_list_role: the contact / deferred envs, a few per step, how many only the device knows) run a small
 // grid whose workgroups walk the list: the (virtual) block indices blockIdx, blockIdx + gridDim, .. below this bound.
 // A grid sized for the worst case would queue thousands of empty workgroups behind the raster that saturates the LDS
 // of every CU.  Main launches have exactly one block index per workgroup.
-__device__ __forceinline__ int mcr_list_len(const McrParams& p) { return p.role == 2 ? p.clist[0] : p.role == 3 ? p.dlist[0] : p.role == 4 ? p.rlist[0] : 0; }
+__device__ __forceinline__ int mcr_list_len(const McrParams& p) { return p.role == ROLE_CONTACT ? p.clist[0] : p.role == ROLE_DEFERRED ? p.dlist[0] : p.role == ROLE_RESPAWN ? p.rlist[0] : 0; }
+// the list whose cars the bookkeeping workgroups of a list raster launch take: the contact list for the contact chain's raster, the deferred list
+// otherwise (ROLE_DEFERRED, ROLE_DEFERRED_RESPAWN: the re-spawned envs' cars take none in this step)
+__device__ __forceinline__ const int32_t* mcr_flags_list_of(const McrParams& p) { return p.role == ROLE_CONTACT ? p.clist : p.dlist; }
 __device__ __forceinline__ int mcr_virtual_blocks(const McrParams& p, int slots_per_block) { return (mcr_list_len(p) + slots_per_block - 1) / slots_per_block; }
 // Skid particles (gym car_dynamics.Car: step() item "Skid trace", _create_particle, draw(viewer, True); call site
 // multi_car_racing.py:564).  Per car: a ring of the last MCR_PART_MAX particles, each a polyline of up to MCR_PART_PTS

@@ -21,6 +21,25 @@ def test_header_symbols_exported(lib):
     assert set(names) == set(lib.SYMBOLS), "multi_car_racing_amd/_lib.py binds a different symbol set than the header declares"
 
 
+def _debug_bits():
+    """enum McrDebugBit of csrc/mcr_kernels.h: name -> value (an enumerator is `1 << n` or an alias of an earlier one)"""
+    src = open(os.path.join(ROOT, "multi_car_racing_amd", "csrc", "mcr_kernels.h")).read()
+    body = re.search(r"enum McrDebugBit \{(.*?)\};", src, flags=re.S).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    out = {}
+    for name, value in re.findall(r"\b(DEBUG_[A-Z0-9_]+)\s*=\s*([^,]+),", body):
+        m = re.fullmatch(r"1 << (\d+)", value.strip())
+        out[name] = 1 << int(m.group(1)) if m else out[value.strip()]
+    return out
+
+
+def test_debug_bits_mirror_the_kernel_header(lib):
+    bits = _debug_bits()
+    assert len(bits) >= 16 and set(bits.values()) == {1 << n for n in range(5, 21)}
+    mirror = {k: v for k, v in vars(lib).items() if k.startswith("DEBUG_")}
+    assert mirror == bits, "multi_car_racing_amd/_lib.py's DEBUG_* constants differ from enum McrDebugBit in csrc/mcr_kernels.h"
+
+
 def test_version_and_sizes(lib):
     L = lib.load()
     assert b"gfx950" in L.mcr_version()

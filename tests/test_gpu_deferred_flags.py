@@ -79,7 +79,7 @@ def test_a_dropped_pending_launch_leaves_stale_flags(torch_cuda, oracle, lib):
         env = _make(B, N, seed, contacts=False, direction="CW", streams=2); env.reset()
         orcs = _oracles(oracle, B, N, seed, contacts=False, direction="CW")
         if in_step:
-            lib.check(env.L.mcr_debug_set(env.h, 1 << 19))
+            lib.check(env.L.mcr_debug_set(env.h, lib.DEBUG_FLAGS_IN_STEP))
         rng = np.random.RandomState(2)
         prev = None
         for k in range(120):
@@ -95,7 +95,7 @@ def test_a_dropped_pending_launch_leaves_stale_flags(torch_cuda, oracle, lib):
         else:
             raise AssertionError("scenario never changed a flag")
         torch.cuda.synchronize()
-        lib.check(env.L.mcr_debug_set(env.h, (1 << 20) | ((1 << 19) if in_step else 0)))
+        lib.check(env.L.mcr_debug_set(env.h, lib.DEBUG_DROP_PENDING_FLAGS | (lib.DEBUG_FLAGS_IN_STEP if in_step else 0)))
         es = env.get_env_state()
         got = np.stack([np.stack([es["driving_backward"][e], es["driving_on_grass"][e]]) for e in range(B)]).astype(np.uint8)
         if in_step:

@@ -394,7 +394,7 @@ def test_a_late_contact_pass_still_reads_the_entry_poses(torch_cuda, lib):
     a1 = _make(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=150, use_random_direction=True, streams=1)
     a2 = _make(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=150, use_random_direction=True, streams=2)
     a1.reset(); a2.reset()
-    lib.check(a2.L.mcr_debug_set(a2.h, 1 << 18))
+    lib.check(a2.L.mcr_debug_set(a2.h, lib.DEBUG_SLOW_COLLIDE))
     g = torch.Generator(device="cuda"); g.manual_seed(9)
     for k in range(320):
         a = torch.zeros((B, N, 3), device="cuda")
@@ -742,7 +742,7 @@ def test_status_word_reports_a_starved_contact_pass(torch_cuda, lib):
     a = torch.zeros((128, 2, 3), device="cuda"); a[..., 1] = 0.5
     for _ in range(3):
         env.step(a)
-    lib.check(env.L.mcr_debug_set(env.h, 4096))            # env 0's "contact pass done" word is withheld; short spin bound
+    lib.check(env.L.mcr_debug_set(env.h, lib.DEBUG_STARVED_COLLIDE))            # env 0's "contact pass done" word is withheld; short spin bound
     env.step(a); torch.cuda.synchronize()
     with pytest.raises(lib.McrError, match="gave up waiting"):
         env.step(a)
@@ -895,7 +895,7 @@ def test_status_word_reports_a_stalled_stream(torch_cuda, lib):
     torch.cuda.synchronize()
     assert env.L.mcr_step_ordering(env.h) & 1                # (mcr_bind_stream accepted the stream at the first step)
     import time
-    lib.check(env.L.mcr_debug_set(env.h, 8192))            # the side stream's completion is never posted; the wait's REAL bound applies
+    lib.check(env.L.mcr_debug_set(env.h, lib.DEBUG_NO_SIDE_POST))            # the side stream's completion is never posted; the wait's REAL bound applies
     t0 = time.perf_counter()
     env.step(a); torch.cuda.synchronize()
     assert time.perf_counter() - t0 < 8.0, "a stalled INTERNAL stream must be given up on within seconds (only the waits for the caller's stream are long)"

@@ -15,7 +15,7 @@ while G < N: G *= 2
 nb = (B * G + 63) // 64
 ns = (B + 1) // 2                      # side stream: 2 envs per wavefront
 buf = np.zeros((nb + 2 * ns) * 8, np.uint64)
-_lib.check(env.L.mcr_debug_set(env.h, 256))
+_lib.check(env.L.mcr_debug_set(env.h, _lib.DEBUG_DYN_CLOCKS))
 names = ["load+Car.step+contact init", "velocity sweeps", "position loop", "sleep+bookkeeping+epilogue"]
 acc = {0: [], 1: [], 2: []}
 for k in range(900):

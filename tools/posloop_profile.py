@@ -16,7 +16,7 @@ nb = (B * G + 63) // 64
 ns = (B + 1) // 2
 buf = np.zeros((nb + 2 * ns) * 8, np.uint64)
 VEL = int(os.environ.get("VEL", "0"))          # 1: the velocity sweeps instead (debug bit 16)
-_lib.check(env.L.mcr_debug_set(env.h, 256 | (65536 if VEL else 0)))
+_lib.check(env.L.mcr_debug_set(env.h, _lib.DEBUG_DYN_CLOCKS | (_lib.DEBUG_DYN_CLOCKS_VEL if VEL else 0)))
 rows = []
 for k in range(600):
     env.step(pool[k % 64])

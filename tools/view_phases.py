@@ -9,7 +9,7 @@ env = VecMultiCarRacing(B, N, seed=1, use_random_direction=True, auto_reset=True
 env.reset()
 pool = torch.rand((64, B, N, 3), device="cuda"); pool[..., 0] = pool[..., 0] * 2 - 1
 for k in range(80): env.step(pool[k % 64])
-_lib.check(env.L.mcr_debug_set(env.h, 32 | int(os.environ.get('DBG', 0))))
+_lib.check(env.L.mcr_debug_set(env.h, _lib.DEBUG_VIEW_CLOCKS | int(os.environ.get('DBG', 0))))
 for k in range(3): env.step(pool[k])
 torch.cuda.synchronize()
 names = ["prologue (agent 0: env-level loads) / hand-over", "wait: barrier", "clear + label + candidates (cull, set-up, scan)", "wait: barrier",
