@@ -164,6 +164,24 @@ int mcr_set_obs_format(mcr_env* h, int format, int stack);
 size_t mcr_obs_bytes_per_view(const mcr_env* h);
 /* the first ring slot of the observation after the last ENQUEUED drawing step (k > 1: 1 .. k; k = 1 and RGB: 0) */
 int mcr_obs_window(const mcr_env* h);
+/* State-vector observations: the low-dimensional observation a non-pixel policy trains on, written on the device by a kernel of its own
+ * (csrc/k_stateobs.h, which holds the feature table and the arithmetic contract) after every mcr_reset and every mcr_step, on the caller's
+ * stream behind the step — valid once that call is complete on its stream, with obs_enabled 0 or 1.  Per car F = 18 + 2 K + 4 (N - 1) f32
+ * features in raw SI / model units (no normalisation): the hull's velocity in its own frame, yaw rate, wheel speeds, steering angle, on-road
+ * bits, progress, offset and heading against the nearest track point, the episode's direction, K waypoints `stride` tiles apart ahead of the
+ * car in its frame, and every other car's relative position and velocity.  Every value is defined in IEEE f64 operations in a fixed order
+ * and rounded to f32 once: a host reproduces it bit for bit (tests/state_obs_ref.py).  Rows of envs that are not active (never reset,
+ * frozen) are zeros; an env that re-spawned in the step (auto_reset) shows the first state of its new episode, like its d_obs row.
+ * mcr_state_obs_dim: F for num_agents 1..8 and waypoints 0..16 (MCR_ERR_ARG otherwise); no handle, no GPU needed. */
+int mcr_state_obs_dim(int num_agents, int waypoints);
+/* d_state: the caller's device buffer [B, N, F] f32, F = mcr_state_obs_dim(num_agents, waypoints); NULL turns the feature off (the step path
+ * then does nothing new).  MCR_ERR_ARG for a NULL handle, waypoints outside 0..16 or stride outside 1..64.  Allowed at any time; takes effect
+ * with the next mcr_reset / mcr_step / mcr_state_obs_now.  No synchronisation. */
+int mcr_set_state_obs(mcr_env* h, float* d_state, int waypoints, int stride);
+/* Recompute the tensor from the CURRENT state on `stream` (after mcr_set_bodies / mcr_set_state_blob, which do not; tests).  MCR_ERR_STATE
+ * when no buffer is set.  Only enqueues: the features read no backward / on-grass flags, so the pending flag scans (mcr_get_env_state's
+ * note) are neither launched nor waited for. */
+int mcr_state_obs_now(mcr_env* h, void* stream);
 /* Rollout statistics accumulated on the device since creation / the last reset of the counters (synchronises):
  * out2[0] = episodes finished, out2[1] = sum of their returns over all agents.  These are the per-rank inputs of the
  * job-wide metric all-reduce. */

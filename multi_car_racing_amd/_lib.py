@@ -83,6 +83,9 @@ SYMBOLS = {
     "mcr_set_obs_format": (_i, [_vp, _i, _i]),
     "mcr_obs_bytes_per_view": (ctypes.c_size_t, [_vp]),
     "mcr_obs_window": (_i, [_vp]),
+    "mcr_state_obs_dim": (_i, [_i, _i]),
+    "mcr_set_state_obs": (_i, [_vp, _vp, _i, _i]),
+    "mcr_state_obs_now": (_i, [_vp, _vp]),
     "mcr_read_rollout_stats": (_i, [_vp, _vp, _i]),
     "mcr_render": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mcr_debug_read_contact_counts": (_i, [_vp, _vp]),
@@ -182,6 +185,11 @@ def ptr(a):
 
 def episode_bytes():
     return int(load().mcr_episode_bytes())
+
+
+def state_obs_dim(num_agents, waypoints=6):
+    """features per car of the state-vector observation (include/mcr.h: mcr_state_obs_dim): 18 + 2 * waypoints + 4 * (num_agents - 1)"""
+    return check(load().mcr_state_obs_dim(int(num_agents), int(waypoints)), "mcr_state_obs_dim")
 
 
 def unpack_episode(blob):

@@ -9,6 +9,7 @@
 #include "k_viewprep.h"
 #include "k_list_chain.h"
 #include "k_render.h"
+#include "k_stateobs.h"
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <string>
@@ -83,6 +84,7 @@ struct mcr_env {
   uint64_t obs_draws = 0;     // drawing steps enqueued (mcr_step with an observation buffer): the ring head is obs_draws mod k
   bool flags_pending = false; // the last step left the bookkeeping of its main envs (k_flags.h) to its successor (step_phase_words): flags_P launches it
   McrParams flags_P;          // ... the launch's parameters: ROLE_MAIN with that step's partition marks (its parity's part / dpart buffers), no touch verdicts
+  McrStateObs so{nullptr, 0, 0, 0};   // mcr_set_state_obs: the low-dimensional observation (k_stateobs.h); out == nullptr: off
 };
 
 static void flush_flags(mcr_env* h, hipStream_t st);
@@ -398,6 +400,14 @@ static void launch_reset(mcr_env* h, McrParams P, hipStream_t st) {
   LAUNCH_LDS(3, k_collide, B, 64, col::lds_bytes(N), st, P, 1);
   LAUNCH_DYN(4, P.car_contacts && N > 1, dyn_blocks, st, P, 1);
   if (P.obs) launch_view(h, 2, B, st, P, 1);
+}
+
+// The low-dimensional observation of the state a reset / a step ended with (k_stateobs.h), a wavefront per env on the caller's stream: behind
+// launch_reset / launch_step (whose tail makes `st` wait for the whole step), outside the step's streams and outside a replayed step graph.
+// It reads no flags: nothing is flushed.  Off (no buffer): one test.
+static void launch_state_obs(mcr_env* h, hipStream_t st) {
+  if (!h->so.out) return;
+  hipLaunchKernelGGL(k_stateobs, dim3(h->P.B), dim3(64), 0, st, h->P, h->so);
 }
 
 // may a step launched on caller stream `st` order its streams with phase words?  (mcr_bind_stream checked it; an unbound stream: events)
@@ -741,6 +751,7 @@ extern "C" int mcr_reset(mcr_env* h, const uint8_t* d_env_mask, uint8_t* d_obs, 
   h->ring.j = (int)((h->obs_draws + (uint64_t)h->ring.k - 1u) % (uint64_t)h->ring.k);     // the head of the last drawing step: the window stays put
   flush_flags(h, st);
   launch_reset(h, P, st);
+  launch_state_obs(h, st);
   HIPCHK(hipGetLastError());
   h->any_reset = true; h->verdict_fresh = false;
   return MCR_OK;
@@ -794,6 +805,8 @@ extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, doub
     if (G.valid && G.st == st && G.view_flags == vf && memcmp(&G.P, &P, sizeof(P)) == 0) {
       h->step_parity ^= 1;                              // what launch_step does on the host side
       HIPCHK(hipGraphLaunch(G.exec, st));
+      launch_state_obs(h, st);
+      HIPCHK(hipGetLastError());
       return MCR_OK;
     }
     if (G.valid) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); G.valid = false; }
@@ -804,6 +817,8 @@ extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, doub
       if (hipStreamEndCapture(st, &graph) == hipSuccess && graph && hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
         G.graph = graph; G.P = P; G.st = st; G.view_flags = vf; G.valid = true;
         HIPCHK(hipGraphLaunch(G.exec, st));
+        launch_state_obs(h, st);
+        HIPCHK(hipGetLastError());
         return MCR_OK;
       }
       if (graph) (void)hipGraphDestroy(graph);
@@ -813,6 +828,25 @@ extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, doub
     h->step_parity = parity_before;
   }
   launch_step(h, P, st, vf);
+  launch_state_obs(h, st);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+
+extern "C" int mcr_state_obs_dim(int num_agents, int waypoints) {
+  if (num_agents < 1 || num_agents > MCR_MAX_AGENTS || waypoints < 0 || waypoints > MCR_SO_WAYPOINTS_MAX) { g_err = "mcr_state_obs_dim: num_agents 1..8, waypoints 0..16"; return MCR_ERR_ARG; }
+  return mcr_so_dim(num_agents, waypoints);
+}
+extern "C" int mcr_set_state_obs(mcr_env* h, float* d_state, int waypoints, int stride) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (waypoints < 0 || waypoints > MCR_SO_WAYPOINTS_MAX || stride < 1 || stride > MCR_SO_STRIDE_MAX) { g_err = "mcr_set_state_obs: waypoints 0..16, stride 1..64"; return MCR_ERR_ARG; }
+  h->so.out = d_state; h->so.K = waypoints; h->so.stride = stride; h->so.F = mcr_so_dim(h->P.N, waypoints);
+  return MCR_OK;
+}
+extern "C" int mcr_state_obs_now(mcr_env* h, void* stream) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!h->so.out) { g_err = "mcr_state_obs_now: no buffer set (mcr_set_state_obs)"; return MCR_ERR_STATE; }
+  launch_state_obs(h, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MCR_OK;
 }

@@ -29,6 +29,14 @@ itself: [B, N, 96, 96].  With `frame_stack=k > 1` it is also gym's FrameStack(k)
 an auto-reset the env's first frame k times (gym's rule; SB3's VecFrameStack zero-fills instead).  The stack is a strided VIEW of a ring of
 2k frames per agent that the raster writes in place (include/mcr.h: mcr_set_obs_format): nothing is shifted or copied, and the view
 changes with every step — keep the tensor step() returns, not an older one.
+
+State-vector observation: `state_obs=True` adds what a non-pixel policy trains on, with `obs=True` or `obs=False`: `self.state`, a persistent
+float32 device tensor [B, N, F] that a kernel of its own (csrc/k_stateobs.h: the feature table) rewrites after every reset() / reset_envs() /
+step() on the stepping stream, also handed out as info["state"].  F = 18 + 2 * state_waypoints + 4 * (N - 1) raw, un-normalised features
+per car: own velocity in the hull's frame, yaw rate, wheel speeds, steering angle, on-road bits, progress, offset and heading against the
+nearest track point, the episode's direction, `state_waypoints` track points `state_stride` tiles apart ahead of the car, and the other
+cars' relative positions and velocities.  The row of an env that auto-reset in the step describes the first state of its new episode, like
+its `obs` row.  After set_bodies() / set_state_blob() call refresh_state().
 """
 import atexit
 import collections
@@ -68,7 +76,8 @@ class VecMultiCarRacing:
                  use_random_direction=True, backwards_flag=True, h_ratio=0.25, use_ego_color=False,
                  obs=True, auto_reset=True, max_episode_steps=1000, car_contacts=True,
                  gen_threads=None, async_refill=True, streams=None, refill_lag=64, world_size=1, graph=None,
-                 skid_particles=False, terminal_obs=False, terminal_cap=None, fresh_world=False, obs_format="rgb", frame_stack=1):
+                 skid_particles=False, terminal_obs=False, terminal_cap=None, fresh_world=False, obs_format="rgb", frame_stack=1,
+                 state_obs=False, state_waypoints=6, state_stride=5):
         if not torch.cuda.is_available():
             raise _lib.McrError("VecMultiCarRacing needs a HIP device: the step path has no CPU fallback")
         self.L = _lib.load()
@@ -163,6 +172,14 @@ class VecMultiCarRacing:
             self.terminal_count = torch.zeros((1,), dtype=torch.int32, device=self.device)
             _lib.check(self.L.mcr_set_terminal_obs(self.h, ctypes.c_void_p(self.terminal_obs.data_ptr()), ctypes.c_void_p(self.terminal_env_ids.data_ptr()),
                                                    ctypes.c_void_p(self.terminal_count.data_ptr()), cap), "mcr_set_terminal_obs")
+        # state-vector observation (include/mcr.h: mcr_set_state_obs): [B, N, F] f32, rewritten by every reset / step on the stepping stream
+        self.state = None
+        self.state_shape = None
+        if state_obs:
+            F = _lib.state_obs_dim(self.N, int(state_waypoints))
+            self.state = torch.zeros((self.B, self.N, F), dtype=torch.float32, device=self.device)
+            self.state_shape = (self.N, F)
+            _lib.check(self.L.mcr_set_state_obs(self.h, ctypes.c_void_p(self.state.data_ptr()), int(state_waypoints), int(state_stride)), "mcr_set_state_obs")
         # RNG streams
         self.mt_track = np.zeros((self.B, _lib.MT_WORDS), np.uint32)
         self.mt_draw = np.zeros((self.B, _lib.MT_WORDS), np.uint32)
@@ -407,7 +424,18 @@ class VecMultiCarRacing:
             info["terminal_observation"] = self.terminal_obs
             info["terminal_env_ids"] = self.terminal_env_ids
             info["terminal_count"] = self.terminal_count
+        if self.state is not None:
+            info["state"] = self.state
         return self.obs, self.reward, self.done, info
+
+    def refresh_state(self):
+        """Recompute `self.state` from the CURRENT state on the current stream (include/mcr.h: mcr_state_obs_now) — after set_bodies() /
+        set_state_blob(), which do not; reset() and step() keep it current by themselves.  Returns the tensor; does not synchronise."""
+        if self.state is None:
+            raise _lib.McrError("created without state_obs=True")
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_state_obs_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_state_obs_now")
+        return self.state
 
     def _obs_ptr(self):
         """the observation buffer the raster writes: the frames, or the ring of a stacked format"""
