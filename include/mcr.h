@@ -131,6 +131,26 @@ int mcr_reset(mcr_env* h, const uint8_t* d_env_mask, uint8_t* d_obs, void* strea
  * With auto_reset, a finished env's obs row is the first observation of its next episode (its last frame: mcr_set_terminal_obs). */
 int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* d_reward, uint8_t* d_done,
              uint8_t* d_trunc, void* stream);
+/* Action repeat (frame skip): ONE macro-step = FrameSkip_repeat(TimeLimit(env)) per env, auto-reset outside it.  The same d_actions drive up to
+ * `repeat` consecutive env steps (sub-steps) of every env; an env stops at the sub-step in which its episode ends (all tiles visited, out of
+ * the playfield, TimeLimit — which keeps counting env steps, as do d_ep_len and mcr_refill_lag's epochs).  Per env:
+ *   d_reward   the f64 sum of its sub-step rewards, added in sub-step order starting from the first one's value (gym's `total += r`)
+ *   d_done     the OR of the sub-steps' flags (with auto_reset at most one episode ends per env and macro-step); d_trunc: the ending sub-step's
+ *   d_obs      drawn ONCE, from the state after the last sub-step; a stacked ring advances once (one drawing step: mcr_obs_window moves by one),
+ *              so the stack holds macro-step frames; the state-vector observation (mcr_set_state_obs) is written once, too
+ * With auto_reset an env whose episode ended in the macro-step is re-spawned in its LAST sub-step and shows the first observation (first state) of
+ * the next episode, which this macro-step has not advanced; episode, proxy ids and RNG streams are those of a re-spawn in the ending sub-step.
+ * In between the env is parked (inactive, zero outputs) — not starved: neither mcr_debug_read_counters [3] nor mcr_status word 4 count it, unless
+ * the host has staged no episode by the last sub-step (then it is an ordinary frozen env from there on).  A frozen env thaws in a last sub-step only.
+ * Without auto_reset a finished env goes through the later sub-steps as it goes through later mcr_step calls.
+ * repeat == 1 is mcr_step (which forwards here): the same launches, the same bits.  repeat > 1: the sub-steps are ordinary steps of the same
+ * topology, enqueued without synchronising, the first repeat - 1 without a draw; MCR_ERR_ARG for NULL d_actions or a repeat outside
+ * 1 .. MCR_REPEAT_MAX.  With mcr_set_step_graph(1) a macro-step of repeat > 1 runs as plain launches (no macro-step graph is captured).
+ * With terminal observations set (mcr_set_terminal_obs) repeat > 1 returns MCR_ERR_STATE: the terminal frame would have to be drawn in a
+ * sub-step that draws nothing — the follow-up to this entry. */
+#define MCR_REPEAT_MAX 16
+int mcr_step_repeat(mcr_env* h, const float* d_actions, int repeat, uint8_t* d_obs, double* d_reward, uint8_t* d_done,
+                    uint8_t* d_trunc, void* stream);
 /* render(mode) at another viewport (multi_car_racing.py:511-604 with VP_W x VP_H of :573-586; 'rgb_array' = 600 x 400):
  * the CURRENT state of env `env` as seen by each of its agents, d_out [N, height, width, 3] u8 (device), rows top-down.
  * Needs obs_enabled. */

@@ -10,6 +10,7 @@ TILE_CAP = 512
 QUAD_CAP = 768
 MT_WORDS = 625
 OBS_RGB, OBS_GRAY, OBS_STACK_MAX = 0, 1, 8
+REPEAT_MAX = 16                 # include/mcr.h: MCR_REPEAT_MAX
 
 # mcr_debug_set bits: the mirror of enum McrDebugBit (csrc/mcr_kernels.h, which says what each one does; tests/test_abi.py compares the two)
 DEBUG_VIEW_CLOCKS = 1 << 5
@@ -60,6 +61,7 @@ SYMBOLS = {
     "mcr_stage_episodes": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mcr_reset": (_i, [_vp, _vp, _vp, _vp]),
     "mcr_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcr_step_repeat": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "mcr_poll_consumed": (_i, [_vp, _vp, _i, _vp]),
     "mcr_refill_start": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "mcr_refill_stop": (_i, [_vp]),

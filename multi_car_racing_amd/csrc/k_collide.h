@@ -118,6 +118,10 @@ __device__ __forceinline__ void collide_block(const McrParams& p, const int pass
     // contact pass in front (single stream, N > 4, serialised kernels): this pass owns the contact chain's marks — an env
     // that froze while its cars were touching must not keep a stale one (it would be skipped by every main launch)
     if (pass == 0 && p.split && !p.cc_mode && lane == 0) p.part[env] = 0;
+    // beside the dynamics (cc_mode): the main dynamics may thaw the env in this very step — not before this pass has looked at the record and
+    // turned away (a parked env of a macro-step, mcr_step_repeat, thaws in a launch whose wavefronts have nothing else to do: microseconds
+    // into the step, while this launch is still starting); it waits for the env's word like a running env's epilogue does
+    if (pass == 0 && p.cc_mode && lane == 0) __hip_atomic_store(&p.collide_epoch[env], mcr_epoch(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return;
   }
   if (pass == 1 && !es.resetting) return;

@@ -813,9 +813,14 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   // Thaw: an env that finished while the host had not staged its next episode yet was frozen (inactive, zero
   // outputs).  As soon as the staged slot is filled, the next step's main launch re-spawns it exactly like the
   // auto-reset of a `done` step does (install -> reset pass -> first observation); reward/done of that step are 0.
+  // Action repeat (mcr_step_repeat, McrParams::defer_respawn): a sub-step that is not the macro-step's last re-spawns nobody.  An env whose
+  // episode ends there is PARKED through the same freeze (frozen = MCR_PARKED instead of 1: not starved — no count, no ST_FROZEN) and the
+  // macro-step's last sub-step thaws it, as it thaws a starved env; one that finds no staged episode even then becomes an ordinary frozen
+  // env there.  (A starved env does not thaw in the middle of a macro-step either: every re-spawned env shows a first observation.)
   const bool frozen_now = lane_ok && mode == 0 && mcr_is_main_role(p.role) && !es.active && es.frozen && p.auto_reset;
-  const bool thaw = frozen_now && es.staged_ready;
-  if (frozen_now && agent == 0) atomicAdd(&p.counters[3], 1ull);          // env-steps that produced nothing
+  const bool thaw = frozen_now && es.staged_ready && !p.defer_respawn;
+  const bool starved = frozen_now && (es.frozen != MCR_PARKED || (!p.defer_respawn && !es.staged_ready));
+  if (starved && agent == 0) atomicAdd(&p.counters[3], 1ull);             // env-steps that produced nothing
 
   const McrShapes& S = *p.shapes;
   const float mH = S.hull_invMass, iH = S.hull_invI, mW = S.wheel_invMass, iW = S.wheel_invI;
@@ -1502,7 +1507,8 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   // behind it here, the word is long posted) and an env of the main launch that thaws (inactive: the contact pass has no word for it).
   // The resume chain awaits W_COL in its prologue.
   const bool col_word = p.flags_deferred && mode == 0 && (p.role == ROLE_CONTACT || (p.role == ROLE_MAIN && thaw));
-  if ((p.cc_mode && mode == 0 && p.role == ROLE_MAIN && run) || col_word)   // k_collide pass 0 runs beside this launch: wait until it is through with this env
+  // (a thawing env, too: the contact pass must have seen the record inactive before the re-spawn rewrites it — k_collide.h posts the word for it)
+  if ((p.cc_mode && mode == 0 && p.role == ROLE_MAIN && (run || thaw)) || col_word)   // k_collide pass 0 runs beside this launch: wait until it is through with this env
   {
     // p.epoch is the handle's step counter: no earlier pass can have left the same value behind.  The wait is bounded (~3 s; on the
     // phase-word path this launch is enqueued first and the contact pass after it, on another stream, so the bound also covers the host's
@@ -1562,14 +1568,22 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
         atomicAdd(&p.stats[1], epret);
       }
     }
-    if (lane_ok && es.active) {
+    if (lane_ok && es.active && p.accumulate) {
+      // A later sub-step of a macro-step (mcr_step_repeat) adds to what the earlier ones left: the f64 sum in sub-step order, the OR of the
+      // flags; an inactive env (parked, frozen) adds nothing.  Plain loads and stores by the lane that stores today.  The earlier sub-step's
+      // kernel of this env has stored before this one loads, whichever chains the two ran in: an env changes chains only across whole steps,
+      // and this kernel has loaded the car state which that kernel wrote back BEHIND its reward (car_store below) — every step's kernels
+      // are ordered behind the step before (stream order, the events, the phase words the streams meet through).
+      p.reward_out[ci] = p.reward_out[ci] + step_reward;
+      if (agent == 0) { if (done) p.done_out[env] = 1; if (trunc && p.trunc_out) p.trunc_out[env] = 1; }
+    } else if (lane_ok && es.active) {
       p.reward_out[ci] = step_reward;
       if (agent == 0) { p.done_out[env] = done ? 1 : 0; if (p.trunc_out) p.trunc_out[env] = trunc ? 1 : 0; }
-    } else if (lane_ok) {
+    } else if (lane_ok && !p.accumulate) {
       p.reward_out[ci] = 0.0;
       if (agent == 0) { p.done_out[env] = 0; if (p.trunc_out) p.trunc_out[env] = 0; }
     }
-    respawn = (run && done && p.auto_reset && es.staged_ready) || thaw;
+    respawn = (run && done && p.auto_reset && es.staged_ready && !p.defer_respawn) || thaw;
   }
   // ---- terminal observation (mcr_set_terminal_obs): an episode that ends with a re-spawn leaves an ENTRY — what its frames need of the state
   // the cars end it with — before the spawn poses overwrite that state; the env's reset pass and the list raster of its chain do the rest
@@ -1609,7 +1623,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
         E->t = es.t + 1.0 / MCR_FPS;
         if (p.actions) E->steps = es.steps + 1;
         E->just_reset = 0;
-        if (done && p.auto_reset) { E->active = 0; E->frozen = 1; mcr_raise(p, ST_FROZEN); if (p.part_next) { p.part[env] = 0; p.part_next[env] = 0; } }   // no staged episode yet (host refill late): frozen until it arrives, see `thaw` (a frozen env is the main launch's)
+        if (done && p.auto_reset) { E->active = 0; E->frozen = p.defer_respawn ? MCR_PARKED : 1; if (!p.defer_respawn) mcr_raise(p, ST_FROZEN); if (p.part_next) { p.part[env] = 0; p.part_next[env] = 0; } }   // no staged episode yet (host refill late): frozen until it arrives, see `thaw` (a frozen env is the main launch's)
       }
       // raster launch order: zoomed-out frames (first second of an episode, :540-542) cost several times a normal
       // one, so their workgroups go FIRST (front of vorder) and cannot end up as the launch's tail
@@ -1631,6 +1645,9 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
       E->resetting = 0;
     }
   }
+
+  // (a parked env that finds no staged episode in the macro-step's last sub-step: starved from here on, and reported)
+  if (starved && es.frozen == MCR_PARKED && agent == 0) { p.env[env].frozen = 1; mcr_raise(p, ST_FROZEN); }
 
   if (run || thaw) {
   if (respawn) {

@@ -133,6 +133,7 @@ enum {
 // pair (pa, pb), pa = carA * 8 + fixA < pb: 0 = no contact (the fat AABBs do not overlap), else 1 + the label of the FindNewContacts
 // batch that made it
 MCR_HD size_t mcr_cc_stamp_words(int N) { return 2 + (size_t)64 * N * N; }
+#define MCR_PARKED 2       // McrEnvState::frozen of an env that waits for the end of its macro-step, not for the host
 // per-env state
 struct McrEnvState {
   double t;                // self.t
@@ -143,7 +144,9 @@ struct McrEnvState {
   int32_t active;          // 0 until the first reset
   int32_t resetting;       // episode installed; the action-less step of reset() (:408) is still pending
   int32_t just_reset;      // the obs being produced is a first observation (a7 bookkeeping is skipped, :435)
-  int32_t frozen;          // auto-reset found no staged episode when this env finished: inactive until the host stages one (then it thaws)
+  int32_t frozen;          // 1: auto-reset found no staged episode when this env finished: inactive until the host stages one (then it thaws);
+                           // MCR_PARKED: the episode ended in a sub-step of a macro-step (mcr_step_repeat) that is not its last: inactive until
+                           // the last sub-step re-spawns it through the same thaw.  Parked envs exist only inside a macro-step
   uint32_t touch_blocks;   // bit b: some tile of block b (MCR_TBLK tiles) had a wheel on it after the last contact pass (k_collide looks at those + the ones near a car)
   uint32_t bp_step;        // contact passes this episode has seen (the reset pass is 0): labels the batches of the broadphase model (k_collide.h), owned by k_collide
 };

@@ -757,20 +757,15 @@ extern "C" int mcr_reset(mcr_env* h, const uint8_t* d_env_mask, uint8_t* d_obs, 
   return MCR_OK;
 }
 
-extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* d_reward, uint8_t* d_done, uint8_t* d_trunc, void* stream) {
-  if (!h || !d_reward || !d_done) { g_err = "null argument"; return MCR_ERR_ARG; }
-  if (!h->any_reset) { g_err = "step() before reset()"; return MCR_ERR_STATE; }
-  if (h->ring.k > 1 && !d_obs) { g_err = "mcr_step: a stacked observation format needs d_obs every step (a skipped draw leaves a hole in the ring)"; return MCR_ERR_ARG; }
-  if (int rc = check_status(h)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (h->use_graph <= 0) {
-    // a step captured by the CALLER cannot be replayed: its launches carry this step's epoch and list parity as constants.  The supported
-    // way to replay a step is mcr_set_step_graph (the handle captures both parities itself and keeps the epoch in device memory).
-    if (capturing(st)) { g_err = "mcr_step inside a stream capture: use mcr_set_step_graph for graph replay"; return MCR_ERR_STATE; }
-  }
+// One env step of a checked call: mcr_step's only one, or sub-step `sub` of the `repeat` of a macro-step (mcr_step_repeat; mcr_kernels.h has the
+// table of what each sub-step carries).  The handle's bookkeeping — step counter, list parity, verdicts, fused list, pending scans — advances
+// here, per env step.  Sub-steps in front of the last one draw nothing, write no state observation and are not replayed from the step graph.
+static int step_one(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* d_reward, uint8_t* d_done, uint8_t* d_trunc, hipStream_t st, int sub, int repeat) {
+  const bool last = sub == repeat - 1;
   McrParams P = h->P;
-  P.actions = d_actions; P.obs = h->cfg.obs_enabled ? d_obs : nullptr;
+  P.actions = d_actions; P.obs = (h->cfg.obs_enabled && last) ? d_obs : nullptr;
   P.reward_out = d_reward; P.done_out = d_done; P.trunc_out = d_trunc;
+  P.defer_respawn = last ? 0 : 1; P.accumulate = sub > 0 ? 1 : 0;
   P.bp_fresh = h->bp_fresh ? 1 : 0; h->bp_fresh = false;
   if (P.obs) { h->ring.j = (int)(h->obs_draws % (uint64_t)h->ring.k); ++h->obs_draws; }
   h->step_count = (int32_t)((uint32_t)h->step_count + 1u);      // (wraps: epochs are compared as 32-bit distances, mcr_kernels.h)
@@ -795,7 +790,7 @@ extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, doub
   }
   h->verdict_fresh = vf != 0;             // this step's bookkeeping evaluates the next step's
   h->last_fused = fz && vf != 0;
-  if (h->use_graph > 0 && !h->timing) {
+  if (h->use_graph > 0 && !h->timing && repeat == 1) {
     // The step is a fixed sequence of ~13 launches on up to three streams whose arguments only change with the
     // contact-list parity: it can be replayed as a hipGraph (measured r02: 0.4 % faster — the gaps between the step's
     // dependent kernels are GPU-side drain/start-up, not host launch cost — so VecMultiCarRacing leaves it off).  Any change of an argument
@@ -828,9 +823,31 @@ extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, doub
     h->step_parity = parity_before;
   }
   launch_step(h, P, st, vf);
-  launch_state_obs(h, st);
+  if (last) launch_state_obs(h, st);
   HIPCHK(hipGetLastError());
   return MCR_OK;
+}
+
+extern "C" int mcr_step_repeat(mcr_env* h, const float* d_actions, int repeat, uint8_t* d_obs, double* d_reward, uint8_t* d_done, uint8_t* d_trunc, void* stream) {
+  if (!h || !d_reward || !d_done) { g_err = "null argument"; return MCR_ERR_ARG; }
+  if (repeat < 1 || repeat > MCR_REPEAT_MAX) { g_err = "mcr_step_repeat: repeat 1 .. MCR_REPEAT_MAX"; return MCR_ERR_ARG; }
+  if (repeat > 1 && !d_actions) { g_err = "mcr_step_repeat: repeat > 1 needs actions (the action-less step belongs to reset)"; return MCR_ERR_ARG; }
+  if (!h->any_reset) { g_err = "step() before reset()"; return MCR_ERR_STATE; }
+  if (h->ring.k > 1 && !d_obs) { g_err = "mcr_step: a stacked observation format needs d_obs every step (a skipped draw leaves a hole in the ring)"; return MCR_ERR_ARG; }
+  if (repeat > 1 && h->term_slab) { g_err = "mcr_step_repeat: repeat > 1 with terminal observations is not supported (the terminal frame would be drawn in a sub-step that draws nothing)"; return MCR_ERR_STATE; }
+  if (int rc = check_status(h)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (h->use_graph <= 0) {
+    // a step captured by the CALLER cannot be replayed: its launches carry this step's epoch and list parity as constants.  The supported
+    // way to replay a step is mcr_set_step_graph (the handle captures both parities itself and keeps the epoch in device memory).
+    if (capturing(st)) { g_err = "mcr_step inside a stream capture: use mcr_set_step_graph for graph replay"; return MCR_ERR_STATE; }
+  }
+  for (int sub = 0; sub < repeat; ++sub)
+    if (int rc = step_one(h, d_actions, d_obs, d_reward, d_done, d_trunc, st, sub, repeat)) return rc;
+  return MCR_OK;
+}
+extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* d_reward, uint8_t* d_done, uint8_t* d_trunc, void* stream) {
+  return mcr_step_repeat(h, d_actions, 1, d_obs, d_reward, d_done, d_trunc, stream);
 }
 
 extern "C" int mcr_state_obs_dim(int num_agents, int waypoints) {

@@ -126,6 +126,15 @@ struct McrParams {
   int32_t split_views;          // list raster launches: one workgroup per VIEW of a listed env instead of one per env
   int32_t use_vorder;           // k_view maps workgroups to envs through vorder (step path, main roles)
   int32_t role;                 // McrRole: which envs the launch serves
+  // action repeat (include/mcr.h: mcr_step_repeat): sub-step i of a macro-step of k steps is an ordinary step with
+  //   sub-step           defer_respawn   accumulate   obs
+  //   0                  1               0            null
+  //   1 .. k - 2         1               1            null
+  //   k - 1              0               1            the caller's
+  // (mcr_step, k = 1: 0, 0, the caller's).  Every dynamics launch of the step carries them, whatever its role: the epilogue is shared.
+  int32_t defer_respawn;        // no env is re-spawned by this step: one whose episode ends is parked (McrEnvState::frozen = MCR_PARKED: inactive, zero
+                                // outputs, neither counted nor reported as starved), and no frozen env thaws; the step that clears it re-spawns them all
+  int32_t accumulate;           // the epilogue ADDS the step's reward to reward_out and ORs done / truncated into done_out / trunc_out; inactive envs write nothing
   // step I/O
   const float* actions;         // [B,N,3] or null
   uint8_t* obs;                 // [B,N,96,96,3] or null

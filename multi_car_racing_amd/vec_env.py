@@ -37,6 +37,14 @@ per car: own velocity in the hull's frame, yaw rate, wheel speeds, steering angl
 nearest track point, the episode's direction, `state_waypoints` track points `state_stride` tiles apart ahead of the car, and the other
 cars' relative positions and velocities.  The row of an env that auto-reset in the step describes the first state of its new episode, like
 its `obs` row.  After set_bodies() / set_state_blob() call refresh_state().
+
+Action repeat: `frame_skip=k` (1..16) makes step() one MACRO-step, gym's FrameSkip_k(TimeLimit(env)) per env with the auto-reset outside it
+(include/mcr.h: mcr_step_repeat): the same actions drive up to k env steps of every env, an env stops at the step that ends its episode,
+`reward` is the f64 sum of the env steps' rewards in order, `done` their OR, `truncated` the ending step's; `max_episode_steps`,
+`episode_length` and `refill_lag` keep counting env steps.  Observations are drawn once, from the state after the last env step, so a
+`frame_stack` holds policy-step frames (FrameStack(FrameSkip(env))) and `self.state` is written once.  With `auto_reset` an env whose episode
+ended inside the macro-step shows the first observation of its next episode, which that macro-step has not advanced.  `frame_skip=1` is
+the plain step.  Not with `terminal_obs=True`, and step(None) — reset()'s action-less step — needs `frame_skip=1`.
 """
 import atexit
 import collections
@@ -77,7 +85,12 @@ class VecMultiCarRacing:
                  obs=True, auto_reset=True, max_episode_steps=1000, car_contacts=True,
                  gen_threads=None, async_refill=True, streams=None, refill_lag=64, world_size=1, graph=None,
                  skid_particles=False, terminal_obs=False, terminal_cap=None, fresh_world=False, obs_format="rgb", frame_stack=1,
-                 state_obs=False, state_waypoints=6, state_stride=5):
+                 state_obs=False, state_waypoints=6, state_stride=5, frame_skip=1):
+        frame_skip = int(frame_skip)
+        if not 1 <= frame_skip <= _lib.REPEAT_MAX:
+            raise ValueError(f"frame_skip must be 1..{_lib.REPEAT_MAX}, got {frame_skip}")
+        if frame_skip > 1 and terminal_obs:
+            raise ValueError("frame_skip > 1 cannot be combined with terminal_obs=True (the terminal frame would belong to an env step that draws nothing)")
         if not torch.cuda.is_available():
             raise _lib.McrError("VecMultiCarRacing needs a HIP device: the step path has no CPU fallback")
         self.L = _lib.load()
@@ -99,6 +112,7 @@ class VecMultiCarRacing:
             raise ValueError("max_episode_steps must be 0 or at least frame_stack: a terminal stack reads the ring copies of the episode's last "
                              "frame_stack - 1 frames")
         self.obs_format, self.frame_stack = obs_format, frame_stack
+        self.frame_skip = frame_skip      # env steps per step() call (include/mcr.h: mcr_step_repeat)
         if streams is None:           # contact side stream (include/mcr.h: num_streams) pays as soon as there is a batch
             streams = 2 if int(num_envs) >= 64 and int(num_agents) > 1 and car_contacts else 1
         self.auto_reset = bool(auto_reset)
@@ -385,17 +399,21 @@ class VecMultiCarRacing:
         return self.obs
 
     def step(self, actions):
-        """actions: float32 device tensor [B,N,3] (steer, gas, brake) or None. Returns (obs, reward, done, info)."""
+        """actions: float32 device tensor [B,N,3] (steer, gas, brake) or None. Returns (obs, reward, done, info).
+        With frame_skip=k > 1 one call is a macro-step of up to k env steps per env (module docstring); actions must not be None then."""
+        if actions is None and self.frame_skip > 1:
+            raise ValueError("step(None) needs frame_skip=1: the action-less step belongs to reset()")
         st = torch.cuda.current_stream(self.device)
         self._raise_worker_error()
         if self._svc:
             lag = int(self.L.mcr_refill_lag(self.h))
             if lag < 0:
                 _lib.check(lag, "mcr_refill_lag")
-            behind = lag >= max(1, self.refill_lag - 4)      # (the service notices a consumption up to a few steps after it happened)
+            # (the service notices a consumption up to a few steps after it happened; the lag counts env steps, and this call adds frame_skip of them)
+            behind = lag + self.frame_skip - 1 >= max(1, self.refill_lag - 4)
         else:
             with self._pending_lock:          # (the refill worker pops entries under the same lock)
-                behind = bool(self._pending) and self._step_idx - self._pending[0] >= self.refill_lag
+                behind = bool(self._pending) and self._step_idx + self.frame_skip - 1 - self._pending[0] >= self.refill_lag
         if behind:
             t0 = time.perf_counter()
             self.wait_refills()               # the host fell behind: block instead of letting an env freeze
@@ -410,10 +428,10 @@ class VecMultiCarRacing:
             if actions.numel() != self.B * self.N * 3:
                 raise ValueError(f"actions must have {self.B * self.N * 3} elements, got {actions.numel()}")
             a_ptr = ctypes.c_void_p(actions.data_ptr())
-        _lib.check(self.L.mcr_step(self.h, a_ptr, self._obs_ptr(),
-                                   ctypes.c_void_p(self.reward.data_ptr()), ctypes.c_void_p(self.done.data_ptr()),
-                                   ctypes.c_void_p(self.truncated.data_ptr()), ctypes.c_void_p(st.cuda_stream)), "mcr_step")
-        self._step_idx += 1                   # (only a step that was launched counts: a reported McrError leaves the accounting alone)
+        _lib.check(self.L.mcr_step_repeat(self.h, a_ptr, self.frame_skip, self._obs_ptr(),
+                                          ctypes.c_void_p(self.reward.data_ptr()), ctypes.c_void_p(self.done.data_ptr()),
+                                          ctypes.c_void_p(self.truncated.data_ptr()), ctypes.c_void_p(st.cuda_stream)), "mcr_step_repeat")
+        self._step_idx += self.frame_skip     # env steps (only a step that was launched counts: a reported McrError leaves the accounting alone)
         if self._ring is not None:
             self.obs = self._window()
         self._warn_degraded()
