@@ -271,6 +271,36 @@ size_t mcr_state_blob_bytes(const mcr_env* h);
 int mcr_get_state_blob(mcr_env* h, int env, void* blob_out);
 int mcr_set_state_blob(mcr_env* h, int env, const void* blob);
 
+/* ---- the same snapshots as BATCHED, stream-ordered device operations (planning with the simulator as the model: fork a
+ * state into K candidates, roll them out, rewind; restore-to-state exploration; checkpoints of the envs).  One kernel
+ * (csrc/k_envcopy.h), one workgroup per listed env.  The calls only enqueue on `stream` — the stepping stream — and never
+ * synchronise; the pending flag scans of a phase-word step are launched in front, like for every reader / writer of env state.
+ *   d_blobs     [n][mcr_state_blob_pitch] bytes of device memory, 16-byte aligned.  The first mcr_state_blob_bytes bytes of a
+ *               row are exactly what mcr_get_state_blob writes, header (magic, N, flags word, total bytes) included; the
+ *               bytes up to the pitch are zero.
+ *   d_env_ids   [n] int32 on the device: the env of row i; NULL: envs 0 .. n-1.
+ *   n           0 .. num_envs (0: MCR_OK, nothing is launched).
+ * mcr_load_states / mcr_copy_states follow mcr_set_state_blob's rule: slot, staged_ready and consumed of the env record
+ * stay the TARGET's, the episode image goes into the target's current slot, the staged slot and the install counters are
+ * not touched (an env restored on an auto_reset handle continues with that handle's own next staged episode).  The next
+ * step re-evaluates the touch verdicts and the contact list; if a state-vector buffer is set (mcr_set_state_obs) it is
+ * rewritten behind the copy.  Observation buffers are not part of the state and are not redrawn: the next step draws them.
+ * mcr_load_states SKIPS a row, leaving its env untouched, when the row's header is not this handle's (another build,
+ * num_agents, skid_particles or fresh_world setting) or its id is outside 0 .. num_envs-1, and counts it with one atomic
+ * add into *d_refused (int32 on the device, zeroed by the caller; may be NULL).  mcr_save_states writes a zero header —
+ * a row mcr_load_states refuses — for an id out of range; mcr_copy_states skips a pair with such an id.
+ * The caller's obligations, NOT checked: destination ids are distinct, and in mcr_copy_states (env d_dst_ids[i] becomes a
+ * copy of env d_src_ids[i]; a source may be listed many times) disjoint from the sources — a violation is a data race
+ * between workgroups with an unspecified result.
+ * MCR_ERR_ARG: NULL handle or buffer, misaligned d_blobs, n out of range.  MCR_ERR_STATE: save / copy before the first
+ * reset; any of the three inside a caller's stream capture. */
+size_t mcr_state_blob_pitch(const mcr_env* h);   /* mcr_state_blob_bytes rounded up to 16; 0 for NULL */
+/* the four header words a blob of this handle starts with (what mcr_load_states compares) */
+int mcr_state_blob_header(const mcr_env* h, uint32_t* out4);
+int mcr_save_states(mcr_env* h, const int32_t* d_env_ids, int n, void* d_blobs, void* stream);
+int mcr_load_states(mcr_env* h, const int32_t* d_env_ids, int n, const void* d_blobs, int32_t* d_refused, void* stream);
+int mcr_copy_states(mcr_env* h, const int32_t* d_src_ids, const int32_t* d_dst_ids, int n, void* stream);
+
 /* ---- synthetic workload (bench.py, tests): counter-based action stream, action of (global env, agent) at step t is a
  * pure function of (seed, env_offset + env, agent, t): steer ~ U(-1,1), gas ~ U(0,1), brake ~ U(0,1) (the action_space
  * bounds, multi_car_racing.py:162-165).  Device version writes d_actions [B,N,3] f32 on `stream`; the host twin produces

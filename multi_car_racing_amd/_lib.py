@@ -115,6 +115,11 @@ SYMBOLS = {
     "mcr_state_blob_bytes": (ctypes.c_size_t, [_vp]),
     "mcr_get_state_blob": (_i, [_vp, _i, _vp]),
     "mcr_set_state_blob": (_i, [_vp, _i, _vp]),
+    "mcr_state_blob_pitch": (ctypes.c_size_t, [_vp]),
+    "mcr_state_blob_header": (_i, [_vp, _vp]),
+    "mcr_save_states": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "mcr_load_states": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "mcr_copy_states": (_i, [_vp, _vp, _vp, _i, _vp]),
     "mcr_synth_actions": (_i, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp]),
     "mcr_synth_actions_block": (_i, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _i, ctypes.c_uint32, _vp]),
     "mcr_synth_actions_host": (None, [_vp, _i, _i, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),

@@ -10,6 +10,7 @@
 #include "k_list_chain.h"
 #include "k_render.h"
 #include "k_stateobs.h"
+#include "k_envcopy.h"
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <string>
@@ -1371,6 +1372,124 @@ extern "C" int mcr_set_state_blob(mcr_env* h, int env, const void* blob) {
     HIPCHK(hipMemcpy(P.pid_meta + (size_t)env * 4, b + L.world + sizeof(uint16_t) * (MCR_PID_TAB + MCR_PID_STACK), sizeof(int32_t) * 4, hipMemcpyHostToDevice));
   }
   h->any_reset = true; h->verdict_fresh = false;
+  return MCR_OK;
+}
+
+// ---------------------------------------------------------------------------- batched snapshot / restore / clone on the device (k_envcopy.h)
+namespace {
+// The segment table of k_envcopy: blob_layout()'s sections, in blob order, as (device array, strides, rows) — the device format is the host
+// format by construction — with the bytes between two sections (and up to the row pitch) as EC_ZERO entries.
+int envcopy_table(const mcr_env* h, McrEnvCopy& a) {
+  const McrParams& P = h->P; const uint64_t N = (uint64_t)P.N, BN = (uint64_t)P.BN;
+  const BlobLayout L = blob_layout(P.N, P.particles != nullptr);
+  const size_t pitch = align_up(L.total, 16);
+  a.nseg = 0; a.B = P.B; a.pitch = pitch; a.env = P.env;
+  a.hdr[0] = BLOB_MAGIC; a.hdr[1] = (uint32_t)P.N; a.hdr[2] = (P.particles ? 1u : 0u) | (P.pid_tab ? 2u : 0u); a.hdr[3] = (uint32_t)L.total;
+  auto width = [](uint64_t bits) { uint64_t w = 16; while (bits & (w - 1)) w >>= 1; return (uint8_t)w; };
+  size_t cursor = 16;                                                    // the header: the kernel's own
+  bool ok = true;
+  auto push = [&](const McrEcSeg& g) { if (a.nseg < MCR_EC_MAX_SEGS) a.seg[a.nseg++] = g; else ok = false; };
+  auto zero_to = [&](size_t off) {
+    if (off > cursor) { McrEcSeg z{}; z.kind = EC_ZERO; z.rows = 1; z.row_bytes = (uint32_t)(off - cursor); z.blob_off = (uint32_t)cursor; z.w_blob = z.w_env = width(cursor | (off - cursor)); push(z); }
+    cursor = off;
+  };
+  auto add = [&](int kind, const void* base, uint64_t env_stride, uint64_t rows, uint64_t row_stride, uint64_t row_bytes, size_t off) {
+    zero_to(off);
+    McrEcSeg g{}; g.kind = (uint8_t)kind; g.base = (uint8_t*)base; g.env_stride = env_stride; g.rows = (uint32_t)rows; g.row_stride = row_stride;
+    g.row_bytes = (uint32_t)row_bytes; g.blob_off = (uint32_t)off;
+    g.w_env = width((uint64_t)(uintptr_t)base | env_stride | row_bytes | (rows > 1 ? row_stride : 0) | (kind == EC_SLOT ? (uint64_t)MCR_SLOT_BYTES : 0));
+    g.w_blob = width((uint64_t)g.w_env | off);                           // (blob rows start at multiples of 16: checked by the calls)
+    push(g); cursor = off + rows * row_bytes;
+  };
+  const uint64_t ccw = MCR_CC_MAX * MCR_CC_WORDS + 4;
+  add(EC_PLAIN, P.carf, 4 * N, CF_COUNT, 4 * BN, 4 * N, L.carf);
+  add(EC_PLAIN, P.card, 8 * N, CD_COUNT, 8 * BN, 8 * N, L.card);
+  add(EC_PLAIN, P.caru, 4 * N, CU_COUNT, 4 * BN, 4 * N, L.caru);
+  add(EC_ENVREC, P.env, sizeof(McrEnvState), 1, 0, sizeof(McrEnvState), L.es);
+  add(EC_PLAIN, P.tile_touch, 4 * MCR_TILE_CAP, 1, 0, 4 * MCR_TILE_CAP, L.touch);
+  add(EC_PLAIN, P.tile_flags, 2 * MCR_TILE_CAP, 1, 0, 2 * MCR_TILE_CAP, L.tflags);
+  add(EC_PLAIN, P.cc_store, 4 * ccw, 1, 0, 4 * ccw, L.cc);
+  add(EC_PLAIN, P.viewp, 4 * MCR_VIEWP_FLOATS * N, 1, 0, 4 * MCR_VIEWP_FLOATS * N, L.viewp);
+  add(EC_PLAIN, P.carpoly, 4 * MCR_CARPOLY_FLOATS * N, 1, 0, 4 * MCR_CARPOLY_FLOATS * N, L.carpoly);
+  add(EC_PLAIN, P.bpf, sizeof(float4) * MCR_BP_FIX * N, BP_COUNT, sizeof(float4) * MCR_BP_FIX * BN, sizeof(float4) * MCR_BP_FIX * N, L.bpf);
+  add(EC_PLAIN, P.bp_stamp, 4 * (uint64_t)MCR_TILE_CAP * 4 * N, 1, 0, 4 * (uint64_t)MCR_TILE_CAP * 4 * N, L.stamp);
+  add(EC_PLAIN, P.cc_stamp, 4 * mcr_cc_stamp_words(P.N), 1, 0, 4 * mcr_cc_stamp_words(P.N), L.ccstamp);
+  add(EC_SLOT, P.slots, 2 * (uint64_t)MCR_SLOT_BYTES, 1, 0, MCR_SLOT_BYTES, L.slot);
+  if (P.pid_tab) {
+    add(EC_PLAIN, P.pid_tab, 2 * MCR_PID_TAB, 1, 0, 2 * MCR_PID_TAB, L.world);
+    add(EC_PLAIN, P.pid_stack, 2 * MCR_PID_STACK, 1, 0, 2 * MCR_PID_STACK, L.world + 2 * MCR_PID_TAB);
+    add(EC_PLAIN, P.pid_meta, 16, 1, 0, 16, L.world + 2 * (MCR_PID_TAB + MCR_PID_STACK));
+  }
+  if (P.particles) add(EC_PLAIN, P.particles, 4 * (uint64_t)MCR_PART_WORDS * N, 1, 0, 4 * (uint64_t)MCR_PART_WORDS * N, L.particles);
+  zero_to(pitch);
+  if (!ok) { g_err = "state copy: the segment table is full (MCR_EC_MAX_SEGS)"; return MCR_ERR_STATE; }
+  return MCR_OK;
+}
+// what the three calls share: arguments, the capture rule, the pending flag scans in front (they read and write what the copy reads and writes)
+int envcopy_begin(mcr_env* h, int n, hipStream_t st, const char* who) {
+  if (n < 0 || n > h->P.B) { g_err = std::string(who) + ": n must be 0 .. num_envs"; return MCR_ERR_ARG; }
+  if (capturing(st)) { g_err = std::string(who) + " inside a stream capture (the handle's host bookkeeping would not be replayed)"; return MCR_ERR_STATE; }
+  return MCR_OK;
+}
+// restore / clone: mcr_set_state_blob's host bookkeeping (the next step re-evaluates the touch verdicts and the contact list) and the state vector
+void envcopy_wrote(mcr_env* h, hipStream_t st) {
+  h->any_reset = true; h->verdict_fresh = false;
+  launch_state_obs(h, st);
+}
+}  // namespace
+
+extern "C" size_t mcr_state_blob_pitch(const mcr_env* h) { return h ? align_up(mcr_state_blob_bytes(h), 16) : 0; }
+extern "C" int mcr_state_blob_header(const mcr_env* h, uint32_t* out4) {
+  if (!h || !out4) { g_err = "null argument"; return MCR_ERR_ARG; }
+  out4[0] = BLOB_MAGIC; out4[1] = (uint32_t)h->P.N; out4[2] = (h->P.particles ? 1u : 0u) | (h->P.pid_tab ? 2u : 0u); out4[3] = (uint32_t)mcr_state_blob_bytes(h);
+  return MCR_OK;
+}
+
+extern "C" int mcr_save_states(mcr_env* h, const int32_t* d_env_ids, int n, void* d_blobs, void* stream) {
+  if (!h || !d_blobs) { g_err = "mcr_save_states: null argument"; return MCR_ERR_ARG; }
+  if (((uintptr_t)d_blobs & 15) != 0) { g_err = "mcr_save_states: d_blobs must be 16-byte aligned"; return MCR_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = envcopy_begin(h, n, st, "mcr_save_states")) return rc;
+  if (!h->any_reset) { g_err = "mcr_save_states before reset()"; return MCR_ERR_STATE; }
+  if (n == 0) return MCR_OK;
+  McrEnvCopy a{};
+  if (int rc = envcopy_table(h, a)) return rc;
+  a.ids = d_env_ids; a.src_ids = nullptr; a.blobs = (uint8_t*)d_blobs; a.refused = nullptr;
+  flush_flags(h, st);
+  hipLaunchKernelGGL(k_envcopy<ENV_TO_BLOB>, dim3(n), dim3(MCR_EC_LANES), 0, st, a);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+
+extern "C" int mcr_load_states(mcr_env* h, const int32_t* d_env_ids, int n, const void* d_blobs, int32_t* d_refused, void* stream) {
+  if (!h || !d_blobs) { g_err = "mcr_load_states: null argument"; return MCR_ERR_ARG; }
+  if (((uintptr_t)d_blobs & 15) != 0) { g_err = "mcr_load_states: d_blobs must be 16-byte aligned"; return MCR_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = envcopy_begin(h, n, st, "mcr_load_states")) return rc;
+  if (n == 0) return MCR_OK;
+  McrEnvCopy a{};
+  if (int rc = envcopy_table(h, a)) return rc;
+  a.ids = d_env_ids; a.src_ids = nullptr; a.blobs = (uint8_t*)d_blobs; a.refused = d_refused;
+  flush_flags(h, st);
+  hipLaunchKernelGGL(k_envcopy<BLOB_TO_ENV>, dim3(n), dim3(MCR_EC_LANES), 0, st, a);
+  envcopy_wrote(h, st);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+
+extern "C" int mcr_copy_states(mcr_env* h, const int32_t* d_src_ids, const int32_t* d_dst_ids, int n, void* stream) {
+  if (!h || !d_src_ids || !d_dst_ids) { g_err = "mcr_copy_states: null argument"; return MCR_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = envcopy_begin(h, n, st, "mcr_copy_states")) return rc;
+  if (!h->any_reset) { g_err = "mcr_copy_states before reset()"; return MCR_ERR_STATE; }
+  if (n == 0) return MCR_OK;
+  McrEnvCopy a{};
+  if (int rc = envcopy_table(h, a)) return rc;
+  a.ids = d_dst_ids; a.src_ids = d_src_ids; a.blobs = nullptr; a.refused = nullptr;
+  flush_flags(h, st);
+  hipLaunchKernelGGL(k_envcopy<ENV_TO_ENV>, dim3(n), dim3(MCR_EC_LANES), 0, st, a);
+  envcopy_wrote(h, st);
+  HIPCHK(hipGetLastError());
   return MCR_OK;
 }
 

@@ -45,6 +45,15 @@ Action repeat: `frame_skip=k` (1..16) makes step() one MACRO-step, gym's FrameSk
 `frame_stack` holds policy-step frames (FrameStack(FrameSkip(env))) and `self.state` is written once.  With `auto_reset` an env whose episode
 ended inside the macro-step shows the first observation of its next episode, which that macro-step has not advanced.  `frame_skip=1` is
 the plain step.  Not with `terminal_obs=True`, and step(None) — reset()'s action-less step — needs `frame_skip=1`.
+
+Batched snapshots: `save_states()`, `load_states()` and `clone_envs()` are get_state_blob / set_state_blob for many envs at once, as one
+kernel each (csrc/k_envcopy.h; include/mcr.h: mcr_save_states) — for planning with the simulator as the model (fork a state into K
+candidates, roll them out, rewind), restore-to-state exploration and checkpoints of the envs.  They are STREAM-ORDERED and ASYNCHRONOUS:
+enqueued on the current stream, which must be the stepping stream, with ids that may live on the device; nothing synchronises unless
+load_states(check=True) is asked to validate on the host.  The blob rows are byte for byte what get_state_blob returns.  The staging
+protocol stays the target's: an env restored or cloned on an `auto_reset=True` handle continues with that handle's own next staged episode
+when its episode ends (set_state_blob's rule) — planning handles are normally created with `auto_reset=False`.  Observations are not part
+of the state: clone_envs copies the rows of `obs`, load_states leaves them to the next step (and refuses `frame_stack > 1`).
 """
 import atexit
 import collections
@@ -566,6 +575,111 @@ class VecMultiCarRacing:
         blob = np.ascontiguousarray(blob, np.uint8)
         _lib.check(self.L.mcr_set_state_blob(self.h, int(e), _lib.ptr(blob)), "mcr_set_state_blob")
         self._has_reset = self._has_reset or True
+
+    # ------------------------------------------------------------------ batched snapshots on the device (stream-ordered; module docstring)
+    @property
+    def state_blob_pitch(self):
+        """bytes per row of a save_states() tensor: mcr_state_blob_bytes rounded up to 16"""
+        return int(self.L.mcr_state_blob_pitch(self.h))
+
+    def _env_ids(self, ids, what, distinct=False):
+        """env ids -> (int32 device tensor or None, count, host array or None).  A sequence is validated here (range, and
+        distinctness where asked: ValueError); a device tensor is taken as it is — the kernel skips ids out of range."""
+        if ids is None:
+            return None, self.B, None
+        if torch.is_tensor(ids):
+            if ids.dim() != 1:
+                raise ValueError(f"{what} must be one-dimensional")
+            if ids.numel() > self.B:
+                raise ValueError(f"{what}: at most num_envs = {self.B} ids, got {ids.numel()}")
+            return ids.to(device=self.device, dtype=torch.int32).contiguous(), int(ids.numel()), None
+        host = np.asarray(list(ids), dtype=np.int64).reshape(-1)
+        if len(host) > self.B:
+            raise ValueError(f"{what}: at most num_envs = {self.B} ids, got {len(host)}")
+        if len(host) and (host.min() < 0 or host.max() >= self.B):
+            raise ValueError(f"{what} must be in 0..{self.B - 1}")
+        if distinct and len(np.unique(host)) != len(host):
+            raise ValueError(f"{what} must be distinct")
+        return torch.from_numpy(host.astype(np.int32)).to(self.device), len(host), host
+
+    def save_states(self, env_ids=None, out=None):
+        """Snapshot envs `env_ids` (None: all; a sequence; an int32 device tensor) into a uint8 device tensor [n, state_blob_pitch]: row i
+        starts with exactly the bytes of get_state_blob(env_ids[i]).  One kernel on the current stream; does not synchronise."""
+        ids, n, _ = self._env_ids(env_ids, "env_ids")
+        pitch = self.state_blob_pitch
+        if out is None:
+            out = torch.empty((n, pitch), dtype=torch.uint8, device=self.device)
+        elif (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.device != self.device or tuple(out.shape) != (n, pitch)
+              or not out.is_contiguous() or out.data_ptr() % 16):
+            raise ValueError(f"out must be a contiguous, 16-byte aligned uint8 tensor [{n}, {pitch}] on {self.device}")
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_save_states(self.h, None if ids is None else ctypes.c_void_p(ids.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
+                                          ctypes.c_void_p(st.cuda_stream)), "mcr_save_states")
+        return out
+
+    def load_states(self, blobs, env_ids=None, check=True):
+        """Restore rows of a save_states() tensor into envs `env_ids` (None: row i into env i) of this handle — any handle with the same
+        num_agents, skid_particles and fresh_world; stepping continues bit-identically (set_state_blob's rule: an env restored on an
+        auto_reset handle continues with THIS handle's next staged episode when its episode ends).  `self.state` is rewritten; the
+        observation buffers are not redrawn (the next step draws them).  check=True validates on the host first — shape, ids given as a
+        sequence, the header words of every row: ValueError, nothing changed — which synchronises, and raises McrError if the kernel
+        refused a row.  check=False never synchronises and returns the int32 device counter [1] of refused rows (rows whose header is not
+        this handle's, ids out of range: those envs stay untouched)."""
+        if self.frame_stack > 1:
+            raise ValueError("load_states with frame_stack > 1: a restored env has no frame history to fill its stack with")
+        pitch = self.state_blob_pitch
+        if not torch.is_tensor(blobs) or blobs.dtype != torch.uint8 or blobs.dim() != 2 or blobs.shape[1] != pitch:
+            raise ValueError(f"blobs must be a uint8 tensor [n, {pitch}] (save_states)")
+        ids, n, _ = self._env_ids(env_ids, "env_ids", distinct=check)
+        if env_ids is None:
+            n = int(blobs.shape[0])
+            if n > self.B:
+                raise ValueError(f"blobs has {n} rows, the handle {self.B} envs")
+        elif blobs.shape[0] != n:
+            raise ValueError(f"blobs has {blobs.shape[0]} rows for {n} env ids")
+        if blobs.device != self.device or not blobs.is_contiguous() or blobs.data_ptr() % 16:
+            blobs = blobs.to(self.device).contiguous().clone()
+        if check and n:
+            want = np.zeros(4, np.uint32)
+            _lib.check(self.L.mcr_state_blob_header(self.h, _lib.ptr(want)), "mcr_state_blob_header")
+            got = blobs[:, :16].cpu().numpy().view(np.uint32)
+            bad = np.nonzero((got != want[None]).any(1))[0]
+            if len(bad):
+                raise ValueError(f"rows {bad[:8].tolist()} are not state blobs of this handle (header {got[bad[0]].tolist()}, expected {want.tolist()}: "
+                                 "magic, num_agents, skid_particles | one-world tables << 1, bytes)")
+        refused = torch.zeros(1, dtype=torch.int32, device=self.device)
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_load_states(self.h, None if ids is None else ctypes.c_void_p(ids.data_ptr()), n, ctypes.c_void_p(blobs.data_ptr()),
+                                          ctypes.c_void_p(refused.data_ptr()), ctypes.c_void_p(st.cuda_stream)), "mcr_load_states")
+        self._has_reset = True
+        if not check:
+            return refused
+        k = int(refused.item())
+        if k:
+            raise _lib.McrError(f"load_states: the kernel refused {k} rows (their envs are untouched)")
+        return refused
+
+    def clone_envs(self, src_ids, dst_ids, check=True):
+        """Env dst_ids[i] becomes a copy of env src_ids[i] (a source may be listed many times): the state by one kernel (mcr_copy_states),
+        then the rows of obs (the ring of a stacked format), reward, done and truncated, so that the clone is observationally equal at once;
+        `self.state` is rewritten.  Destinations must be distinct and disjoint from the sources — validated (ValueError) with check=True when
+        the ids are sequences, the caller's obligation otherwise.  On the current stream; does not synchronise."""
+        src, n, src_h = self._env_ids(src_ids, "src_ids")
+        dst, m, dst_h = self._env_ids(dst_ids, "dst_ids", distinct=check)
+        if src is None or dst is None:
+            raise ValueError("clone_envs needs src_ids and dst_ids")
+        if n != m:
+            raise ValueError(f"{n} src_ids for {m} dst_ids")
+        if check and src_h is not None and dst_h is not None and len(np.intersect1d(src_h, dst_h)):
+            raise ValueError("dst_ids must be disjoint from src_ids")
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_copy_states(self.h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()), n,
+                                          ctypes.c_void_p(st.cuda_stream)), "mcr_copy_states")
+        s64, d64 = src.long(), dst.long()
+        frames = self._ring if self._ring is not None else self.obs
+        for t in (frames, self.reward, self.done, self.truncated):
+            if t is not None and n:
+                t.index_copy_(0, d64, t.index_select(0, s64))
 
     def synth_actions(self, t, seed=0, out=None, steps=None):
         """Counter-based synthetic actions (bench/tests): a pure function of (seed, global env index, agent, t).  Step t as a
