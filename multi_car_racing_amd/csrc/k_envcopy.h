@@ -1,9 +1,10 @@
 // k_envcopy.h — batched snapshot / restore / clone of env states on the device (include/mcr.h: mcr_save_states, mcr_load_states,
-// mcr_copy_states).  One kernel, three modes: env -> blob row, blob row -> env, env -> env.  The blob bytes are those of mcr_get_state_blob
-// (mcr_hip.hip: blob_layout), header included; the kernel knows nothing about that layout: it walks a SEGMENT TABLE the host derives from
-// blob_layout() for every call (mcr_hip.hip: envcopy_table), one entry per blob section — where the section lives on the device (base, bytes
-// between two envs, rows, bytes between two rows, bytes per row) and where in the blob — plus EC_ZERO entries for the bytes the host version
-// leaves zero (padding between sections, an absent world section, the tail up to the row pitch).
+// mcr_copy_states).  One kernel, three modes: env -> blob row, blob row -> env, env -> env.  The blob bytes are those of mcr_get_state_blob,
+// header included; the kernel knows nothing about that layout: it walks a SEGMENT TABLE the host makes for every call (mcr_state.hip:
+// envcopy_table) from the one description of an env's state, state_sections() — the table mcr_get_state_blob / mcr_set_state_blob walk
+// too, so sections, strides and blob offsets cannot differ between the host and the device format.  One entry per section this handle has —
+// where it lives on the device (base, bytes between two envs, rows, bytes between two rows, bytes per row) and where in the blob — plus
+// EC_ZERO entries for the bytes the host version leaves zero (padding between sections, an absent world section, the tail up to the row pitch).
 //
 // One workgroup per listed env; the workgroup takes the segments one after the other, its lanes striding over each.  The kernel moves bytes
 // and computes nothing: what counts is the width of the accesses and how many are in flight.  The host picks the access width per segment —
@@ -23,7 +24,7 @@
 #include <cstddef>
 
 #define MCR_EC_LANES 256
-#define MCR_EC_MAX_SEGS 28         // 17 sections + the gaps between them
+#define MCR_EC_MAX_SEGS 28         // every state section + the gaps between them (mcr_state.hip: a static_assert beside the section table)
 enum McrEnvCopyMode { ENV_TO_BLOB = 0, BLOB_TO_ENV = 1, ENV_TO_ENV = 2 };
 enum McrEcKind {
   EC_PLAIN = 0,

@@ -43,12 +43,6 @@
 #define MCR_SO_TILES_PER_LANE (MCR_TILE_CAP / 64)
 MCR_HD int mcr_so_dim(int N, int K) { return MCR_SO_BASE + 2 * K + 4 * (N - 1); }
 
-// launch argument beside McrParams (null `out`: the feature is off and nothing is launched)
-struct McrStateObs {
-  float* out;                   // [B][N][F] the caller's device buffer
-  int32_t K, stride, F;         // waypoints, tiles between them, features per car
-};
-
 #ifndef MCR_DEVICE_FUNCTIONS_ONLY
 __global__ __launch_bounds__(64) void k_stateobs(McrParams p, McrStateObs so) {
   const int lane = (int)threadIdx.x;

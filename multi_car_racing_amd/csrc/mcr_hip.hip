@@ -1,7 +1,6 @@
 // mcr_hip.hip — C-ABI implementation (include/mcr.h) over the gfx950 kernels.
 // One handle owns one env slice on one device: SoA car state, per-env state, two episode slots per env.
-#include "../../include/mcr.h"
-#include "mcr_kernels.h"
+#include "mcr_env.h"
 #include "k_dynamics.h"
 #include "k_collide.h"
 #include "k_raster_common.h"
@@ -10,7 +9,6 @@
 #include "k_list_chain.h"
 #include "k_render.h"
 #include "k_stateobs.h"
-#include "k_envcopy.h"
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <string>
@@ -21,76 +19,11 @@
 
 void mcr_build_shapes(McrShapes* S);   // mcr_host.cpp
 
-static thread_local std::string g_err;
+thread_local std::string g_err;
 extern "C" const char* mcr_last_error(void) { return g_err.c_str(); }
 extern "C" const char* mcr_version(void) { return "mcr-hip 0.1 (gfx950)"; }
 
-#define HIPCHK(x)                                                                                         \
-  do {                                                                                                    \
-    hipError_t e_ = (x);                                                                                  \
-    if (e_ != hipSuccess) {                                                                               \
-      g_err = std::string(#x) + ": " + hipGetErrorString(e_);                                             \
-      return MCR_ERR_HIP;                                                                                 \
-    }                                                                                                     \
-  } while (0)
-
 #define MCR_LIST_GRID 128        // workgroups of a list launch (they walk the device-side list)
-struct TimedLaunch { int id; hipEvent_t a, b; };
-
-struct mcr_env {
-  mcr_config cfg;
-  McrParams P;
-  void* slab;
-  size_t slab_bytes;
-  int32_t* consumed_host;     // mapped host memory
-  int32_t* consumed_seen;     // host copy of the last polled counters
-  int timing;                 // bit mask of kernel ids to time with HIP events
-  std::vector<TimedLaunch> pending;
-  std::vector<hipEvent_t> free_events;
-  double t_ms[MCR_TIMING_SLOTS]; int64_t t_n[MCR_TIMING_SLOTS];
-  bool any_reset;
-  bool split;                 // contact side stream enabled (cfg.num_streams == 2)
-  int step_parity;            // which contact-list buffer the next step fills
-  int32_t* stage_ids;         // [B] device scratch of mcr_stage_episodes
-  hipStream_t s_side, s_defer; // internal streams: the contact envs' chain, the deferred envs' chain
-  hipEvent_t ev_fork, ev_join, ev_fork2, ev_join2, ev_col;
-  unsigned long long* view_stamps;   // [BN][16] phase clocks of the rasteriser (DEBUG_VIEW_CLOCKS)
-  // hipGraph of one step (mcr_set_step_graph): one per contact-list parity, re-captured when any argument changes
-  struct StepGraph { bool valid; McrParams P; hipStream_t st; int view_flags; hipGraph_t graph; hipGraphExec_t exec; };
-  StepGraph sg[2 * MCR_OBS_STACK_MAX];   // [ring head j][parity] (mcr_set_obs_format: the raster's launches carry j)
-  int use_graph;              // 0 off, 1 on, -1 capture failed once: stay off
-  bool concurrent_collide;    // the contact pass may run beside the main dynamics (kernels of different streams do overlap here: probed at create)
-  bool verdict_fresh;         // the touch verdicts (k_touch.h) of the next step's entry poses are in place (last step's bookkeeping wrote them)
-  bool last_fused = false;    // ... and so is the next step's contact list (the last step ran with McrParams::fuse_collide)
-  uint32_t* status_host;      // [MCR_STATUS_WORDS] mapped host memory the kernels report trouble in (mcr_kernels.h: ST_*)
-  uint32_t status_seen[MCR_STATUS_WORDS];   // what mcr_step has already reported
-  int32_t step_count;         // steps launched: the epoch of the three-chain step's per-env "contact pass done" words
-  bool bp_fresh;              // mcr_set_bodies teleported cars: the next contact pass re-creates their broadphase proxies
-  int simd_count;             // SIMDs of the device (4 per CU)
-  int32_t* dev_step_ctr;      // device-side step counter (the epoch of a replayed step graph)
-  bool viewprep_in_flags;     // three-chain step: k_viewprep (side stream, beside the bookkeeping) produces the main envs' view records / car polygons
-  int list_view_grid;         // workgroups of a list raster launch
-  std::vector<std::pair<hipStream_t, bool>> bound;   // caller streams checked by mcr_bind_stream: may the step order its streams with phase words when launched on this one?
-  bool soft_denied = false;   // kernels overlap here, but another handle of this process holds the device's one phase-word token (mcr_create)
-  bool soft_token = false;    // this handle is its device's one phase-word handle (mcr_create)
-  bool soft_sync = false;     // the step's streams meet through phase words in device memory (mcr_kernels.h: mcr_post / mcr_await) instead of events
-  int chain_grid;             // workgroups of a list chain launch (each walks the list, 2 envs at a time)
-  bool vorder_dirty[2];       // the raster order list of that step parity was filled by a step that did not draw
-  void* term_slab = nullptr;  // terminal observations (mcr_set_terminal_obs): entry state, view records, per-parity counters and lists
-  int32_t* term_cnt2 = nullptr;   // [2][4] counters by step parity
-  int32_t* term_list2 = nullptr;  // [2][2][cap] entry lists by step parity and chain
-  struct RefillSvc* svc = nullptr;  // mcr_refill_start: the handle's own host thread that generates and stages consumed episodes
-  bool obs_gray = false;      // mcr_set_obs_format: the raster's GRAY instantiations ...
-  McrObsRing ring{nullptr, 1, 0};   // ... and where their frames go (ring.j: set per launch)
-  uint64_t obs_draws = 0;     // drawing steps enqueued (mcr_step with an observation buffer): the ring head is obs_draws mod k
-  bool flags_pending = false; // the last step left the bookkeeping of its main envs (k_flags.h) to its successor (step_phase_words): flags_P launches it
-  McrParams flags_P;          // ... the launch's parameters: ROLE_MAIN with that step's partition marks (its parity's part / dpart buffers), no touch verdicts
-  McrStateObs so{nullptr, 0, 0, 0};   // mcr_set_state_obs: the low-dimensional observation (k_stateobs.h); out == nullptr: off
-};
-
-static void flush_flags(mcr_env* h, hipStream_t st);
-static hipError_t sync_state(mcr_env* h);
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // Does the three-chain step run the contact pass BESIDE the main dynamics?  Only where kernels of different streams overlap
 // (probed at create), up to 7 cars per env (measured), and only for batches whose main dynamics launch puts at most one of its
 // 256-VGPR wavefronts on a SIMD: that launch waits INSIDE the kernel for words of the contact pass, which must be able to get onto
@@ -379,14 +312,14 @@ static void launch_view(mcr_env* h, int kid, int slots, hipStream_t st, const Mc
 // the scans read or write (CU_FLAGS, poses, env records, episode slots) launches them first, on the stream its own work goes to — every state
 // getter / setter, reset, render, and a step that takes another path than the last one.  The scans depend on nothing a later call changes:
 // the poses, env records and episode slots are the ones the step ended with until the next step's dynamics writes back.
-static void flush_flags(mcr_env* h, hipStream_t st) {
+void flush_flags(mcr_env* h, hipStream_t st) {
   if (!h->flags_pending) return;
   h->flags_pending = false;
   if (h->P.debug & DEBUG_DROP_PENDING_FLAGS) return;     // (tests): the pending launch is DROPPED — stale flags show that the results came through it
   hipLaunchKernelGGL(k_flags, dim3(h->flags_P.B * h->flags_P.N), dim3(64), 0, st, h->flags_P);
 }
 // the synchronous calls (state getters / setters): the device's work is complete and so is the pending bookkeeping (null stream, waited for)
-static hipError_t sync_state(mcr_env* h) {
+hipError_t sync_state(mcr_env* h) {
   hipError_t e = hipDeviceSynchronize();
   if (e == hipSuccess && h->flags_pending) { flush_flags(h, nullptr); e = hipDeviceSynchronize(); }
   return e;
@@ -406,7 +339,7 @@ static void launch_reset(mcr_env* h, McrParams P, hipStream_t st) {
 // The low-dimensional observation of the state a reset / a step ended with (k_stateobs.h), a wavefront per env on the caller's stream: behind
 // launch_reset / launch_step (whose tail makes `st` wait for the whole step), outside the step's streams and outside a replayed step graph.
 // It reads no flags: nothing is flushed.  Off (no buffer): one test.
-static void launch_state_obs(mcr_env* h, hipStream_t st) {
+void launch_state_obs(mcr_env* h, hipStream_t st) {
   if (!h->so.out) return;
   hipLaunchKernelGGL(k_stateobs, dim3(h->P.B), dim3(64), 0, st, h->P, h->so);
 }
@@ -416,7 +349,7 @@ static bool stream_bound(const mcr_env* h, hipStream_t st) {
   for (const auto& b : h->bound) if (b.first == st) return b.second;
   return false;
 }
-static bool capturing(hipStream_t st) { hipStreamCaptureStatus c = hipStreamCaptureStatusNone; (void)hipStreamIsCapturing(st, &c); return c != hipStreamCaptureStatusNone; }
+bool capturing(hipStream_t st) { hipStreamCaptureStatus c = hipStreamCaptureStatusNone; (void)hipStreamIsCapturing(st, &c); return c != hipStreamCaptureStatusNone; }
 // Does a three-chain step launched on `st` order its streams with phase words (step_phase_words)?  Otherwise with events (step_events).
 static bool phase_words(const mcr_env* h, hipStream_t st) {
   return h->soft_sync && h->use_graph <= 0 && !capturing(st) && stream_bound(h, st);
@@ -1202,313 +1135,6 @@ extern "C" int mcr_refill_lag(mcr_env* h) {
 extern "C" int mcr_refill_debug(mcr_env* h, long long* out8) { if (!h || !h->svc || !out8) return MCR_ERR_STATE; for (int i = 0; i < 8; ++i) out8[i] = h->svc->dbg[i]; return MCR_OK; }
 extern "C" int mcr_refill_hold(mcr_env* h, int hold) { if (!h || !h->svc) return MCR_ERR_STATE; h->svc->hold.store(hold != 0); return MCR_OK; }
 extern "C" long long mcr_refill_generated(mcr_env* h) { return (h && h->svc) ? h->svc->generated.load() : 0; }
-
-// ---------------------------------------------------------------------------- state access (synchronous)
-extern "C" int mcr_get_state(mcr_env* h, float* bodies, float* joints, double* wheels, int32_t* limit, uint8_t* on_road, float* sleep) {
-  if (!h) return MCR_ERR_ARG;
-  HIPCHK(sync_state(h));
-  const size_t BN = h->P.BN;
-  std::vector<float> cf(CF_COUNT * BN); std::vector<double> cd(CD_COUNT * BN); std::vector<uint32_t> cu(CU_COUNT * BN);
-  HIPCHK(hipMemcpy(cf.data(), h->P.carf, cf.size() * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cd.data(), h->P.card, cd.size() * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cu.data(), h->P.caru, cu.size() * 4, hipMemcpyDeviceToHost));
-  for (size_t c = 0; c < BN; ++c) {
-    if (bodies) for (int k = 0; k < 5; ++k) {
-      float* o = bodies + (c * 5 + k) * 6;
-      o[0] = cf[(CF_CX + k) * BN + c]; o[1] = cf[(CF_CY + k) * BN + c]; o[2] = cf[(CF_A + k) * BN + c];
-      o[3] = cf[(CF_VX + k) * BN + c]; o[4] = cf[(CF_VY + k) * BN + c]; o[5] = cf[(CF_W + k) * BN + c];
-    }
-    if (sleep) for (int k = 0; k < 5; ++k) sleep[c * 5 + k] = cf[(CF_SLEEP + k) * BN + c];
-    for (int k = 0; k < 4; ++k) {
-      if (joints) { float* o = joints + (c * 4 + k) * 4; o[0] = cf[(CF_JIX + k) * BN + c]; o[1] = cf[(CF_JIY + k) * BN + c]; o[2] = cf[(CF_JIZ + k) * BN + c]; o[3] = cf[(CF_JM + k) * BN + c]; }
-      if (wheels) {
-        double* o = wheels + (c * 4 + k) * 5;
-        o[0] = k >= 2 ? cd[(CD_GAS + k - 2) * BN + c] : 0.0; o[1] = cd[CD_BRAKE * BN + c]; o[2] = k < 2 ? cd[CD_STEER * BN + c] : 0.0;
-        o[3] = cd[(CD_PHASE + k) * BN + c]; o[4] = cd[(CD_OMEGA + k) * BN + c];
-      }
-      if (limit) limit[c * 4 + k] = (cu[CU_LIMIT * BN + c] >> (2 * k)) & 3;
-      if (on_road) on_road[c * 4 + k] = (cu[CU_ONROAD * BN + c] >> k) & 1;
-    }
-  }
-  return MCR_OK;
-}
-
-extern "C" int mcr_set_bodies(mcr_env* h, const float* bodies) {
-  if (!h || !bodies) return MCR_ERR_ARG;
-  HIPCHK(sync_state(h));
-  const size_t BN = h->P.BN;
-  std::vector<float> cf(30 * BN);
-  for (size_t c = 0; c < BN; ++c) for (int k = 0; k < 5; ++k) {
-    const float* o = bodies + (c * 5 + k) * 6;
-    cf[(CF_CX + k) * BN + c] = o[0]; cf[(CF_CY + k) * BN + c] = o[1]; cf[(CF_A + k) * BN + c] = o[2];
-    cf[(CF_VX + k) * BN + c] = o[3]; cf[(CF_VY + k) * BN + c] = o[4]; cf[(CF_W + k) * BN + c] = o[5];
-  }
-  HIPCHK(hipMemcpy(h->P.carf, cf.data(), cf.size() * 4, hipMemcpyHostToDevice));
-  h->bp_fresh = true; h->verdict_fresh = false;      // teleported cars: their broadphase proxies are re-created by the next contact pass
-  return MCR_OK;
-}
-
-extern "C" int mcr_get_env_state(mcr_env* h, double* reward, int32_t* tvc, uint8_t* backward, uint8_t* on_grass, double* t,
-                                 uint16_t* tile_flags, int32_t* num_tiles) {
-  if (!h) return MCR_ERR_ARG;
-  HIPCHK(sync_state(h));
-  const size_t BN = h->P.BN; const int B = h->P.B;
-  std::vector<double> r(BN); std::vector<uint32_t> cu(CU_COUNT * BN); std::vector<McrEnvState> es(B);
-  HIPCHK(hipMemcpy(r.data(), h->P.card + CD_REWARD * BN, BN * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cu.data(), h->P.caru, cu.size() * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(es.data(), h->P.env, sizeof(McrEnvState) * B, hipMemcpyDeviceToHost));
-  for (size_t c = 0; c < BN; ++c) {
-    if (reward) reward[c] = r[c];
-    if (tvc) tvc[c] = (int32_t)cu[CU_TVC * BN + c];
-    if (backward) backward[c] = cu[CU_FLAGS * BN + c] & 1;
-    if (on_grass) on_grass[c] = (cu[CU_FLAGS * BN + c] >> 1) & 1;
-  }
-  if (t) for (int e = 0; e < B; ++e) t[e] = es[e].t;
-  if (tile_flags) HIPCHK(hipMemcpy(tile_flags, h->P.tile_flags, sizeof(uint16_t) * MCR_TILE_CAP * (size_t)B, hipMemcpyDeviceToHost));
-  if (num_tiles) for (int e = 0; e < B; ++e) {
-    McrSlotHeader H;
-    HIPCHK(hipMemcpy(&H, h->P.slots + ((size_t)e * 2 + es[e].slot) * MCR_SLOT_BYTES, sizeof(H), hipMemcpyDeviceToHost));
-    num_tiles[e] = H.T;
-  }
-  return MCR_OK;
-}
-
-// ---------------------------------------------------------------------------- full state snapshot / restore
-namespace {
-struct BlobLayout { size_t carf, card, caru, es, touch, tflags, cc, viewp, carpoly, bpf, stamp, ccstamp, slot, world, particles, total; };
-BlobLayout blob_layout(int N, bool with_particles) {
-  BlobLayout L; size_t o = 16;                                         // header: magic (carries the layout version), N, flags (bit 0: particles), total bytes
-  L.carf = o; o += sizeof(float) * CF_COUNT * N;
-  o = (o + 7) & ~(size_t)7; L.card = o; o += sizeof(double) * CD_COUNT * N;
-  L.caru = o; o += sizeof(uint32_t) * CU_COUNT * N;
-  o = (o + 7) & ~(size_t)7; L.es = o; o += sizeof(McrEnvState);
-  L.touch = o; o += sizeof(uint32_t) * MCR_TILE_CAP;
-  L.tflags = o; o += sizeof(uint16_t) * MCR_TILE_CAP;
-  L.cc = o; o += sizeof(uint32_t) * (MCR_CC_MAX * MCR_CC_WORDS + 4);
-  L.viewp = o; o += sizeof(float) * MCR_VIEWP_FLOATS * N;
-  L.carpoly = o; o += sizeof(float) * MCR_CARPOLY_FLOATS * N;
-  L.bpf = o; o += sizeof(float4) * BP_COUNT * MCR_BP_FIX * N;
-  L.stamp = o; o += sizeof(uint32_t) * MCR_TILE_CAP * 4 * N;
-  L.ccstamp = o; o += sizeof(uint32_t) * mcr_cc_stamp_words(N);
-  o = (o + 15) & ~(size_t)15; L.slot = o; o += MCR_SLOT_BYTES;
-  L.world = o; o += sizeof(uint16_t) * (MCR_PID_TAB + MCR_PID_STACK) + sizeof(int32_t) * 4;      // the env's b2World (k_world.h): ids, free leaf stack, meta
-  L.particles = o; if (with_particles) o += sizeof(uint32_t) * MCR_PART_WORDS * N;
-  L.total = o;
-  return L;
-}
-const uint32_t BLOB_MAGIC = 0x3552434du;   // "MCR5": bumped whenever the layout of a blob (McrEnvState, slot image, field lists) changes
-}  // namespace
-
-extern "C" size_t mcr_state_blob_bytes(const mcr_env* h) { return h ? blob_layout(h->P.N, h->P.particles != nullptr).total : 0; }
-
-extern "C" int mcr_get_state_blob(mcr_env* h, int env, void* blob_out) {
-  if (!h || !blob_out) { g_err = "null argument"; return MCR_ERR_ARG; }
-  if (env < 0 || env >= h->P.B) { g_err = "env out of range"; return MCR_ERR_ARG; }
-  if (!h->any_reset) { g_err = "state snapshot before reset()"; return MCR_ERR_STATE; }
-  HIPCHK(sync_state(h));
-  const McrParams& P = h->P; const int N = P.N; const size_t BN = P.BN;
-  const BlobLayout L = blob_layout(N, P.particles != nullptr);
-  uint8_t* b = (uint8_t*)blob_out;
-  memset(b, 0, L.total);
-  ((uint32_t*)b)[0] = BLOB_MAGIC; ((uint32_t*)b)[1] = (uint32_t)N; ((uint32_t*)b)[2] = (P.particles ? 1u : 0u) | (P.pid_tab ? 2u : 0u); ((uint32_t*)b)[3] = (uint32_t)L.total;
-  HIPCHK(hipMemcpy2D(b + L.carf, sizeof(float) * N, P.carf + (size_t)env * N, sizeof(float) * BN, sizeof(float) * N, CF_COUNT, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy2D(b + L.card, sizeof(double) * N, P.card + (size_t)env * N, sizeof(double) * BN, sizeof(double) * N, CD_COUNT, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy2D(b + L.caru, sizeof(uint32_t) * N, P.caru + (size_t)env * N, sizeof(uint32_t) * BN, sizeof(uint32_t) * N, CU_COUNT, hipMemcpyDeviceToHost));
-  McrEnvState es;
-  HIPCHK(hipMemcpy(&es, P.env + env, sizeof(es), hipMemcpyDeviceToHost));
-  memcpy(b + L.es, &es, sizeof(es));
-  HIPCHK(hipMemcpy(b + L.touch, P.tile_touch + (size_t)env * MCR_TILE_CAP, sizeof(uint32_t) * MCR_TILE_CAP, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(b + L.tflags, P.tile_flags + (size_t)env * MCR_TILE_CAP, sizeof(uint16_t) * MCR_TILE_CAP, hipMemcpyDeviceToHost));
-  const size_t ccw = MCR_CC_MAX * MCR_CC_WORDS + 4;
-  HIPCHK(hipMemcpy(b + L.cc, P.cc_store + (size_t)env * ccw, sizeof(uint32_t) * ccw, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(b + L.viewp, P.viewp + (size_t)env * N * MCR_VIEWP_FLOATS, sizeof(float) * MCR_VIEWP_FLOATS * N, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(b + L.carpoly, P.carpoly + (size_t)env * N * MCR_CARPOLY_FLOATS, sizeof(float) * MCR_CARPOLY_FLOATS * N, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy2D(b + L.bpf, sizeof(float4) * MCR_BP_FIX * N, P.bpf + (size_t)env * MCR_BP_FIX * N, sizeof(float4) * MCR_BP_FIX * BN, sizeof(float4) * MCR_BP_FIX * N, BP_COUNT, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(b + L.ccstamp, P.cc_stamp + (size_t)env * mcr_cc_stamp_words(N), sizeof(uint32_t) * mcr_cc_stamp_words(N), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(b + L.stamp, P.bp_stamp + (size_t)env * MCR_TILE_CAP * 4 * N, sizeof(uint32_t) * MCR_TILE_CAP * 4 * N, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(b + L.slot, P.slots + ((size_t)env * 2 + es.slot) * MCR_SLOT_BYTES, MCR_SLOT_BYTES, hipMemcpyDeviceToHost));
-  if (P.particles) HIPCHK(hipMemcpy(b + L.particles, P.particles + (size_t)env * N * MCR_PART_WORDS, sizeof(uint32_t) * MCR_PART_WORDS * N, hipMemcpyDeviceToHost));
-  if (P.pid_tab) {
-    HIPCHK(hipMemcpy(b + L.world, P.pid_tab + (size_t)env * MCR_PID_TAB, sizeof(uint16_t) * MCR_PID_TAB, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(b + L.world + sizeof(uint16_t) * MCR_PID_TAB, P.pid_stack + (size_t)env * MCR_PID_STACK, sizeof(uint16_t) * MCR_PID_STACK, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(b + L.world + sizeof(uint16_t) * (MCR_PID_TAB + MCR_PID_STACK), P.pid_meta + (size_t)env * 4, sizeof(int32_t) * 4, hipMemcpyDeviceToHost));
-  }
-  return MCR_OK;
-}
-
-extern "C" int mcr_set_state_blob(mcr_env* h, int env, const void* blob) {
-  if (!h || !blob) { g_err = "null argument"; return MCR_ERR_ARG; }
-  if (env < 0 || env >= h->P.B) { g_err = "env out of range"; return MCR_ERR_ARG; }
-  const McrParams& P = h->P; const int N = P.N; const size_t BN = P.BN;
-  const uint8_t* b = (const uint8_t*)blob;
-  const BlobLayout L = blob_layout(N, P.particles != nullptr);
-  if (((const uint32_t*)b)[0] != BLOB_MAGIC || ((const uint32_t*)b)[1] != (uint32_t)N) { g_err = "not a state blob of this build and num_agents"; return MCR_ERR_ARG; }
-  if (((const uint32_t*)b)[2] != ((P.particles ? 1u : 0u) | (P.pid_tab ? 2u : 0u)) || ((const uint32_t*)b)[3] != (uint32_t)L.total) { g_err = "state blob was taken from a handle with another skid_particles or fresh_world setting"; return MCR_ERR_ARG; }
-  HIPCHK(sync_state(h));
-  HIPCHK(hipMemcpy2D(P.carf + (size_t)env * N, sizeof(float) * BN, b + L.carf, sizeof(float) * N, sizeof(float) * N, CF_COUNT, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy2D(P.card + (size_t)env * N, sizeof(double) * BN, b + L.card, sizeof(double) * N, sizeof(double) * N, CD_COUNT, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy2D(P.caru + (size_t)env * N, sizeof(uint32_t) * BN, b + L.caru, sizeof(uint32_t) * N, sizeof(uint32_t) * N, CU_COUNT, hipMemcpyHostToDevice));
-  // the staging protocol (which slot is current, whether a staged episode waits, install counter) belongs to the
-  // TARGET handle; everything else of the env record comes from the blob
-  McrEnvState cur, in;
-  HIPCHK(hipMemcpy(&cur, P.env + env, sizeof(cur), hipMemcpyDeviceToHost));
-  memcpy(&in, b + L.es, sizeof(in));
-  in.slot = cur.slot; in.staged_ready = cur.staged_ready; in.consumed = cur.consumed;
-  HIPCHK(hipMemcpy(P.env + env, &in, sizeof(in), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(P.tile_touch + (size_t)env * MCR_TILE_CAP, b + L.touch, sizeof(uint32_t) * MCR_TILE_CAP, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(P.tile_flags + (size_t)env * MCR_TILE_CAP, b + L.tflags, sizeof(uint16_t) * MCR_TILE_CAP, hipMemcpyHostToDevice));
-  const size_t ccw = MCR_CC_MAX * MCR_CC_WORDS + 4;
-  HIPCHK(hipMemcpy(P.cc_store + (size_t)env * ccw, b + L.cc, sizeof(uint32_t) * ccw, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(P.viewp + (size_t)env * N * MCR_VIEWP_FLOATS, b + L.viewp, sizeof(float) * MCR_VIEWP_FLOATS * N, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(P.carpoly + (size_t)env * N * MCR_CARPOLY_FLOATS, b + L.carpoly, sizeof(float) * MCR_CARPOLY_FLOATS * N, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy2D(P.bpf + (size_t)env * MCR_BP_FIX * N, sizeof(float4) * MCR_BP_FIX * BN, b + L.bpf, sizeof(float4) * MCR_BP_FIX * N, sizeof(float4) * MCR_BP_FIX * N, BP_COUNT, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(P.cc_stamp + (size_t)env * mcr_cc_stamp_words(N), b + L.ccstamp, sizeof(uint32_t) * mcr_cc_stamp_words(N), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(P.bp_stamp + (size_t)env * MCR_TILE_CAP * 4 * N, b + L.stamp, sizeof(uint32_t) * MCR_TILE_CAP * 4 * N, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(P.slots + ((size_t)env * 2 + cur.slot) * MCR_SLOT_BYTES, b + L.slot, MCR_SLOT_BYTES, hipMemcpyHostToDevice));
-  if (P.particles) HIPCHK(hipMemcpy(P.particles + (size_t)env * N * MCR_PART_WORDS, b + L.particles, sizeof(uint32_t) * MCR_PART_WORDS * N, hipMemcpyHostToDevice));
-  if (P.pid_tab) {
-    HIPCHK(hipMemcpy(P.pid_tab + (size_t)env * MCR_PID_TAB, b + L.world, sizeof(uint16_t) * MCR_PID_TAB, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(P.pid_stack + (size_t)env * MCR_PID_STACK, b + L.world + sizeof(uint16_t) * MCR_PID_TAB, sizeof(uint16_t) * MCR_PID_STACK, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(P.pid_meta + (size_t)env * 4, b + L.world + sizeof(uint16_t) * (MCR_PID_TAB + MCR_PID_STACK), sizeof(int32_t) * 4, hipMemcpyHostToDevice));
-  }
-  h->any_reset = true; h->verdict_fresh = false;
-  return MCR_OK;
-}
-
-// ---------------------------------------------------------------------------- batched snapshot / restore / clone on the device (k_envcopy.h)
-namespace {
-// The segment table of k_envcopy: blob_layout()'s sections, in blob order, as (device array, strides, rows) — the device format is the host
-// format by construction — with the bytes between two sections (and up to the row pitch) as EC_ZERO entries.
-int envcopy_table(const mcr_env* h, McrEnvCopy& a) {
-  const McrParams& P = h->P; const uint64_t N = (uint64_t)P.N, BN = (uint64_t)P.BN;
-  const BlobLayout L = blob_layout(P.N, P.particles != nullptr);
-  const size_t pitch = align_up(L.total, 16);
-  a.nseg = 0; a.B = P.B; a.pitch = pitch; a.env = P.env;
-  a.hdr[0] = BLOB_MAGIC; a.hdr[1] = (uint32_t)P.N; a.hdr[2] = (P.particles ? 1u : 0u) | (P.pid_tab ? 2u : 0u); a.hdr[3] = (uint32_t)L.total;
-  auto width = [](uint64_t bits) { uint64_t w = 16; while (bits & (w - 1)) w >>= 1; return (uint8_t)w; };
-  size_t cursor = 16;                                                    // the header: the kernel's own
-  bool ok = true;
-  auto push = [&](const McrEcSeg& g) { if (a.nseg < MCR_EC_MAX_SEGS) a.seg[a.nseg++] = g; else ok = false; };
-  auto zero_to = [&](size_t off) {
-    if (off > cursor) { McrEcSeg z{}; z.kind = EC_ZERO; z.rows = 1; z.row_bytes = (uint32_t)(off - cursor); z.blob_off = (uint32_t)cursor; z.w_blob = z.w_env = width(cursor | (off - cursor)); push(z); }
-    cursor = off;
-  };
-  auto add = [&](int kind, const void* base, uint64_t env_stride, uint64_t rows, uint64_t row_stride, uint64_t row_bytes, size_t off) {
-    zero_to(off);
-    McrEcSeg g{}; g.kind = (uint8_t)kind; g.base = (uint8_t*)base; g.env_stride = env_stride; g.rows = (uint32_t)rows; g.row_stride = row_stride;
-    g.row_bytes = (uint32_t)row_bytes; g.blob_off = (uint32_t)off;
-    g.w_env = width((uint64_t)(uintptr_t)base | env_stride | row_bytes | (rows > 1 ? row_stride : 0) | (kind == EC_SLOT ? (uint64_t)MCR_SLOT_BYTES : 0));
-    g.w_blob = width((uint64_t)g.w_env | off);                           // (blob rows start at multiples of 16: checked by the calls)
-    push(g); cursor = off + rows * row_bytes;
-  };
-  const uint64_t ccw = MCR_CC_MAX * MCR_CC_WORDS + 4;
-  add(EC_PLAIN, P.carf, 4 * N, CF_COUNT, 4 * BN, 4 * N, L.carf);
-  add(EC_PLAIN, P.card, 8 * N, CD_COUNT, 8 * BN, 8 * N, L.card);
-  add(EC_PLAIN, P.caru, 4 * N, CU_COUNT, 4 * BN, 4 * N, L.caru);
-  add(EC_ENVREC, P.env, sizeof(McrEnvState), 1, 0, sizeof(McrEnvState), L.es);
-  add(EC_PLAIN, P.tile_touch, 4 * MCR_TILE_CAP, 1, 0, 4 * MCR_TILE_CAP, L.touch);
-  add(EC_PLAIN, P.tile_flags, 2 * MCR_TILE_CAP, 1, 0, 2 * MCR_TILE_CAP, L.tflags);
-  add(EC_PLAIN, P.cc_store, 4 * ccw, 1, 0, 4 * ccw, L.cc);
-  add(EC_PLAIN, P.viewp, 4 * MCR_VIEWP_FLOATS * N, 1, 0, 4 * MCR_VIEWP_FLOATS * N, L.viewp);
-  add(EC_PLAIN, P.carpoly, 4 * MCR_CARPOLY_FLOATS * N, 1, 0, 4 * MCR_CARPOLY_FLOATS * N, L.carpoly);
-  add(EC_PLAIN, P.bpf, sizeof(float4) * MCR_BP_FIX * N, BP_COUNT, sizeof(float4) * MCR_BP_FIX * BN, sizeof(float4) * MCR_BP_FIX * N, L.bpf);
-  add(EC_PLAIN, P.bp_stamp, 4 * (uint64_t)MCR_TILE_CAP * 4 * N, 1, 0, 4 * (uint64_t)MCR_TILE_CAP * 4 * N, L.stamp);
-  add(EC_PLAIN, P.cc_stamp, 4 * mcr_cc_stamp_words(P.N), 1, 0, 4 * mcr_cc_stamp_words(P.N), L.ccstamp);
-  add(EC_SLOT, P.slots, 2 * (uint64_t)MCR_SLOT_BYTES, 1, 0, MCR_SLOT_BYTES, L.slot);
-  if (P.pid_tab) {
-    add(EC_PLAIN, P.pid_tab, 2 * MCR_PID_TAB, 1, 0, 2 * MCR_PID_TAB, L.world);
-    add(EC_PLAIN, P.pid_stack, 2 * MCR_PID_STACK, 1, 0, 2 * MCR_PID_STACK, L.world + 2 * MCR_PID_TAB);
-    add(EC_PLAIN, P.pid_meta, 16, 1, 0, 16, L.world + 2 * (MCR_PID_TAB + MCR_PID_STACK));
-  }
-  if (P.particles) add(EC_PLAIN, P.particles, 4 * (uint64_t)MCR_PART_WORDS * N, 1, 0, 4 * (uint64_t)MCR_PART_WORDS * N, L.particles);
-  zero_to(pitch);
-  if (!ok) { g_err = "state copy: the segment table is full (MCR_EC_MAX_SEGS)"; return MCR_ERR_STATE; }
-  return MCR_OK;
-}
-// what the three calls share: arguments, the capture rule, the pending flag scans in front (they read and write what the copy reads and writes)
-int envcopy_begin(mcr_env* h, int n, hipStream_t st, const char* who) {
-  if (n < 0 || n > h->P.B) { g_err = std::string(who) + ": n must be 0 .. num_envs"; return MCR_ERR_ARG; }
-  if (capturing(st)) { g_err = std::string(who) + " inside a stream capture (the handle's host bookkeeping would not be replayed)"; return MCR_ERR_STATE; }
-  return MCR_OK;
-}
-// restore / clone: mcr_set_state_blob's host bookkeeping (the next step re-evaluates the touch verdicts and the contact list) and the state vector
-void envcopy_wrote(mcr_env* h, hipStream_t st) {
-  h->any_reset = true; h->verdict_fresh = false;
-  launch_state_obs(h, st);
-}
-}  // namespace
-
-extern "C" size_t mcr_state_blob_pitch(const mcr_env* h) { return h ? align_up(mcr_state_blob_bytes(h), 16) : 0; }
-extern "C" int mcr_state_blob_header(const mcr_env* h, uint32_t* out4) {
-  if (!h || !out4) { g_err = "null argument"; return MCR_ERR_ARG; }
-  out4[0] = BLOB_MAGIC; out4[1] = (uint32_t)h->P.N; out4[2] = (h->P.particles ? 1u : 0u) | (h->P.pid_tab ? 2u : 0u); out4[3] = (uint32_t)mcr_state_blob_bytes(h);
-  return MCR_OK;
-}
-
-extern "C" int mcr_save_states(mcr_env* h, const int32_t* d_env_ids, int n, void* d_blobs, void* stream) {
-  if (!h || !d_blobs) { g_err = "mcr_save_states: null argument"; return MCR_ERR_ARG; }
-  if (((uintptr_t)d_blobs & 15) != 0) { g_err = "mcr_save_states: d_blobs must be 16-byte aligned"; return MCR_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = envcopy_begin(h, n, st, "mcr_save_states")) return rc;
-  if (!h->any_reset) { g_err = "mcr_save_states before reset()"; return MCR_ERR_STATE; }
-  if (n == 0) return MCR_OK;
-  McrEnvCopy a{};
-  if (int rc = envcopy_table(h, a)) return rc;
-  a.ids = d_env_ids; a.src_ids = nullptr; a.blobs = (uint8_t*)d_blobs; a.refused = nullptr;
-  flush_flags(h, st);
-  hipLaunchKernelGGL(k_envcopy<ENV_TO_BLOB>, dim3(n), dim3(MCR_EC_LANES), 0, st, a);
-  HIPCHK(hipGetLastError());
-  return MCR_OK;
-}
-
-extern "C" int mcr_load_states(mcr_env* h, const int32_t* d_env_ids, int n, const void* d_blobs, int32_t* d_refused, void* stream) {
-  if (!h || !d_blobs) { g_err = "mcr_load_states: null argument"; return MCR_ERR_ARG; }
-  if (((uintptr_t)d_blobs & 15) != 0) { g_err = "mcr_load_states: d_blobs must be 16-byte aligned"; return MCR_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = envcopy_begin(h, n, st, "mcr_load_states")) return rc;
-  if (n == 0) return MCR_OK;
-  McrEnvCopy a{};
-  if (int rc = envcopy_table(h, a)) return rc;
-  a.ids = d_env_ids; a.src_ids = nullptr; a.blobs = (uint8_t*)d_blobs; a.refused = d_refused;
-  flush_flags(h, st);
-  hipLaunchKernelGGL(k_envcopy<BLOB_TO_ENV>, dim3(n), dim3(MCR_EC_LANES), 0, st, a);
-  envcopy_wrote(h, st);
-  HIPCHK(hipGetLastError());
-  return MCR_OK;
-}
-
-extern "C" int mcr_copy_states(mcr_env* h, const int32_t* d_src_ids, const int32_t* d_dst_ids, int n, void* stream) {
-  if (!h || !d_src_ids || !d_dst_ids) { g_err = "mcr_copy_states: null argument"; return MCR_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = envcopy_begin(h, n, st, "mcr_copy_states")) return rc;
-  if (!h->any_reset) { g_err = "mcr_copy_states before reset()"; return MCR_ERR_STATE; }
-  if (n == 0) return MCR_OK;
-  McrEnvCopy a{};
-  if (int rc = envcopy_table(h, a)) return rc;
-  a.ids = d_dst_ids; a.src_ids = d_src_ids; a.blobs = nullptr; a.refused = nullptr;
-  flush_flags(h, st);
-  hipLaunchKernelGGL(k_envcopy<ENV_TO_ENV>, dim3(n), dim3(MCR_EC_LANES), 0, st, a);
-  envcopy_wrote(h, st);
-  HIPCHK(hipGetLastError());
-  return MCR_OK;
-}
-
-__global__ void k_positions(McrParams p, float* out) {
-  const int ci = blockIdx.x * blockDim.x + threadIdx.x;
-  if (ci >= p.BN) return;
-  const McrShapes& S = *p.shapes;
-  Xf xf = xf_of(v2(p.carf[CF_CX * p.BN + ci], p.carf[CF_CY * p.BN + ci]), p.carf[CF_A * p.BN + ci], v2(S.hull_lcx, S.hull_lcy));
-  out[ci * 2] = xf.p.x; out[ci * 2 + 1] = xf.p.y;
-}
-extern "C" int mcr_get_positions(mcr_env* h, float* pos) {
-  if (!h || !pos) return MCR_ERR_ARG;
-  float* d = nullptr;
-  HIPCHK(hipMalloc(&d, sizeof(float) * 2 * h->P.BN));
-  hipLaunchKernelGGL(k_positions, dim3((h->P.BN + 63) / 64), dim3(64), 0, 0, h->P, d);
-  HIPCHK(hipMemcpy(pos, d, sizeof(float) * 2 * h->P.BN, hipMemcpyDeviceToHost));
-  (void)hipFree(d);
-  return MCR_OK;
-}
 
 __global__ void k_sincos(const float* in, float* s, float* c, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

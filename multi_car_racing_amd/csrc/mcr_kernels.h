@@ -176,6 +176,12 @@ struct McrObsRing {
   int32_t j;                    // ring head of the launch, 0 .. k - 1
 };
 
+// The state-vector observation (k_stateobs.h): launch argument of k_stateobs beside McrParams, kept in the handle (null `out`: the feature is off and nothing is launched)
+struct McrStateObs {
+  float* out;                   // [B][N][F] the caller's device buffer
+  int32_t K, stride, F;         // waypoints, tiles between them, features per car
+};
+
 // status words (mapped host memory).  FATAL ones (give-up, verdict) make the next mcr_step return MCR_ERR_STATE; an OVERFLOW truncated a
 // capacity-bound list (documented deviation): the step goes on, mcr_status shows the count
 enum { ST_SPIN_GIVEUP = 0,     // a kernel gave up waiting for another stream's kernels (three-chain step: the contact pass of an env, a phase word)

@@ -1,6 +1,9 @@
 """MI355X: batched device-side snapshot / restore / clone of env states (VecMultiCarRacing.save_states / load_states / clone_envs over
 csrc/k_envcopy.h) against the per-env host path it batches (get_state_blob / set_state_blob), the oracle, and itself."""
 import ctypes
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -47,11 +50,8 @@ CASES = {
 }
 
 
-@pytest.mark.parametrize("case", list(CASES))
-def test_save_states_is_byte_identical_with_the_host_snapshot(torch_cuda, case):
-    """Row e of save_states() — taken FIRST after the steps, so a pending flag scan has to be flushed by the call itself — holds exactly
-    get_state_blob(e), header included, zeros up to the pitch; also for a permuted id list that holds env B-1, for one id, and into `out`."""
-    torch = torch_cuda
+def scripted_rollout(torch, case):
+    """the env of CASES[case] after its scripted steps, nothing synchronous behind the last one (tools/make_state_blob_golden.py runs the same)"""
     c = CASES[case]; N, B = c["N"], c["B"]
     env = _make(B, N, 70 + N, contacts=True, **c["kw"]); env.reset()
     if c.get("rear"):
@@ -59,6 +59,15 @@ def test_save_states_is_byte_identical_with_the_host_snapshot(torch_cuda, case):
     rng = np.random.RandomState(5)
     for k in range(c["steps"]):
         env.step(torch.from_numpy(_crash_actions(rng, B, N, k) if c.get("rear") else random_actions(rng, B, N, 0.2)).cuda())
+    return env
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_save_states_is_byte_identical_with_the_host_snapshot(torch_cuda, case):
+    """Row e of save_states() — taken FIRST after the steps, so a pending flag scan has to be flushed by the call itself — holds exactly
+    get_state_blob(e), header included, zeros up to the pitch; also for a permuted id list that holds env B-1, for one id, and into `out`."""
+    torch = torch_cuda
+    c = CASES[case]; N, B = c["N"], c["B"]
+    env = scripted_rollout(torch, case)
     dev = env.save_states()
     some = [B - 1, 0, 2]
     dev_some = env.save_states(some)
@@ -79,6 +88,27 @@ def test_save_states_is_byte_identical_with_the_host_snapshot(torch_cuda, case):
     for i, e in enumerate(some):
         assert np.array_equal(got_some[i, :nbytes], host[e]), f"id list row {i} (env {e})"
     assert np.array_equal(got1[0, :nbytes], host[B - 2]) and not got1[0, nbytes:].any()
+    env.close()
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_blobs_reproduce_the_recorded_format(torch_cuda, case):
+    """tests/golden/state_blob_format.json (tools/make_state_blob_golden.py, recorded before the section table replaced the four hand-written
+    layouts): after the case's scripted rollout the blob size, the header words and the SHA-256 of every env's blob are the recorded ones,
+    from get_state_blob (the host walk over the table) and from the first blob_bytes of each save_states() row (the kernel's segment table)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "state_blob_format.json")) as f:
+        want = json.load(f)[case]
+    env = scripted_rollout(torch_cuda, case)
+    rows = env.save_states().cpu().numpy()
+    nbytes = int(env.L.mcr_state_blob_bytes(env.h))
+    hdr = np.zeros(4, np.uint32)
+    assert env.L.mcr_state_blob_header(env.h, hdr.ctypes.data) == MCR_OK
+    assert nbytes == want["blob_bytes"] and hdr.tolist() == want["header"] and len(want["sha256"]) == env.B
+    for e in range(env.B):
+        host = env.get_state_blob(e)
+        assert host[:16].view(np.uint32).tolist() == want["header"]
+        assert hashlib.sha256(host.tobytes()).hexdigest() == want["sha256"][e], f"env {e}: get_state_blob"
+        assert hashlib.sha256(rows[e, :nbytes].tobytes()).hexdigest() == want["sha256"][e], f"env {e}: save_states"
     env.close()
 
 
