@@ -700,6 +700,50 @@ def test_random_rollout_with_contacts_enabled(torch_cuda, oracle, streams):
     env.close()
 
 
+def _out_of_range_actions(rng, B, N):
+    """per car and per step, each component either in range or from a fixed set beyond the action space"""
+    a = random_actions(rng, B, N, 0.3)
+    for j, vals in enumerate(([-10, -3, -1.5, 1.5, 3, 10], [-1, -0.05, 1.2, 5], [-0.5, 0.89999, 0.9, 1.5, 4])):
+        pick = rng.choice(np.array(vals, np.float32), (B, N))
+        a[..., j] = np.where(rng.uniform(size=(B, N)) < (0.25 if j == 2 else 0.5), pick, a[..., j])
+    return a
+
+
+@pytest.mark.parametrize("N,contacts", [(1, False), (2, False), (2, True)])
+def test_actions_outside_the_action_space_match_oracle(torch_cuda, oracle, N, contacts):
+    """The Python layer hands actions through untouched, and a policy with an unbounded head sends values outside the Box: the reference
+    clips gas to [0, 1] (Car.gas) and neither steering (the wheel joints' motor runs into their +-0.4 rad limits) nor brake (>= 0.9 locks the
+    wheels, a negative one accelerates them) — k_dynamics.h's controls restate that.  Steering in +-{1.5, 3, 10}, gas in {-1, -0.05, 1.2, 5},
+    brake in {-0.5, 0.89999, 0.9, 1.5, 4}, mixed per car and per step with values in range; 120 steps with the cars as ghosts, and once with car 1
+    rear-ending car 0.  Rewards and done every step, the full state every 20 steps.  NaN actions are out of scope: what the reference does with
+    them is an accident of np.clip and np.sign, not a behaviour to restate."""
+    torch = torch_cuda
+    B, seed = 5, 500 + 2 * N + int(contacts)
+    env = _make(B, N, seed, contacts=contacts); env.reset()
+    orcs = _oracles(oracle, B, N, seed, contacts=contacts)
+    if contacts:
+        _rear_end_setup(env, orcs)
+    rng = np.random.RandomState(seed)
+    touched = 0; beyond = np.zeros(3, int)
+    for k in range(120):
+        a = _out_of_range_actions(rng, B, N)
+        if contacts:
+            a[:, 1, 1] = rng.choice(np.array([1.2, 5], np.float32), B); a[:, 1, 0] *= np.float32(0.02); a[:, 1, 2] = -0.5 if k % 7 == 0 else 0.0
+            a[:, 0, 1] = rng.choice(np.array([-1, -0.05], np.float32), B)
+        beyond += [(np.abs(a[..., 0]) > 1).sum(), ((a[..., 1] < 0) | (a[..., 1] > 1)).sum(), ((a[..., 2] < 0) | (a[..., 2] > 1)).sum()]
+        _, rew, done, _ = env.step(torch.from_numpy(a).cuda())
+        rw, dn = rew.cpu().numpy(), done.cpu().numpy()
+        for e, o in enumerate(orcs):
+            _, r, d, _ = o.step(a[e], render=False)
+            touched += o.num_car_contacts()
+            assert np.array_equal(r, rw[e]) and bool(dn[e]) == d, f"step {k} env {e}: reward/done differ (actions {a[e].tolist()})"
+        if k % 20 == 19:
+            _assert_state_equal(env, orcs, f"out-of-range actions, step {k}")
+    assert (beyond > 50).all(), beyond
+    assert not contacts or touched > 50, "the contact run produced no car<->car contacts"
+    env.close()
+
+
 def test_side_by_side_cars_take_shared_tiles_in_box2d_order(torch_cuda, oracle):
     """Two cars of a start row share their tiles; driven alike they keep reaching new tiles in the SAME step, and who is served
     first (Box2D: the contact of the later FindNewContacts batch, then the higher proxy id = the car created last) decides who
