@@ -117,6 +117,25 @@ int mcr_world_proxy_ids(const mcr_world* w, int32_t* out, int cap);
 /* Copy n host blobs into the STAGED slot of envs env_ids[0..n) (async on stream; blobs must stay valid
  * until the stream reaches this point — use pinned memory for real overlap). */
 int mcr_stage_episodes(mcr_env* h, const int32_t* env_ids, int n, const void* blobs, void* stream);
+/* Level pools: a finite set of K tracks that the DEVICE re-stages by itself (procgen's num_levels: train on K tracks, evaluate on others;
+ * fixed-track evaluation; per-track statistics) — and no host work per step.  d_pool is the caller's device memory [K][mcr_episode_bytes()],
+ * 16-byte aligned, holding K episode blobs exactly as mcr_episodes_generate writes them; it must outlive the handle's use of it.  From then on
+ * a kernel of the handle (csrc/k_pool.h) does what mcr_stage_episodes does for the host: in front of and behind every mcr_reset and behind
+ * every mcr_step / mcr_step_repeat, on the caller's stream, every env that installed its staged episode gets its next one copied from the
+ * pool into its staged slot.  Env e plays pool row mcr_pool_level(seed, env_offset + e, k, K, mode) in its k-th episode (k = 0: the first;
+ * k counts the episodes the env has installed, by reset or auto-reset):
+ *   mode 0 "random"  mcr_mix64(mcr_mix64(seed + 0x9e3779b97f4a7c15 * ((k << 32) | global env))) % K   (splitmix64's finaliser, csrc/mcr_common.h)
+ *   mode 1 "cycle"   (global env + k) % K
+ * — a pure function: results do not depend on the batch size, on the sharding (env_offset) or on scheduling.  mcr_pool_level is that
+ * function on the host (no handle, no GPU; MCR_ERR_ARG for K < 1 or a bad mode).  d_level, [num_envs] int32 on the device or NULL, receives
+ * the pool row of each env's CURRENT episode (written when the env installs it; valid once that reset / step is complete on its stream).
+ * With a pool an env never finds its staged slot empty at a step's begin: mcr_status word 4 and mcr_debug_read_counters [3] stay 0.
+ * MCR_ERR_ARG: NULL handle or pool, K < 1, a misaligned pool, a bad mode.  MCR_ERR_STATE: after the first mcr_reset (the pool is chosen for
+ * the life of the handle: the staged slots have ONE owner), or with the refill service running.  While a pool is set mcr_stage_episodes,
+ * mcr_refill_start and mcr_poll_consumed return MCR_ERR_STATE.  mcr_load_states / mcr_copy_states / mcr_set_state_blob keep their rule: the
+ * staging words of the target's record and its staged slot are not touched, so a restored env goes on with the TARGET's next level. */
+int32_t mcr_pool_level(uint64_t seed, uint32_t global_env, uint32_t episode, int32_t K, int mode);
+int mcr_set_episode_pool(mcr_env* h, const void* d_pool, int K, uint64_t seed, uint32_t env_offset, int mode, int32_t* d_level);
 /* reset() (:340-408): installs the staged episode for every env whose d_env_mask byte != 0 (NULL = all),
  * spawns the cars, runs the no-action step of :408 and writes the first observation.
  * d_obs: [B,N,96,96,3] u8 or NULL; with mcr_set_obs_format the layout that call describes. */

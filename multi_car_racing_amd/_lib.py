@@ -11,6 +11,7 @@ QUAD_CAP = 768
 MT_WORDS = 625
 OBS_RGB, OBS_GRAY, OBS_STACK_MAX = 0, 1, 8
 REPEAT_MAX = 16                 # include/mcr.h: MCR_REPEAT_MAX
+LEVEL_ORDER = {"random": 0, "cycle": 1}      # include/mcr.h: mcr_set_episode_pool's mode
 
 # mcr_debug_set bits: the mirror of enum McrDebugBit (csrc/mcr_kernels.h, which says what each one does; tests/test_abi.py compares the two)
 DEBUG_VIEW_CLOCKS = 1 << 5
@@ -59,6 +60,8 @@ SYMBOLS = {
     "mcr_episodes_generate_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i]),
     "mcr_episode_unpack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcr_stage_episodes": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "mcr_pool_level": (ctypes.c_int32, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _i]),
+    "mcr_set_episode_pool": (_i, [_vp, _vp, _i, ctypes.c_uint64, ctypes.c_uint32, _i, _vp]),
     "mcr_reset": (_i, [_vp, _vp, _vp, _vp]),
     "mcr_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcr_step_repeat": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -170,6 +170,14 @@ MCR_HD uint64_t mcr_mix64(uint64_t x) {
   x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull; x ^= x >> 27; x *= 0x94d049bb133111ebull; x ^= x >> 31;
   return x;
 }
+// Level pools (include/mcr.h: mcr_set_episode_pool): the pool row that global env g plays in its k-th episode (k = 0: the first), K >= 1
+// rows.  mode 0 "random": the same counter-based hash as the action stream, keyed by (seed, k, g); mode 1 "cycle": (g + k) mod K.  One
+// function for the kernel (k_pool.h) and the host (mcr_pool_level).
+MCR_HD int32_t mcr_pool_level_of(uint64_t seed, uint32_t g, uint32_t k, int32_t K, int mode) {
+  if (mode == 1) return (int32_t)(((uint64_t)g + (uint64_t)k) % (uint64_t)K);
+  const uint64_t ctr = ((uint64_t)k << 32) | (uint64_t)g;
+  return (int32_t)(mcr_mix64(mcr_mix64(seed + 0x9e3779b97f4a7c15ull * ctr)) % (uint64_t)K);
+}
 MCR_HD float mcr_synth_uniform(uint64_t seed, uint32_t g, uint32_t agent, uint32_t t, uint32_t comp) {
   const uint64_t ctr = ((uint64_t)t << 32) | ((uint64_t)g * 8u + agent);
   const uint64_t x = mcr_mix64(mcr_mix64(seed + 0x9e3779b97f4a7c15ull * ctr) + comp);

@@ -9,6 +9,7 @@
 #include "k_list_chain.h"
 #include "k_render.h"
 #include "k_stateobs.h"
+#include "k_pool.h"
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <string>
@@ -237,6 +238,7 @@ extern "C" int mcr_destroy(mcr_env* h) {
 
 extern "C" int mcr_stage_episodes(mcr_env* h, const int32_t* env_ids, int n, const void* blobs, void* stream) {
   if (!h || !blobs || n < 0) { g_err = "bad argument"; return MCR_ERR_ARG; }
+  if (h->pool.blobs) { g_err = "mcr_stage_episodes: the handle stages its episodes from a level pool (mcr_set_episode_pool)"; return MCR_ERR_STATE; }
   hipStream_t st = (hipStream_t)stream;
   const int B = h->cfg.num_envs;
   // The staged slot of env e is ((installs & 1) ^ 1): slot 0 is "current" before the first install and every
@@ -342,6 +344,19 @@ static void launch_reset(mcr_env* h, McrParams P, hipStream_t st) {
 void launch_state_obs(mcr_env* h, hipStream_t st) {
   if (!h->so.out) return;
   hipLaunchKernelGGL(k_stateobs, dim3(h->P.B), dim3(64), 0, st, h->P, h->so);
+}
+
+// Level pools (k_pool.h): every env that installed its staged episode gets its next one from the pool.  Launched where launch_state_obs goes — on
+// the caller's stream in front of and behind launch_reset and behind the LAST sub-step of a macro-step (a parked env re-spawns only there), whose
+// tail makes `st` wait for the whole step, outside the step's streams and outside a replayed step graph.  Behind the step's tail the terminal
+// frames (mcr_set_terminal_obs), which read the slot an env just left — the slot this kernel overwrites —, are drawn.  No flush_flags: the
+// scans a phase-word step left pending (k_flags.h) read an env's record and its CURRENT slot, and return at once for an env that just
+// re-spawned; the kernel writes staged slots and `staged_ready`, which the scans load with the record and never look at — and they are
+// launched by the NEXT step, behind this kernel in stream order (W_BEGIN is posted by that step's dynamics on `st`).
+static void launch_pool_restage(mcr_env* h, hipStream_t st, int envs_per_group) {
+  if (!h->pool.blobs) return;
+  const int B = h->P.B;
+  hipLaunchKernelGGL(k_pool_restage, dim3((B + envs_per_group - 1) / envs_per_group), dim3(MCR_POOL_LANES), 0, st, h->P.env, h->P.slots, B, h->pool, envs_per_group);
 }
 
 // may a step launched on caller stream `st` order its streams with phase words?  (mcr_bind_stream checked it; an unbound stream: events)
@@ -684,7 +699,9 @@ extern "C" int mcr_reset(mcr_env* h, const uint8_t* d_env_mask, uint8_t* d_obs, 
   P.reset_mask = d_env_mask; P.obs = h->cfg.obs_enabled ? d_obs : nullptr; P.actions = nullptr;
   h->ring.j = (int)((h->obs_draws + (uint64_t)h->ring.k - 1u) % (uint64_t)h->ring.k);     // the head of the last drawing step: the window stays put
   flush_flags(h, st);
+  launch_pool_restage(h, st, 1);          // the first reset finds every env staged (a later one: nothing to do) ...
   launch_reset(h, P, st);
+  launch_pool_restage(h, st, 1);          // ... and every env that installed gets its next episode: up to B copies, one workgroup per env
   launch_state_obs(h, st);
   HIPCHK(hipGetLastError());
   h->any_reset = true; h->verdict_fresh = false;
@@ -735,6 +752,7 @@ static int step_one(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* 
       h->step_parity ^= 1;                              // what launch_step does on the host side
       HIPCHK(hipGraphLaunch(G.exec, st));
       launch_state_obs(h, st);
+      launch_pool_restage(h, st, MCR_POOL_GROUP);
       HIPCHK(hipGetLastError());
       return MCR_OK;
     }
@@ -747,6 +765,7 @@ static int step_one(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* 
         G.graph = graph; G.P = P; G.st = st; G.view_flags = vf; G.valid = true;
         HIPCHK(hipGraphLaunch(G.exec, st));
         launch_state_obs(h, st);
+        launch_pool_restage(h, st, MCR_POOL_GROUP);
         HIPCHK(hipGetLastError());
         return MCR_OK;
       }
@@ -757,7 +776,7 @@ static int step_one(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* 
     h->step_parity = parity_before;
   }
   launch_step(h, P, st, vf);
-  if (last) launch_state_obs(h, st);
+  if (last) { launch_state_obs(h, st); launch_pool_restage(h, st, MCR_POOL_GROUP); }
   HIPCHK(hipGetLastError());
   return MCR_OK;
 }
@@ -941,8 +960,19 @@ extern "C" int mcr_set_episode_stats(mcr_env* h, double* d_ep_return, int32_t* d
   return MCR_OK;
 }
 
+extern "C" int mcr_set_episode_pool(mcr_env* h, const void* d_pool, int K, uint64_t seed, uint32_t env_offset, int mode, int32_t* d_level) {
+  if (!h || !d_pool) { g_err = "mcr_set_episode_pool: null argument"; return MCR_ERR_ARG; }
+  if (K < 1 || ((uintptr_t)d_pool & 15u) || (mode != 0 && mode != 1)) { g_err = "mcr_set_episode_pool: K >= 1 rows, a 16-byte aligned pool, mode 0 (random) or 1 (cycle)"; return MCR_ERR_ARG; }
+  // (the staged slots have ONE owner for the life of the handle: a pool set later would meet episodes the host staged and counters it polls)
+  if (h->any_reset) { g_err = "mcr_set_episode_pool after the first mcr_reset"; return MCR_ERR_STATE; }
+  if (h->svc) { g_err = "mcr_set_episode_pool: the refill service is running"; return MCR_ERR_STATE; }
+  h->pool.blobs = (const uint8_t*)d_pool; h->pool.K = K; h->pool.mode = mode; h->pool.seed = seed; h->pool.env_offset = env_offset; h->pool.level = d_level;
+  return MCR_OK;
+}
+
 extern "C" int mcr_poll_consumed(mcr_env* h, int32_t* env_ids_out, int cap, void* stream) {
   if (!h) return MCR_ERR_ARG;
+  if (h->pool.blobs) { g_err = "mcr_poll_consumed: the handle stages its episodes from a level pool (mcr_set_episode_pool)"; return MCR_ERR_STATE; }
   if (h->svc) { g_err = "mcr_poll_consumed: the handle's refill service owns the counters (mcr_refill_start)"; return MCR_ERR_STATE; }
   (void)stream;   // counters live in mapped host memory: no device synchronisation needed
   int n = 0;
@@ -1073,6 +1103,7 @@ static void refill_main(mcr_env* h, RefillSvc* s) {
 extern "C" int mcr_refill_start(mcr_env* h, uint32_t* mt_track, uint32_t* mt_draw, int direction_mode, int gen_threads, void* blobs_pinned, int32_t* episode_info) {
   if (!h || !mt_track || !mt_draw || !blobs_pinned) { g_err = "mcr_refill_start: null argument"; return MCR_ERR_ARG; }
   if (h->svc) { g_err = "mcr_refill_start: already running"; return MCR_ERR_STATE; }
+  if (h->pool.blobs) { g_err = "mcr_refill_start: the handle stages its episodes from a level pool (mcr_set_episode_pool)"; return MCR_ERR_STATE; }
   HIPCHK(hipSetDevice(h->cfg.device));
   RefillSvc* s = new RefillSvc();
   s->mt_track = mt_track; s->mt_draw = mt_draw; s->direction_mode = direction_mode; s->gen_threads = std::max(1, gen_threads);

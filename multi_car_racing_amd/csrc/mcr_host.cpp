@@ -593,6 +593,12 @@ extern "C" int mcr_episode_unpack(const void* blob_in, int32_t* T, int32_t* P, i
   return MCR_OK;
 }
 
+// the level function of a pool handle (mcr_common.h: mcr_pool_level_of, which the kernel calls too)
+extern "C" int32_t mcr_pool_level(uint64_t seed, uint32_t global_env, uint32_t episode, int32_t K, int mode) {
+  if (K < 1 || (mode != 0 && mode != 1)) return MCR_ERR_ARG;
+  return mcr_pool_level_of(seed, global_env, episode, K, mode);
+}
+
 // host twin of mcr_synth_actions (same counter-based stream; the CPU baseline and the tests consume it)
 extern "C" void mcr_synth_actions_host(float* out, int num_envs, int num_agents, uint64_t seed, uint32_t t, uint32_t env_offset) {
   for (int e = 0; e < num_envs; ++e)

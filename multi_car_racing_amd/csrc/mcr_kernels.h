@@ -182,6 +182,16 @@ struct McrStateObs {
   int32_t K, stride, F;         // waypoints, tiles between them, features per car
 };
 
+// A level pool (include/mcr.h: mcr_set_episode_pool; k_pool.h): launch argument of k_pool_restage, kept in the handle (null `blobs`: no pool —
+// the host stages the episodes — and nothing is launched)
+struct McrPool {
+  const uint8_t* blobs;         // [K][MCR_SLOT_BYTES] the caller's device memory, 16-byte aligned
+  int32_t K, mode;              // rows; 0 random, 1 cycle (mcr_common.h: mcr_pool_level_of)
+  uint64_t seed;
+  uint32_t env_offset;          // global index of env 0
+  int32_t* level;               // [B] the pool row of each env's current episode, or null
+};
+
 // status words (mapped host memory).  FATAL ones (give-up, verdict) make the next mcr_step return MCR_ERR_STATE; an OVERFLOW truncated a
 // capacity-bound list (documented deviation): the step goes on, mcr_status shows the count
 enum { ST_SPIN_GIVEUP = 0,     // a kernel gave up waiting for another stream's kernels (three-chain step: the contact pass of an env, a phase word)

@@ -54,6 +54,19 @@ load_states(check=True) is asked to validate on the host.  The blob rows are byt
 protocol stays the target's: an env restored or cloned on an `auto_reset=True` handle continues with that handle's own next staged episode
 when its episode ends (set_state_blob's rule) — planning handles are normally created with `auto_reset=False`.  Observations are not part
 of the state: clone_envs copies the rows of `obs`, load_states leaves them to the next step (and refuses `frame_stack > 1`).
+
+Level pools: by default every episode of every env is a brand-new random track, generated by host threads and copied over PCIe while the
+rollout runs.  `levels=K` plays a FINITE set of K tracks instead (procgen's `num_levels`: train on K levels, evaluate on held-out ones;
+fixed-track evaluation; per-track return statistics): the K episodes are generated once, by the same bit-exact generator
+(multi_car_racing_amd/levels.py: level j is the first episode of global env j under `level_seed`, default `seed`), uploaded once, and from
+then on a kernel re-stages every env that re-spawned from the resident pool (csrc/k_pool.h; include/mcr.h: mcr_set_episode_pool) — no
+refill service, no worker thread, no host work per step, and an env can never freeze waiting for a track (`gen_threads`, `async_refill`
+and `refill_lag` are ignored).  `levels` may also be a uint8 array [K, episode_bytes] of the caller's own blobs.  Env with global index g
+plays level levels.pool_level(seed, g, k, K, level_order) in its k-th episode — `level_order="random"` a counter-based hash, `"cycle"`
+(g + k) % K — so rollouts do not depend on B, sharding or scheduling.  `self.level` (int32 device tensor [B], also info["level"]) is the
+pool row of each env's CURRENT episode; `self.level_info` the [K, 12] info rows (T, P, retries, cw, car order) of a generated pool, None
+for caller blobs.  Snapshots: clone_envs copies the `level` rows; load_states sets them to -1 (a state blob does not say which level it
+came from); either way the env goes on with its OWN next level when the restored episode ends (the staging words stay the target's).
 """
 import atexit
 import collections
@@ -94,12 +107,21 @@ class VecMultiCarRacing:
                  obs=True, auto_reset=True, max_episode_steps=1000, car_contacts=True,
                  gen_threads=None, async_refill=True, streams=None, refill_lag=64, world_size=1, graph=None,
                  skid_particles=False, terminal_obs=False, terminal_cap=None, fresh_world=False, obs_format="rgb", frame_stack=1,
-                 state_obs=False, state_waypoints=6, state_stride=5, frame_skip=1):
+                 state_obs=False, state_waypoints=6, state_stride=5, frame_skip=1, levels=None, level_seed=None, level_order="random"):
         frame_skip = int(frame_skip)
         if not 1 <= frame_skip <= _lib.REPEAT_MAX:
             raise ValueError(f"frame_skip must be 1..{_lib.REPEAT_MAX}, got {frame_skip}")
         if frame_skip > 1 and terminal_obs:
             raise ValueError("frame_skip > 1 cannot be combined with terminal_obs=True (the terminal frame would belong to an env step that draws nothing)")
+        if levels is not None:            # (checked before anything is created)
+            if level_order not in _lib.LEVEL_ORDER:
+                raise ValueError(f"level_order must be one of {sorted(_lib.LEVEL_ORDER)}, got {level_order!r}")
+            if isinstance(levels, (int, np.integer)) and not isinstance(levels, bool):
+                if int(levels) < 1:
+                    raise ValueError(f"levels must be at least 1, got {levels}")
+            elif (not isinstance(levels, np.ndarray) or levels.dtype != np.uint8 or levels.ndim != 2 or levels.shape[0] < 1
+                  or levels.shape[1] != _lib.episode_bytes()):
+                raise ValueError(f"levels must be an int K >= 1 or a uint8 array [K, {_lib.episode_bytes()}] of episode blobs")
         if not torch.cuda.is_available():
             raise _lib.McrError("VecMultiCarRacing needs a HIP device: the step path has no CPU fallback")
         self.L = _lib.load()
@@ -211,8 +233,9 @@ class VecMultiCarRacing:
             self.L.mcr_mt_seed(_lib.ptr(self.mt_track[e]), ctypes.c_uint32(g))
             self.L.mcr_mt_seed(_lib.ptr(self.mt_draw[e]), ctypes.c_uint32((g + 2 ** 31) % 2 ** 32))
         self.slot_bytes = _lib.episode_bytes()
-        self._blobs = torch.empty((self.B, self.slot_bytes), dtype=torch.uint8, pin_memory=True)
-        self._blobs_np = self._blobs.numpy()
+        # the staging source of the host path, [B, 96 KB] page-locked — not with a level pool, which stages from device memory
+        self._blobs = torch.empty((self.B, self.slot_bytes), dtype=torch.uint8, pin_memory=True) if levels is None else None
+        self._blobs_np = self._blobs.numpy() if levels is None else None
         self._refill_pin = None       # pinned bounce buffer of the refill thread (grown on demand)
         self.episode_info = np.zeros((self.B, 12), np.int32)      # T, P, retries, cw, car_order[8] of the newest generated episode
         self._ids = np.zeros(self.B, np.int32)
@@ -229,7 +252,32 @@ class VecMultiCarRacing:
         self._worker = None
         self._closed = False
         self._has_reset = False
+        # level pool (module docstring): K resident episodes the device re-stages from; the host generates nothing after this
+        self.level = self.level_info = self._pool = self._pool_np = None
+        self.num_levels = 0
+        if levels is not None:
+            self._init_levels(levels, seed if level_seed is None else level_seed, level_order, seed)
         _LIVE.add(self)
+
+    def _init_levels(self, levels, level_seed, level_order, seed):
+        if isinstance(levels, np.ndarray):
+            blobs = np.array(levels, dtype=np.uint8, order="C", copy=True)      # (the handle's own copy: the caller may reuse the array)
+        else:
+            from .levels import make_levels
+            blobs, self.level_info = make_levels(int(levels), self.N, int(level_seed), self.direction_mode, threads=self.gen_threads)
+        self.num_levels = int(blobs.shape[0])
+        self.level_order = level_order
+        self._pool_np = blobs                                  # host copy: current_episode()
+        self._pool = torch.from_numpy(blobs).to(self.device)   # resident for the life of the handle
+        # [B] + one spare row that load_states points ids out of range at
+        self._level_buf = torch.full((self.B + 1,), -1, dtype=torch.int32, device=self.device)
+        self.level = self._level_buf[:self.B]
+        _lib.check(self.L.mcr_set_episode_pool(self.h, ctypes.c_void_p(self._pool.data_ptr()), self.num_levels, ctypes.c_uint64(int(seed) % 2 ** 64),
+                                               ctypes.c_uint32(self.env_offset), _lib.LEVEL_ORDER[level_order],
+                                               ctypes.c_void_p(self.level.data_ptr())), "mcr_set_episode_pool")
+        torch.cuda.synchronize(self.device)                    # the upload is complete whichever stream the first reset() runs on
+        self._episodes_generated = self.num_levels
+        self._async = self._native = False                     # nobody polls, generates or stages: the kernel owns the staged slots
 
     # ------------------------------------------------------------------ episode generation / staging
     def _generate(self, ids):
@@ -332,6 +380,8 @@ class VecMultiCarRacing:
             _lib.check(self.L.mcr_refill_hold(self.h, int(self._hold_refills)), "mcr_refill_hold")
 
     def _poll_and_refill(self):
+        if self._pool is not None:    # level pool: the device re-staged the env behind the step that consumed its episode
+            return 0
         if self._native:
             if not self._svc:         # (started after the first reset()'s own staging: from here on the RNG states and the blob rows are the service's)
                 _lib.check(self.L.mcr_refill_start(self.h, _lib.ptr(self.mt_track), _lib.ptr(self.mt_draw), self.direction_mode, self.gen_threads,
@@ -369,6 +419,8 @@ class VecMultiCarRacing:
     def _settle_staging(self, st):
         """Every env that consumed its staged episode gets the next one staged NOW (stream drained, consumption polled,
         refills finished): afterwards k_install finds `staged_ready` set for every env it is asked to reset."""
+        if self._pool is not None:    # level pool: every env was re-staged behind the reset / step that consumed its episode
+            return
         st.synchronize()
         self._poll_and_refill()
         self.wait_refills()
@@ -378,7 +430,9 @@ class VecMultiCarRacing:
         """Reset every env; returns obs [B, *obs_shape] uint8 (device tensor, overwritten by later steps)."""
         st = torch.cuda.current_stream(self.device)
         self.wait_refills()
-        if not self._has_reset:
+        if self._pool is not None:
+            pass                      # level pool: mcr_reset stages every env from the pool itself
+        elif not self._has_reset:
             every = np.arange(self.B, dtype=np.int32)
             self._stage(every, self._generate(every), st)
         else:
@@ -414,7 +468,9 @@ class VecMultiCarRacing:
             raise ValueError("step(None) needs frame_skip=1: the action-less step belongs to reset()")
         st = torch.cuda.current_stream(self.device)
         self._raise_worker_error()
-        if self._svc:
+        if self._pool is not None:
+            behind = False            # level pool: no host refills to fall behind
+        elif self._svc:
             lag = int(self.L.mcr_refill_lag(self.h))
             if lag < 0:
                 _lib.check(lag, "mcr_refill_lag")
@@ -453,6 +509,8 @@ class VecMultiCarRacing:
             info["terminal_count"] = self.terminal_count
         if self.state is not None:
             info["state"] = self.state
+        if self.level is not None:
+            info["level"] = self.level
         return self.obs, self.reward, self.done, info
 
     def refresh_state(self):
@@ -652,6 +710,12 @@ class VecMultiCarRacing:
         _lib.check(self.L.mcr_load_states(self.h, None if ids is None else ctypes.c_void_p(ids.data_ptr()), n, ctypes.c_void_p(blobs.data_ptr()),
                                           ctypes.c_void_p(refused.data_ptr()), ctypes.c_void_p(st.cuda_stream)), "mcr_load_states")
         self._has_reset = True
+        if self.level is not None:            # the blob does not say which level it came from (rows the kernel refuses — check=False — read -1 too)
+            if ids is None:
+                self.level[:n] = -1
+            else:                             # (no synchronisation: an id out of range, which the kernel skips, lands on the spare row)
+                i64 = ids.long()
+                self._level_buf.index_fill_(0, torch.where((i64 >= 0) & (i64 < self.B), i64, torch.full_like(i64, self.B)), -1)
         if not check:
             return refused
         k = int(refused.item())
@@ -662,7 +726,7 @@ class VecMultiCarRacing:
     def clone_envs(self, src_ids, dst_ids, check=True):
         """Env dst_ids[i] becomes a copy of env src_ids[i] (a source may be listed many times): the state by one kernel (mcr_copy_states),
         then the rows of obs (the ring of a stacked format), reward, done and truncated, so that the clone is observationally equal at once;
-        `self.state` is rewritten.  Destinations must be distinct and disjoint from the sources — validated (ValueError) with check=True when
+        `self.state` is rewritten, and with a level pool the `level` rows are copied.  Destinations must be distinct and disjoint from the sources — validated (ValueError) with check=True when
         the ids are sequences, the caller's obligation otherwise.  On the current stream; does not synchronise."""
         src, n, src_h = self._env_ids(src_ids, "src_ids")
         dst, m, dst_h = self._env_ids(dst_ids, "dst_ids", distinct=check)
@@ -677,7 +741,7 @@ class VecMultiCarRacing:
                                           ctypes.c_void_p(st.cuda_stream)), "mcr_copy_states")
         s64, d64 = src.long(), dst.long()
         frames = self._ring if self._ring is not None else self.obs
-        for t in (frames, self.reward, self.done, self.truncated):
+        for t in (frames, self.reward, self.done, self.truncated, self.level):
             if t is not None and n:
                 t.index_copy_(0, d64, t.index_select(0, s64))
 
@@ -698,7 +762,13 @@ class VecMultiCarRacing:
         return pos
 
     def current_episode(self, e):
-        """Host copy of the NEWEST generated episode of env e (the staged one once the env has reset)."""
+        """Host copy of the NEWEST generated episode of env e (the staged one once the env has reset).  With a level pool: of the level env e
+        is playing NOW, pool row `self.level[e]` (synchronises)."""
+        if self._pool is not None:
+            lv = int(self.level[int(e)].item())
+            if lv < 0:
+                raise _lib.McrError(f"env {e} has no known level (before reset(), or restored by load_states)")
+            return _lib.unpack_episode(np.ascontiguousarray(self._pool_np[lv]))
         return _lib.unpack_episode(np.ascontiguousarray(self._blobs_np[e]))
 
     def timing(self, mask):
