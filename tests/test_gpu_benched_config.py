@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.util import oracle_episode  # noqa: F401  (kept for symmetry with the other parity files)
+from tests.util import Follower, assert_frame, assert_state, rear_end_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -20,56 +20,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return torch
-
-
-class _Follower:
-    """Per-env oracle that follows global env g of a VecMultiCarRacing through its episodes: same RNG streams
-    (vec_env.py docstring), TimeLimit counted here (the oracle is the bare env), next episode = next draw."""
-
-    def __init__(self, O, N, seed, g, max_steps, use_random_direction=True, contacts=True):
-        s = (seed + g) % 2 ** 32
-        self.O, self.N, self.g, self.max_steps, self.urd = O, N, g, max_steps, use_random_direction
-        self.tr, self.gr = np.random.RandomState(s), np.random.RandomState((s + 2 ** 31) % 2 ** 32)
-        self.o = O.OracleEnv(N, car_contacts=contacts)
-        self.first_obs = None
-        self.new_episode()
-
-    def new_episode(self):
-        ep = self.O.new_episode(self.N, self.tr, self.gr, use_random_direction=self.urd)
-        self.first_obs = self.o.reset(ep)
-        self.first_amb = self.o.last_amb
-        self.steps = 0
-
-    def after_step(self, done):
-        """bookkeeping after the batched oracle step: returns (done incl. TimeLimit, truncated)"""
-        self.steps += 1
-        trunc = False
-        if self.max_steps > 0 and self.steps >= self.max_steps:
-            trunc = not done
-            done = True
-        return done, trunc
-
-
-def _cmp_pixels(got, want, amb, what, budget=14):
-    d = (got != want).any(-1)
-    bad = int((d & (amb == 0)).sum())
-    if bad:
-        where = np.argwhere(d & (amb == 0))[:6]
-        detail = "; ".join(f"view {a} row {r} col {c}: got {got[a, r, c].tolist()} want {want[a, r, c].tolist()}" for a, r, c in where)
-        raise AssertionError(f"{what}: {bad} unambiguous pixels differ: {detail}")
-    assert int(d.sum()) <= budget * got.shape[0], f"{what}: {int(d.sum())} edge pixels differ"
-
-
-def _cmp_state(env, followers, idx, what):
-    st = env.get_state(); es = env.get_env_state()
-    for f, e in zip(followers, idx):
-        so = f.o.state(); eo = f.o.env_state()
-        for k in ("bodies", "joints", "wheels", "limit", "on_road", "sleep"):
-            assert np.array_equal(st[k][e], so[k]), f"{what} env {e}: {k} differs"
-        assert np.array_equal(es["reward"][e], eo["reward"]) and np.array_equal(es["tile_visited_count"][e], eo["tile_visited_count"]), f"{what} env {e}: reward/tvc"
-        T = f.o.T
-        assert np.array_equal(es["tile_flags"][e, :T] & 0xff, eo["visited"]) and np.array_equal((es["tile_flags"][e, :T] >> 8) & 1, eo["touched"]), f"{what} env {e}: tile flags"
-        assert es["num_tiles"][e] == T
 
 
 def _actions(torch, g, B, N, car1_floors):
@@ -112,11 +62,11 @@ def _run_sampled(torch, O, B, N, seed, steps, n_sample, max_steps, masked_reset_
     else:
         idx = np.sort(rs.choice(B, n_sample, replace=False))
     idx_t = torch.from_numpy(idx).cuda()
-    fol = [_Follower(O, N, seed, int(g), max_steps) for g in idx]
+    fol = [Follower(O, N, seed, int(g), max_steps) for g in idx]
     if with_obs:
         o0 = obs[idx_t].cpu().numpy()
         for j, f in enumerate(fol):
-            _cmp_pixels(o0[j], f.first_obs, f.first_amb, f"reset env {f.g}")
+            assert_frame(o0[j], f.first_obs, f.first_amb, f"reset env {f.g}", 14)
     g = torch.Generator(device="cuda"); g.manual_seed(seed)
     threads = os.cpu_count() or 1
     n_resets = n_contacts = 0
@@ -143,11 +93,11 @@ def _run_sampled(torch, O, B, N, seed, steps, n_sample, max_steps, masked_reset_
                 if j in resets:
                     f.new_episode(); n_resets += 1
                     if with_obs:
-                        _cmp_pixels(got[j], f.first_obs, f.first_amb, f"step {k} env {f.g} first frame after auto-reset")
+                        assert_frame(got[j], f.first_obs, f.first_amb, f"step {k} env {f.g} first frame after auto-reset", 14)
                 elif check_px:
-                    _cmp_pixels(got[j], o_obs[j], o_amb[j], f"step {k} env {f.g}")
+                    assert_frame(got[j], o_obs[j], o_amb[j], f"step {k} env {f.g}", 14)
         if check_st:
-            _cmp_state(env, fol, idx, f"step {k}")
+            assert_state(env, zip(idx, (f.o for f in fol)), f"step {k}")
         if k in masked_reset_at:                       # masked reset of a random quarter of the batch incl. some followers
             m = (rs.uniform(size=B) < 0.25); m[idx[::3]] = True
             obs = env.reset_envs(torch.from_numpy(m.astype(np.uint8)).cuda())
@@ -156,8 +106,8 @@ def _run_sampled(torch, O, B, N, seed, steps, n_sample, max_steps, masked_reset_
                 if m[f.g]:
                     f.new_episode(); n_resets += 1
                     if with_obs:
-                        _cmp_pixels(got[j], f.first_obs, f.first_amb, f"masked reset at step {k} env {f.g}")
-            _cmp_state(env, fol, idx, f"after masked reset at step {k}")
+                        assert_frame(got[j], f.first_obs, f.first_amb, f"masked reset at step {k} env {f.g}", 14)
+            assert_state(env, zip(idx, (f.o for f in fol)), f"after masked reset at step {k}")
     frozen = int(env.debug_counters()[3])
     assert env.verdict_mismatches() == 0, "the touch verdict of the main launches disagreed with the contact pass"
     env.close()
@@ -266,7 +216,7 @@ def test_freeze_and_thaw_when_host_withholds_staging(torch_cuda, oracle, streams
                             car_contacts=True, async_refill=False, streams=streams)
     env.reset()                                          # consumes episode 1 and stages episode 2
     env.hold_refills = True                              # from now on nothing new gets staged
-    fol = [_Follower(oracle, N, seed, g, L) for g in range(B)]
+    fol = [Follower(oracle, N, seed, g, L) for g in range(B)]
     rs = np.random.RandomState(4)
 
     def step_both(expect_done=None):
@@ -300,8 +250,8 @@ def test_freeze_and_thaw_when_host_withholds_staging(torch_cuda, oracle, streams
     assert (rw == 0).all() and not dn.any()
     for j, f in enumerate(fol):
         f.new_episode()
-        _cmp_pixels(obs[j], f.first_obs, f.first_amb, f"thaw env {j}")
-    _cmp_state(env, fol, range(B), "after thaw")
+        assert_frame(obs[j], f.first_obs, f.first_amb, f"thaw env {j}", 14)
+    assert_state(env, zip(range(B), (f.o for f in fol)), "after thaw")
     for k in range(L - 1):                               # and the episode continues bit-exact
         a, obs, rw, dn = step_both()
         _, _, orw, od = oracle.step_batch([f.o for f in fol], a, None, threads=2)
@@ -324,7 +274,7 @@ def test_freeze_with_touching_cars_contact_pass_in_front(torch_cuda, oracle, mon
     assert not env.L.mcr_concurrent_collide(env.h)
     env.reset()
     env.hold_refills = True
-    fol = [_Follower(oracle, N, seed, g, L) for g in range(B)]
+    fol = [Follower(oracle, N, seed, g, L) for g in range(B)]
     rs = np.random.RandomState(5)
 
     def step_both(touching_drive):
@@ -342,16 +292,7 @@ def test_freeze_with_touching_cars_contact_pass_in_front(torch_cuda, oracle, mon
             if d:
                 f.new_episode()
     # episode 2: car 1 is put right behind car 0 (overlapping it a little), so the pair touches until the TimeLimit ends the episode
-    st = env.get_state()["bodies"].copy()
-    for e in range(B):
-        ang = st[e, 0, 0, 2]
-        fwd = np.array([-np.sin(ang), np.cos(ang)], np.float32)
-        delta = (st[e, 0, 0, :2] - fwd * np.float32(4.9)) - st[e, 1, 0, :2]
-        st[e, 1, :, 0] += delta[0]; st[e, 1, :, 1] += delta[1]; st[e, 1, :, 2] = ang
-    env.set_bodies(st)
-    for e, f in enumerate(fol):
-        for k in range(5):
-            f.o.set_body(1, k, st[e, 1, k])
+    rear_end_setup(env, [f.o for f in fol], gap=4.9)
     touching_at_end = 0
     for k in range(L):
         a, obs, rw, dn = step_both(True)
@@ -369,8 +310,8 @@ def test_freeze_with_touching_cars_contact_pass_in_front(torch_cuda, oracle, mon
     assert (rw == 0).all() and not dn.any()
     for j, f in enumerate(fol):
         f.new_episode()
-        _cmp_pixels(obs[j], f.first_obs, f.first_amb, f"thaw env {j}")
-    _cmp_state(env, fol, range(B), "after thaw")
+        assert_frame(obs[j], f.first_obs, f.first_amb, f"thaw env {j}", 14)
+    assert_state(env, zip(range(B), (f.o for f in fol)), "after thaw")
     for k in range(L - 1):
         a, obs, rw, dn = step_both(False)
         _, _, orw, od = oracle.step_batch([f.o for f in fol], a, None, threads=2)

@@ -10,8 +10,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests.test_gpu_parity import _assert_pixels, _make, _oracles, _rear_end_setup
-from tests.util import random_actions
+from tests.util import assert_pixels, env_streams, make_env, oracles, random_actions, rear_end_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -50,8 +49,8 @@ def test_flags_and_hud_pixels_with_and_without_reads_in_between(torch_cuda, orac
     pixels of every frame must still show the previous step's flags."""
     torch = torch_cuda
     B, N, seed = 3, 2, 21
-    env = _make(B, N, seed, contacts=False, direction="CW", streams=2); env.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=False, direction="CW")
+    env = make_env(B, N, seed, contacts=False, direction="CW", streams=2); env.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=False, direction="CW")
     rng = np.random.RandomState(2)
     back = grass = False
     for k in range(120):
@@ -62,7 +61,7 @@ def test_flags_and_hud_pixels_with_and_without_reads_in_between(torch_cuda, orac
         _assert_deferring(env, torch)
         if read_every_step:
             _assert_flags(env, orcs, f"step {k}")
-        _assert_pixels(obs.cpu().numpy(), orcs, budget=40)
+        assert_pixels(obs.cpu().numpy(), orcs, budget=40)
         b, g = _seen(orcs); back |= b; grass |= g
     assert back and grass, "scenario never set driving_backward / driving_on_grass"
     _assert_flags(env, orcs, "end")
@@ -76,8 +75,8 @@ def test_a_dropped_pending_launch_leaves_stale_flags(torch_cuda, oracle, lib):
     torch = torch_cuda
     B, N, seed = 3, 2, 21
     for in_step in (False, True):
-        env = _make(B, N, seed, contacts=False, direction="CW", streams=2); env.reset()
-        orcs = _oracles(oracle, B, N, seed, contacts=False, direction="CW")
+        env = make_env(B, N, seed, contacts=False, direction="CW", streams=2); env.reset()
+        orcs = oracles(oracle, B, N, seed, contacts=False, direction="CW")
         if in_step:
             lib.check(env.L.mcr_debug_set(env.h, lib.DEBUG_FLAGS_IN_STEP))
         rng = np.random.RandomState(2)
@@ -111,7 +110,7 @@ def test_flags_across_resets_path_switches_and_a_blob_round_trip(torch_cuda, ora
     interruption equal the oracle's."""
     torch = torch_cuda
     B, N, seed, L = 4, 2, 77, 120
-    env = _make(B, N, seed, contacts=False, auto_reset=True, max_episode_steps=L, use_random_direction=True, streams=2)
+    env = make_env(B, N, seed, contacts=False, auto_reset=True, max_episode_steps=L, use_random_direction=True, streams=2)
     env.reset()
     torch.cuda.synchronize()
     bound, unbound = torch.cuda.Stream(), torch.cuda.Stream()     # (bound: not the null stream, which cannot be captured for graph replay)
@@ -119,8 +118,7 @@ def test_flags_across_resets_path_switches_and_a_blob_round_trip(torch_cuda, ora
     modes = set()
     streams, orcs = [], []
     for e in range(B):
-        s = (seed + e) % 2 ** 32
-        tr, gr = np.random.RandomState(s), np.random.RandomState((s + 2 ** 31) % 2 ** 32)
+        tr, gr = env_streams(seed, e)
         o = oracle.OracleEnv(N, car_contacts=False); o.reset(oracle.new_episode(N, tr, gr, use_random_direction=True))
         streams.append((tr, gr)); orcs.append(o)
     steps = np.zeros(B, np.int64)
@@ -150,7 +148,7 @@ def test_flags_across_resets_path_switches_and_a_blob_round_trip(torch_cuda, ora
                 assert bool(dn[e]) == (steps[e] == L), f"step {k} env {e}: done"
                 if steps[e] == L:                                          # TimeLimit: the env's next episode, first observation in this step's frame
                     o.reset(oracle.new_episode(N, *streams[e], use_random_direction=True)); steps[e] = 0
-            _assert_pixels(frames, orcs, budget=40)
+            assert_pixels(frames, orcs, budget=40)
             b, g = _seen(orcs); back |= b; grass |= g
             if k == 20:                                                    # a snapshot taken and restored while the step's launch is pending
                 blob = env.get_state_blob(1); env.set_state_blob(1, blob)
@@ -177,9 +175,9 @@ def test_flags_of_envs_that_move_between_the_main_launch_and_the_contact_list(to
     every frame against the oracle (no reads in between but the last)."""
     torch = torch_cuda
     B, N, seed = 5, 2, 62
-    env = _make(B, N, seed, contacts=True, streams=2); env.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=True)
-    _rear_end_setup(env, orcs)
+    env = make_env(B, N, seed, contacts=True, streams=2); env.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=True)
+    rear_end_setup(env, orcs)
     rng = np.random.RandomState(4)
     touched = free_after = 0
     for k in range(160):
@@ -195,7 +193,7 @@ def test_flags_of_envs_that_move_between_the_main_launch_and_the_contact_list(to
             n = o.num_car_contacts(); touched += n; free_after += 1 if (touched and not n) else 0
             assert np.array_equal(r, rw[e]), f"step {k} env {e}"
         _assert_deferring(env, torch)
-        _assert_pixels(obs.cpu().numpy(), orcs, budget=40)
+        assert_pixels(obs.cpu().numpy(), orcs, budget=40)
         if k % 40 == 39:
             _assert_flags(env, orcs, f"step {k}")
     assert touched > 50 and free_after > 50, "scenario produced no car<->car contacts, or never left them"

@@ -12,9 +12,7 @@ import numpy as np
 import pytest
 
 from tests import state_obs_ref as R
-from tests.test_gpu_benched_config import _Follower, _cmp_pixels, _cmp_state
-from tests.test_gpu_world import _drive, _device_ids
-from tests.test_gpu_obs_format import _luma_np
+from tests.util import Follower, assert_frame, assert_state, device_proxy_ids, drive_actions, luma_np
 
 pytestmark = pytest.mark.gpu
 
@@ -28,18 +26,11 @@ def torch_cuda():
     return torch
 
 
-class _MacroFollower(_Follower):
-    """_Follower that also keeps the episode it plays (the state-vector restatement reads its track) and the episode's return"""
-
-    def __init__(self, *a, render=True, **kw):
-        self.render = render
-        super().__init__(*a, **kw)
+class _MacroFollower(Follower):
+    """Follower that also keeps the episode's return"""
 
     def new_episode(self):
-        self.ep = self.O.new_episode(self.N, self.tr, self.gr, use_random_direction=self.urd)
-        self.first_obs = self.o.reset(self.ep, render=self.render)
-        self.first_amb = self.o.last_amb
-        self.steps = 0
+        super().new_episode()
         self.ret = np.zeros(self.N)
 
 
@@ -104,11 +95,11 @@ def test_macro_step_matches_the_oracles_frame_skip_loop(torch_cuda, oracle, lib,
         fol = [_MacroFollower(oracle, N, seed, int(g), max_steps) for g in idx]
         o0 = obs[idx_t].cpu().numpy()
         for j, f in enumerate(fol):
-            _cmp_pixels(o0[j], f.first_obs, f.first_amb, f"reset env {f.g}")
+            assert_frame(o0[j], f.first_obs, f.first_amb, f"reset env {f.g}", 14)
         gen = torch.Generator(device="cuda"); gen.manual_seed(seed)
         ends = np.zeros(K, int); contacts = 0; episodes = np.zeros(n_sample, int)
         for m in range(3 * per_ep + 1):
-            a = _drive(torch, gen, B, N, K * m, K * per_ep)
+            a = drive_actions(torch, gen, B, N, K * m, K * per_ep)
             obs, rew, done, info = env.step(a)
             check = m % 8 == 7 or m % per_ep == per_ep - 1
             a_s = a[idx_t].cpu().numpy()
@@ -128,13 +119,13 @@ def test_macro_step_matches_the_oracles_frame_skip_loop(torch_cuda, oracle, lib,
                 assert np.array_equal(er[j], want.ep_return[j]) and el[j] == want.ep_len[j], f"macro-step {m} env {f.g}: episode statistics {er[j]}, {el[j]} vs {want.ep_return[j]}, {want.ep_len[j]}"
                 f.new_episode()
                 tid, fid = f.o.proxy_ids()
-                assert np.array_equal(_device_ids(env, lib, f.g), np.concatenate([tid, fid.ravel()])), f"macro-step {m} env {f.g}: proxy ids of the new episode"
-                _cmp_pixels(got[j], f.first_obs, f.first_amb, f"macro-step {m} env {f.g}: first frame after an ending in sub-step {want.end_sub[j]}")
+                assert np.array_equal(device_proxy_ids(env, lib, f.g), np.concatenate([tid, fid.ravel()])), f"macro-step {m} env {f.g}: proxy ids of the new episode"
+                assert_frame(got[j], f.first_obs, f.first_amb, f"macro-step {m} env {f.g}: first frame after an ending in sub-step {want.end_sub[j]}", 14)
             if check:
                 for j, f in enumerate(fol):
                     if not want.done[j]:
-                        _cmp_pixels(got[j], want.obs[j], want.amb[j], f"macro-step {m} env {f.g}")
-                _cmp_state(env, fol, idx, f"macro-step {m}")          # (a re-spawned env: the new episode's reset state, not advanced)
+                        assert_frame(got[j], want.obs[j], want.amb[j], f"macro-step {m} env {f.g}", 14)
+                assert_state(env, zip(idx, (f.o for f in fol)), f"macro-step {m}")          # (a re-spawned env: the new episode's reset state, not advanced)
         print(f"max_steps {max_steps}: endings per sub-step {ends.tolist()}, env-steps of the sample with a touching pair {contacts}")
         assert int(env.debug_counters()[3]) == 0 and env.verdict_mismatches() == 0 and env.status_words()[:5].tolist() == [0] * 5
         env.close()
@@ -154,7 +145,7 @@ def test_frame_skip_1_is_the_plain_step(torch_cuda):
     assert torch.equal(one.reset(), plain.reset())
     gen = torch.Generator(device="cuda"); gen.manual_seed(seed)
     for k in range(300):
-        a = _drive(torch, gen, B, N, k, 30)
+        a = drive_actions(torch, gen, B, N, k, 30)
         o1, r1, d1, i1 = one.step(a); o0, r0, d0, i0 = plain.step(a)
         assert torch.equal(o1, o0) and torch.equal(r1, r0) and torch.equal(d1, d0) and torch.equal(i1["TimeLimit.truncated"], i0["TimeLimit.truncated"]), f"step {k}"
     s1, s0 = one.get_state(), plain.get_state()
@@ -178,7 +169,7 @@ def test_stack_holds_policy_step_frames(torch_cuda, oracle):
     obs = env.reset().cpu().numpy()
     assert obs.shape == (B, N, ks, 96, 96)
     fol = [_MacroFollower(oracle, N, seed, g, L) for g in range(B)]
-    stacks = [[(_luma_np(f.first_obs), f.first_amb.copy())] * ks for f in fol]
+    stacks = [[(luma_np(f.first_obs), f.first_amb.copy())] * ks for f in fol]
 
     def compare(got, what):
         for e in range(B):
@@ -201,9 +192,9 @@ def test_stack_holds_policy_step_frames(torch_cuda, oracle):
             if want.done[e]:
                 mid_skip += int(want.end_sub[e] < K - 1)
                 f.new_episode()
-                stacks[e] = [(_luma_np(f.first_obs), f.first_amb.copy())] * ks
+                stacks[e] = [(luma_np(f.first_obs), f.first_amb.copy())] * ks
             else:
-                stacks[e] = stacks[e][1:] + [(_luma_np(want.obs[e]), want.amb[e])]
+                stacks[e] = stacks[e][1:] + [(luma_np(want.obs[e]), want.amb[e])]
         compare(obs.cpu().numpy(), f"macro-step {m}")
     assert mid_skip >= 2 * B, mid_skip
     env.close()
@@ -278,8 +269,8 @@ def test_parked_is_not_starved_and_starved_is_still_counted(torch_cuda, oracle, 
         assert dn.all() and (want.end_sub == (L - 1) % K).all() and (L - 1) % K < K - 1
         for j, f in enumerate(fol):
             f.new_episode()
-            _cmp_pixels(obs[j], f.first_obs, f.first_amb, f"re-spawn of a parked env {j}")
-        _cmp_state(env, fol, range(B), "after the re-spawn of the parked envs")
+            assert_frame(obs[j], f.first_obs, f.first_amb, f"re-spawn of a parked env {j}", 14)
+        assert_state(env, zip(range(B), (f.o for f in fol)), "after the re-spawn of the parked envs")
         assert int(env.debug_counters()[3]) == 0 and env.status_words()[4] == 0, "a parked env was counted as starved"
         for m in range(per_ep - 1):                      # episode 2 up to the macro-step that ends it
             a, obs, rw, dn = step()
@@ -304,8 +295,8 @@ def test_parked_is_not_starved_and_starved_is_still_counted(torch_cuda, oracle, 
     assert (rw == 0).all() and not dn.any()
     for j, f in enumerate(fol):
         f.new_episode()
-        _cmp_pixels(obs[j], f.first_obs, f.first_amb, f"thaw env {j}")
-    _cmp_state(env, fol, range(B), "after thaw")
+        assert_frame(obs[j], f.first_obs, f.first_amb, f"thaw env {j}", 14)
+    assert_state(env, zip(range(B), (f.o for f in fol)), "after thaw")
     for m in range(per_ep - 1):                          # and the episode continues bit-exact
         a, obs, rw, dn = step()
         follow(a, rw, dn, f"episode 3 macro-step {m}")
@@ -327,7 +318,7 @@ def test_macro_step_does_not_depend_on_the_batch(torch_cuda):
     gen = torch.Generator(device="cuda"); gen.manual_seed(2)
     n_done = 0
     for m in range(200):
-        a = _drive(torch, gen, 4096, N, K * m, 52)
+        a = drive_actions(torch, gen, 4096, N, K * m, 52)
         ob, rb, db, ib = big.step(a)
         osm, rs_, ds, is_ = small.step(a[g0:g0 + 4].contiguous())
         assert torch.equal(rb[g0:g0 + 4], rs_) and torch.equal(db[g0:g0 + 4], ds) and torch.equal(ib["TimeLimit.truncated"][g0:g0 + 4], is_["TimeLimit.truncated"]), f"macro-step {m}"

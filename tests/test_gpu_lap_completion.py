@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 
 from tests import state_obs_ref as R
-from tests.test_gpu_parity import _assert_state_equal
-from tests.util import LAP_CASES, LAP_DRIVE_MAX, lap_drive_phase, lap_run, lap_teleport_phase, lap_touching_pair
+from tests.util import (LAP_CASES, LAP_DRIVE_MAX, assert_frame, assert_state, env_streams, lap_drive_phase, lap_run, lap_teleport_phase,
+                        lap_touching_pair, make_env)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,12 +27,8 @@ def torch_cuda():
 
 
 def _make(case, B=None, **kw):
-    from multi_car_racing_amd.vec_env import VecMultiCarRacing
-    N, lap_car, direction, seed, nB = LAP_CASES[case]
-    kw.setdefault("auto_reset", False); kw.setdefault("max_episode_steps", 0)
-    kw.setdefault("streams", int(os.environ.get("MCR_TEST_STREAMS", "1")))
-    return VecMultiCarRacing(nB if B is None else B, N, seed=seed, direction=direction, use_random_direction=False, car_contacts=True,
-                             async_refill=False, **kw)
+    N, _, direction, seed, nB = LAP_CASES[case]
+    return make_env(nB if B is None else B, N, seed, direction=direction, **kw)
 
 
 def _np(got):
@@ -49,15 +45,6 @@ def _same_step(what, rew, done, got, truncated=None):
     assert np.array_equal(dn[:n], done), f"{what}: done {dn[:n].tolist()} vs the oracle's {done.tolist()}"
     assert np.array_equal(tr[:n], np.zeros(n, bool) if truncated is None else truncated), f"{what}: truncated {tr[:n].tolist()}"
     return obs, rw, dn, tr
-
-
-def _assert_frame(got, o, what, budget=40):
-    """env frames [N, 96, 96, 3] vs the frame the oracle rendered inside its last step / reset (tests/test_gpu_parity.py: _assert_pixels)"""
-    oo, amb = o.last_obs, o.last_amb
-    assert oo is not None, "the oracle's step was not rendered"
-    d = (oo != got).any(-1)
-    assert (d & (amb == 0)).sum() == 0, f"{what}: {(d & (amb == 0)).sum()} unambiguous pixels differ"
-    assert d.sum() <= budget * len(oo), f"{what}: {d.sum()} edge pixels differ"
 
 
 def _contact_counts(env):
@@ -79,12 +66,12 @@ def _assert_lap_end(env, run, e, obs, what):
     with a score of 900 and more on the label and every tile touched"""
     o = run.orcs[e]; es = env.get_env_state(); eo = o.env_state()
     assert int(es["tile_visited_count"][e, run.lap_car]) == int(es["num_tiles"][e]) == o.T == int(eo["tile_visited_count"][run.lap_car]), what
-    _assert_state_equal(env, run.orcs, what)
+    assert_state(env, enumerate(run.orcs), what)
     if run.N == 8:      # the eighth "visited" bit of tile_flags
         assert np.array_equal(es["tile_flags"][e, :o.T] & 0xff, eo["visited"]) and ((es["tile_flags"][e, :o.T] >> 7) & 1).all(), what
     if obs is not None:
         assert eo["reward"][run.lap_car] >= 900.0 and eo["touched"].all(), "the frame is meant to show a three-digit score and a fully touched track"
-        _assert_frame(obs[e], o, what)
+        assert_frame(obs[e], o.last_obs, o.last_amb, what, 40)
 
 
 def _drive_to_the_lap(env, run, before=None, on_end=None):
@@ -94,7 +81,7 @@ def _drive_to_the_lap(env, run, before=None, on_end=None):
     def chk(k, rew, done, got):
         obs, _, _, _ = _same_step(f"drive step {k}", rew, done, got)
         if k % 10 == 9:
-            _assert_state_equal(env, run.orcs, f"drive step {k}")
+            assert_state(env, enumerate(run.orcs), f"drive step {k}")
         for e in range(len(run.orcs)):
             if done[e] and ended[e] is None:
                 ended[e] = k
@@ -114,9 +101,9 @@ def test_lap_ends_in_the_oracles_step(torch_cuda, oracle, case, streams):
     whose contact pass touches the last tile — not a step later — with the 1000/T share in that step's reward, in whichever lane the car sits."""
     env = _make(case, streams=streams); env.reset()
     run = lap_run(oracle, case, env=env)
-    _assert_state_equal(env, run.orcs, "after reset")
+    assert_state(env, enumerate(run.orcs), "after reset")
     _teleport_in_lockstep(run)
-    _assert_state_equal(env, run.orcs, "end of the teleport phase")
+    assert_state(env, enumerate(run.orcs), "end of the teleport phase")
     ended = _drive_to_the_lap(env, run)
     assert min(ended) >= 20, ended
     assert not env.status_words()[:5].any() and env.verdict_mismatches() == 0
@@ -220,13 +207,6 @@ def _second_episode(oracle, run, e, render=True):
     return obs
 
 
-def _assert_first_frame(got, o, first, what, budget=40):
-    """the first frame of the next episode [N, 96, 96, 3] vs the one the oracle's reset rendered: as _assert_frame"""
-    d = (first != got).any(-1)
-    assert (d & (o.last_amb == 0)).sum() == 0, f"{what}: {(d & (o.last_amb == 0)).sum()} unambiguous pixels differ"
-    assert d.sum() <= budget * len(first), f"{what}: {d.sum()} edge pixels differ"
-
-
 # ------------------------------------------------------------------------------------------------------------ (e) lap on the TimeLimit step
 def test_lap_on_the_time_limit_step_is_not_truncated(torch_cuda, oracle):
     """`trunc = !done`: a lap that completes exactly on the TimeLimit step reports TimeLimit.truncated == False; a limit one step shorter
@@ -272,13 +252,13 @@ def _lap_then_auto_reset(torch, oracle, streams, terminal):
             assert int(o.env_state()["tile_visited_count"][run.lap_car]) == o.T, "the lap is meant to be the cause"
             if terminal:       # the LAST frame of the finished episode: the oracle's frame of the completing step
                 i = ids.cpu().numpy().tolist().index(e)
-                _assert_frame(frames[i].cpu().numpy(), o, f"terminal frame env {e}")
+                assert_frame(frames[i].cpu().numpy(), o.last_obs, o.last_amb, f"terminal frame env {e}", 40)
             assert np.array_equal(got[3]["episode_return"][e].cpu().numpy(), ret[e]), f"env {e}: episode_return vs the ordered f64 sum"
             assert int(got[3]["episode_length"][e].item()) == run.steps
             first = _second_episode(oracle, run, e)
-            _assert_first_frame(obs[e], o, first, f"env {e}: first frame after the lap")
+            assert_frame(obs[e], first, o.last_amb, f"env {e}: first frame after the lap", 40)
         if len(np.nonzero(done)[0]) or k % 10 == 9:
-            _assert_state_equal(env, run.orcs, f"drive step {k}")             # (a re-spawned env: its new episode's reset state, counts cleared)
+            assert_state(env, enumerate(run.orcs), f"drive step {k}")             # (a re-spawned env: its new episode's reset state, counts cleared)
         if all(x is not None for x in ended) and k >= max(ended) + 30:
             break
     assert all(x is not None for x in ended), ended
@@ -338,8 +318,8 @@ def test_lap_inside_a_macro_step(torch_cuda, oracle):
         assert end is not None and int(o.env_state()["tile_visited_count"][run.lap_car]) == o.T, f"n {n}: no lap"
         assert int(info["episode_length"][0].item()) == run.steps
         first = _second_episode(oracle, run, 0)
-        _assert_first_frame(obs[0].cpu().numpy(), o, first, f"n {n}: first frame of the next episode")
-        _assert_state_equal(env, run.orcs, f"n {n}: the next episode, not advanced")
+        assert_frame(obs[0].cpu().numpy(), first, o.last_amb, f"n {n}: first frame of the next episode", 40)
+        assert_state(env, enumerate(run.orcs), f"n {n}: the next episode, not advanced")
         subs.add(end)
         env.close()
     assert subs == {0, 1, 2, 3}, f"completing sub-steps seen: {subs}"
@@ -412,16 +392,15 @@ def test_256_envs_complete_their_lap_in_one_step(torch_cuda, oracle):
     # the sampled envs against their oracles: env g's second episode on env 0's world
     first = []
     for g, run in enumerate(runs):
-        s = (LAP_CASES["n2"][3] + g) % 2 ** 32
-        tr, gr = np.random.RandomState(s), np.random.RandomState((s + 2 ** 31) % 2 ** 32)
+        tr, gr = env_streams(LAP_CASES["n2"][3], g)
         oracle.new_episode(2, tr, gr, direction=run.direction, use_random_direction=False)      # g's first draw: consumed by its reset()
         run.streams[0] = (tr, gr)
         first.append(_second_episode(oracle, run, 0))
     orcs = [run.orcs[0] for run in runs]
     ob = obs[:nS].cpu().numpy()
     for g in range(nS):
-        _assert_first_frame(ob[g], orcs[g], first[g], f"env {g}: first frame after the lap")
-    _assert_state_equal(big, orcs, "the re-spawned envs")
+        assert_frame(ob[g], first[g], orcs[g].last_amb, f"env {g}: first frame after the lap", 40)
+    assert_state(big, enumerate(orcs), "the re-spawned envs")
     gen = torch.Generator(device="cuda"); gen.manual_seed(3)
     for k in range(20):
         at = torch.rand((B, 2, 3), device="cuda", generator=gen); at[..., 0] = at[..., 0] * 2 - 1; at[..., 2] *= 0.2
@@ -432,6 +411,6 @@ def test_256_envs_complete_their_lap_in_one_step(torch_cuda, oracle):
         for g, o in enumerate(orcs):
             _, r, d, _ = o.step(a[g], render=False)
             assert np.array_equal(r, r1[g].cpu().numpy()), f"step {k} after the lap env {g}"
-    _assert_state_equal(big, orcs, "20 steps after the lap")
+    assert_state(big, enumerate(orcs), "20 steps after the lap")
     assert np.array_equal(big.status_words(), baseline) and int(big.debug_counters()[3]) == 0
     big.close(); small.close()

@@ -6,7 +6,7 @@ bit for bit — the same raster keys, so no ambiguity mask —, and a stack is w
 import numpy as np
 import pytest
 
-from tests.util import oracle_episode
+from tests.util import luma_np, oracle_episode
 
 pytestmark = pytest.mark.gpu
 
@@ -22,11 +22,6 @@ def _luma(torch, rgb):
     """OpenCV's COLOR_RGB2GRAY on 8-bit data (the formula of include/mcr.h), on the device"""
     x = rgb.to(torch.int32)
     return ((4899 * x[..., 0] + 9617 * x[..., 1] + 1868 * x[..., 2] + 8192) >> 14).to(torch.uint8)
-
-
-def _luma_np(rgb):
-    x = rgb.astype(np.int64)
-    return ((4899 * x[..., 0] + 9617 * x[..., 1] + 1868 * x[..., 2] + 8192) >> 14).astype(np.uint8)
 
 
 def _pair(B, N, seed, max_steps, k, **kw):
@@ -152,7 +147,7 @@ def test_oracle_gray_stack(torch_cuda, oracle):
             oo, _, d, _ = o.step(a[e], render=t >= steps - k)
             assert not d
             if t >= steps - k:
-                want[e].append((_luma_np(oo), o.last_amb.copy()))
+                want[e].append((luma_np(oo), o.last_amb.copy()))
     assert not bool(done.any().item())
     got = obs.cpu().numpy()
     for e in sample:

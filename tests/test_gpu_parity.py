@@ -6,11 +6,10 @@ pixels are compared exactly outside the oracle's "ambiguous" mask (pixel centres
 edge, where real GL is implementation-defined too), with a small budget inside it."""
 import ctypes
 
-import os
 import numpy as np
 import pytest
 
-from tests.util import oracle_episode, random_actions
+from tests.util import assert_pixels, assert_state, env_streams, make_env, oracles, random_actions, rear_end_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -22,54 +21,15 @@ def torch_cuda():
     return torch
 
 
-def _make(B, N, seed, contacts=True, **kw):
-    from multi_car_racing_amd.vec_env import VecMultiCarRacing
-    kw.setdefault("use_random_direction", False); kw.setdefault("auto_reset", False); kw.setdefault("max_episode_steps", 0)
-    kw.setdefault("streams", int(os.environ.get("MCR_TEST_STREAMS", "1")))     # 2: whole suite with the contact side stream
-    return VecMultiCarRacing(B, N, seed=seed, car_contacts=contacts, async_refill=False, **kw)
-
-
-def _oracles(O, B, N, seed, contacts=True, **kw):
-    out = []
-    for e in range(B):
-        o = O.OracleEnv(N, car_contacts=contacts, h_ratio=kw.get("h_ratio", 0.25), backwards_flag=kw.get("backwards_flag", True),
-                        use_ego_color=kw.get("use_ego_color", False))
-        o.reset(oracle_episode(O, N, seed, e, direction=kw.get("direction", "CCW"), use_random_direction=kw.get("use_random_direction", False)))
-        out.append(o)
-    return out
-
-
-def _assert_state_equal(env, orcs, what=""):
-    st = env.get_state(); es = env.get_env_state()
-    for e, o in enumerate(orcs):
-        so = o.state(); eo = o.env_state()
-        for k in ("bodies", "joints", "wheels", "limit", "on_road", "sleep"):
-            assert np.array_equal(st[k][e], so[k]), f"{what} env {e}: {k} differs (max abs {np.abs(st[k][e].astype(np.float64) - so[k]).max()})"
-        assert np.array_equal(es["reward"][e], eo["reward"]) and np.array_equal(es["tile_visited_count"][e], eo["tile_visited_count"])
-        T = o.T
-        assert np.array_equal(es["tile_flags"][e, :T] & 0xff, eo["visited"]) and np.array_equal((es["tile_flags"][e, :T] >> 8) & 1, eo["touched"])
-        assert es["t"][e] == eo["t"] and es["num_tiles"][e] == T
-
-
-def _assert_pixels(obs, orcs, budget=12):
-    """GPU obs vs the frame the oracle rendered INSIDE its last step/reset (call step(..., render=True))."""
-    for e, o in enumerate(orcs):
-        oo, amb = o.last_obs, o.last_amb
-        assert oo is not None, "oracle step was not rendered"
-        d = (oo != obs[e]).any(-1)
-        assert (d & (amb == 0)).sum() == 0, f"env {e}: {(d & (amb == 0)).sum()} unambiguous pixels differ"
-        assert d.sum() <= budget * len(oo), f"env {e}: {d.sum()} edge pixels differ"
-
-
 @pytest.mark.parametrize("N,direction", [(1, "CCW"), (2, "CCW"), (2, "CW"), (3, "CCW")])
 def test_rollout_bit_exact_no_car_contacts(torch_cuda, oracle, N, direction):
     """Physics + tile contacts + rewards + pixels, cars as ghosts for each other (isolates the per-car path)."""
     torch = torch_cuda
     B, seed = 6, 100 + N
-    env = _make(B, N, seed, contacts=False, direction=direction)
+    env = make_env(B, N, seed, contacts=False, direction=direction)
     obs = env.reset().cpu().numpy()
-    orcs = _oracles(oracle, B, N, seed, contacts=False, direction=direction)
-    _assert_state_equal(env, orcs, "after reset"); _assert_pixels(obs, orcs)
+    orcs = oracles(oracle, B, N, seed, contacts=False, direction=direction)
+    assert_state(env, enumerate(orcs), "after reset"); assert_pixels(obs, orcs)
     rng = np.random.RandomState(N)
     for k in range(240):
         a = random_actions(rng, B, N, brake_scale=0.3 if k < 150 else 1.0)
@@ -79,7 +39,7 @@ def test_rollout_bit_exact_no_car_contacts(torch_cuda, oracle, N, direction):
             _, r, d, _ = o.step(a[e], render=(k % 40 == 39))
             assert np.array_equal(r, rw[e]) and bool(dn[e]) == d, f"step {k} env {e}: reward/done differ"
         if k % 40 == 39:
-            _assert_state_equal(env, orcs, f"step {k}"); _assert_pixels(obs.cpu().numpy(), orcs)
+            assert_state(env, enumerate(orcs), f"step {k}"); assert_pixels(obs.cpu().numpy(), orcs)
     env.close()
 
 
@@ -88,10 +48,10 @@ def test_render_options_and_zoom_in(torch_cuda, oracle):
     torch = torch_cuda
     B, N, seed = 4, 2, 5
     kw = dict(h_ratio=0.4, use_ego_color=True, backwards_flag=True)
-    env = _make(B, N, seed, contacts=False, **kw)
+    env = make_env(B, N, seed, contacts=False, **kw)
     obs = env.reset().cpu().numpy()
-    orcs = _oracles(oracle, B, N, seed, contacts=False, **kw)
-    _assert_pixels(obs, orcs, budget=40)
+    orcs = oracles(oracle, B, N, seed, contacts=False, **kw)
+    assert_pixels(obs, orcs, budget=40)
     rng = np.random.RandomState(9)
     for k in range(70):
         a = random_actions(rng, B, N, 0.2)
@@ -100,7 +60,7 @@ def test_render_options_and_zoom_in(torch_cuda, oracle):
         obs, _, _, _ = env.step(torch.from_numpy(a).cuda())
         for e, o in enumerate(orcs):
             o.step(a[e], render=True)
-        _assert_pixels(obs.cpu().numpy(), orcs, budget=40)
+        assert_pixels(obs.cpu().numpy(), orcs, budget=40)
     env.close()
 
 
@@ -108,9 +68,9 @@ def test_backward_flag_and_grass_flags(torch_cuda, oracle):
     """Drive in reverse gear direction: `driving_backward` turns on and the HUD flag appears one step later."""
     torch = torch_cuda
     B, N, seed = 3, 2, 21
-    env = _make(B, N, seed, contacts=False, direction="CW")      # CW: spawned facing "backwards" w.r.t. track beta+pi? exercise both
+    env = make_env(B, N, seed, contacts=False, direction="CW")      # CW: spawned facing "backwards" w.r.t. track beta+pi? exercise both
     env.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=False, direction="CW")
+    orcs = oracles(oracle, B, N, seed, contacts=False, direction="CW")
     rng = np.random.RandomState(2)
     seen_flag = False
     for k in range(120):
@@ -122,7 +82,7 @@ def test_backward_flag_and_grass_flags(torch_cuda, oracle):
             assert np.array_equal(es["driving_backward"][e], eo["driving_backward"]), (k, e)
             assert np.array_equal(es["driving_on_grass"][e], eo["driving_on_grass"]), (k, e)
             seen_flag |= bool(eo["driving_backward"].any())
-        _assert_pixels(obs.cpu().numpy(), orcs, budget=40)          # every frame: the flag shows one step late
+        assert_pixels(obs.cpu().numpy(), orcs, budget=40)          # every frame: the flag shows one step late
     assert seen_flag, "scenario never set driving_backward"
     env.close()
 
@@ -133,8 +93,8 @@ def test_physics_only_mode_matches_oracle(torch_cuda, oracle, streams):
     backward / on-grass bookkeeping the raster kernel owns (:446-495) must be exactly what the full mode computes."""
     torch = torch_cuda
     B, N, seed = 6, 2, 17
-    env = _make(B, N, seed, contacts=True, obs=False, streams=streams); assert env.reset() is None
-    orcs = _oracles(oracle, B, N, seed, contacts=True)
+    env = make_env(B, N, seed, contacts=True, obs=False, streams=streams); assert env.reset() is None
+    orcs = oracles(oracle, B, N, seed, contacts=True)
     rng = np.random.RandomState(6)
     seen = False
     for k in range(110):
@@ -151,7 +111,7 @@ def test_physics_only_mode_matches_oracle(torch_cuda, oracle, streams):
             assert np.array_equal(es["driving_backward"][e], eo["driving_backward"]) and np.array_equal(es["driving_on_grass"][e], eo["driving_on_grass"]), (k, e)
             seen |= bool(eo["driving_backward"].any())
         if k % 36 == 35:
-            _assert_state_equal(env, orcs, f"physics-only step {k}")
+            assert_state(env, enumerate(orcs), f"physics-only step {k}")
     assert seen
     env.close()
 
@@ -160,8 +120,8 @@ def test_out_of_playfield_and_done(torch_cuda, oracle):
     """Teleport a car beyond PLAYFIELD: done and step_reward = -100 (:503-507), identical to the oracle."""
     torch = torch_cuda
     B, N, seed = 2, 2, 3
-    env = _make(B, N, seed, contacts=False); env.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=False)
+    env = make_env(B, N, seed, contacts=False); env.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=False)
     st = env.get_state()["bodies"].copy()
     st[1, 0, :, 0] += 400.0                                           # env 1, car 0: all five bodies +400 in x
     env.set_bodies(st)
@@ -184,8 +144,8 @@ def test_wheel_joints_at_their_limits(torch_cuda, oracle, N):
     joint impulses and limit states against the oracle's scalar Box2D code for 5 x 6 steps, and every limit state must have occurred on a rear joint."""
     torch = torch_cuda
     B, seed = 5, 41 + N
-    env = _make(B, N, seed, contacts=False); env.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=False)
+    env = make_env(B, N, seed, contacts=False); env.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=False)
     rng = np.random.RandomState(7 + N)
     for k in range(12):                                             # get the cars moving first
         a = random_actions(rng, B, N, brake_scale=0.0)
@@ -210,7 +170,7 @@ def test_wheel_joints_at_their_limits(torch_cuda, oracle, N):
             for e, o in enumerate(orcs):
                 _, r, d, _ = o.step(a[e], render=False)
                 assert np.array_equal(r, rew[e].cpu().numpy()) and bool(done[e].item()) == d, f"round {rnd} step {k} env {e}: reward/done differ"
-            _assert_state_equal(env, orcs, f"round {rnd} step {k}")
+            assert_state(env, enumerate(orcs), f"round {rnd} step {k}")
             lim = env.get_state()["limit"]                          # [env, car, joint]: 0 inactive, 1 lower, 2 upper
             seen |= {int(v) for v in np.unique(lim[:, :, 2:])}
     assert {1, 2} <= seen, f"rear joints never sat at both limits: {seen}"
@@ -222,7 +182,7 @@ def test_time_limit_and_auto_reset(torch_cuda, oracle):
     and that episode is the next draw of the env's own RNG streams."""
     torch = torch_cuda
     B, N, seed, L = 4, 2, 40, 30
-    env = _make(B, N, seed, contacts=False, auto_reset=True, max_episode_steps=L, use_random_direction=True)
+    env = make_env(B, N, seed, contacts=False, auto_reset=True, max_episode_steps=L, use_random_direction=True)
     env.reset()
     rng = np.random.RandomState(0)
     ret = np.zeros((B, N))
@@ -240,8 +200,7 @@ def test_time_limit_and_auto_reset(torch_cuda, oracle):
     env.wait_refills()
     # oracle: second episode of every env = second draw of its streams
     for e in range(B):
-        s = (seed + e) % 2 ** 32
-        tr, gr = np.random.RandomState(s), np.random.RandomState((s + 2 ** 31) % 2 ** 32)
+        tr, gr = env_streams(seed, e)
         ep1 = oracle.new_episode(N, tr, gr, use_random_direction=True)
         ep2 = oracle.new_episode(N, tr, gr, use_random_direction=True)
         o = oracle.OracleEnv(N, car_contacts=False); o.reset(ep1, render=False); o2 = o.reset(ep2)     # (the env's second episode on its one world)
@@ -262,12 +221,11 @@ def test_masked_reset_matches_oracle(torch_cuda, oracle):
     first observation; the others keep stepping undisturbed — all bit-exact against per-env oracles."""
     torch = torch_cuda
     B, N, seed = 4, 2, 77
-    env = _make(B, N, seed, contacts=False, auto_reset=True, max_episode_steps=0, use_random_direction=True)
+    env = make_env(B, N, seed, contacts=False, auto_reset=True, max_episode_steps=0, use_random_direction=True)
     env.reset()
     streams, orcs = [], []
     for e in range(B):
-        s = (seed + e) % 2 ** 32
-        tr, gr = np.random.RandomState(s), np.random.RandomState((s + 2 ** 31) % 2 ** 32)
+        tr, gr = env_streams(seed, e)
         o = oracle.OracleEnv(N, car_contacts=False); o.reset(oracle.new_episode(N, tr, gr, use_random_direction=True))
         streams.append((tr, gr)); orcs.append(o)
     rng = np.random.RandomState(3)
@@ -283,7 +241,7 @@ def test_masked_reset_matches_oracle(torch_cuda, oracle):
         o2 = orcs[e].reset(oracle.new_episode(N, *streams[e], use_random_direction=True))
         d = (o2 != obs[e]).any(-1)
         assert (d & (orcs[e].last_amb == 0)).sum() == 0
-    _assert_state_equal(env, orcs, "after masked reset")
+    assert_state(env, enumerate(orcs), "after masked reset")
     for k in range(25):
         a = random_actions(rng, B, N, 0.2)
         obs, rew, _, _ = env.step(torch.from_numpy(a).cuda())
@@ -291,13 +249,13 @@ def test_masked_reset_matches_oracle(torch_cuda, oracle):
         for e, o in enumerate(orcs):
             _, r, _, _ = o.step(a[e], render=(k == 24))
             assert np.array_equal(r, rw[e]), f"step {k} env {e}"
-    _assert_state_equal(env, orcs, "25 steps after masked reset"); _assert_pixels(obs.cpu().numpy(), orcs)
+    assert_state(env, enumerate(orcs), "25 steps after masked reset"); assert_pixels(obs.cpu().numpy(), orcs)
     env.close()
 
 
 def test_device_sincos_bit_exact_with_host_spec(torch_cuda, lib):
     torch = torch_cuda
-    env = _make(1, 1, 0)
+    env = make_env(1, 1, 0)
     rng = np.random.RandomState(3)
     a = np.concatenate([rng.uniform(-100, 100, 200000), rng.uniform(-1, 1, 50000), [0.0, -0.0, np.pi, 1e-30]]).astype(np.float32)
     d = torch.from_numpy(a).cuda(); s = torch.empty_like(d); c = torch.empty_like(d)
@@ -319,7 +277,7 @@ def test_full_size_properties_and_batch_independence(torch_cuda, oracle):
     a B=4 batch (slice independence is what makes multi-GPU sharding exact)."""
     torch = torch_cuda
     N, seed = 2, 7
-    big = _make(4096, N, seed, contacts=False); small = _make(4, N, seed, contacts=False)
+    big = make_env(4096, N, seed, contacts=False); small = make_env(4, N, seed, contacts=False)
     ob = big.reset(); osm = small.reset()
     assert torch.equal(ob[:4], osm)
     g = torch.Generator(device="cuda"); g.manual_seed(0)
@@ -353,8 +311,8 @@ def test_side_stream_is_bit_identical_to_single_stream(torch_cuda, B, N):
     (short TimeLimit) and car<->car contacts must give identical rewards, dones, observations and state in both modes."""
     torch = torch_cuda
     seed = 11
-    a1 = _make(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=120, use_random_direction=True, streams=1)
-    a2 = _make(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=120, use_random_direction=True, streams=2)
+    a1 = make_env(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=120, use_random_direction=True, streams=1)
+    a2 = make_env(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=120, use_random_direction=True, streams=2)
     o1 = a1.reset(); o2 = a2.reset()
     assert torch.equal(o1, o2)
     g = torch.Generator(device="cuda"); g.manual_seed(5)
@@ -391,8 +349,8 @@ def test_a_late_contact_pass_still_reads_the_entry_poses(torch_cuda, lib):
     of hard steering at full gas park moving cars (a build with -DMCR_NO_PARK_WAIT=1 fails here within 70 steps)."""
     torch = torch_cuda
     B, N, seed = 512, 2, 23
-    a1 = _make(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=150, use_random_direction=True, streams=1)
-    a2 = _make(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=150, use_random_direction=True, streams=2)
+    a1 = make_env(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=150, use_random_direction=True, streams=1)
+    a2 = make_env(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=150, use_random_direction=True, streams=2)
     a1.reset(); a2.reset()
     lib.check(a2.L.mcr_debug_set(a2.h, lib.DEBUG_SLOW_COLLIDE))
     g = torch.Generator(device="cuda"); g.manual_seed(9)
@@ -421,12 +379,11 @@ def test_rgb_array_skid_particles_match_oracle(torch_cuda, oracle):
     between (new Car: no particles).  Exact outside the oracle's ambiguity mask at 600x400 and 133x77."""
     torch = torch_cuda
     B, N, seed = 2, 2, 33
-    env = _make(B, N, seed, contacts=True, skid_particles=True, auto_reset=True); env.reset()
-    plain = _make(B, N, seed, contacts=True, auto_reset=True); plain.reset()   # same rollout, particles not tracked
+    env = make_env(B, N, seed, contacts=True, skid_particles=True, auto_reset=True); env.reset()
+    plain = make_env(B, N, seed, contacts=True, auto_reset=True); plain.reset()   # same rollout, particles not tracked
     streams, orcs = [], []
     for e in range(B):
-        sd = (seed + e) % 2 ** 32
-        tr, gr = np.random.RandomState(sd), np.random.RandomState((sd + 2 ** 31) % 2 ** 32)
+        tr, gr = env_streams(seed, e)
         o = oracle.OracleEnv(N, car_contacts=True); o.reset(oracle.new_episode(N, tr, gr, use_random_direction=False))
         streams.append((tr, gr)); orcs.append(o)
     rng = np.random.RandomState(3)
@@ -468,8 +425,8 @@ def test_rgb_array_render_matches_oracle(torch_cuda, oracle):
     mask during the zoom-in, mid-episode, with touched tiles, the backwards flag and ego colours."""
     torch = torch_cuda
     B, N, seed = 2, 3, 21
-    env = _make(B, N, seed, contacts=True, use_ego_color=True, skid_particles=True); env.reset()   # particles: part of rgb_array frames (:564)
-    orcs = _oracles(oracle, B, N, seed, contacts=True, use_ego_color=True)
+    env = make_env(B, N, seed, contacts=True, use_ego_color=True, skid_particles=True); env.reset()   # particles: part of rgb_array frames (:564)
+    orcs = oracles(oracle, B, N, seed, contacts=True, use_ego_color=True)
     rng = np.random.RandomState(12)
     checked = 0
     for k in range(75):
@@ -576,30 +533,15 @@ def test_facade_reset_reset_is_reward_exact_on_one_world(torch_cuda, oracle, N):
     env.close(); o1.close(); o0.close()
 
 
-def _rear_end_setup(env, orcs, gap=5.2):
-    """Put car 1 of every env `gap` behind car 0 (same heading) so that full gas on car 1 + brake on car 0 collide."""
-    st = env.get_state()["bodies"].copy()
-    for e in range(env.B):
-        a = st[e, 0, 0, 2]
-        fwd = np.array([-np.sin(a), np.cos(a)], np.float32)          # hull forward axis
-        delta = (st[e, 0, 0, :2] - fwd * np.float32(gap)) - st[e, 1, 0, :2]
-        st[e, 1, :, 0] += delta[0]; st[e, 1, :, 1] += delta[1]
-        st[e, 1, :, 2] = a
-    env.set_bodies(st)
-    for e, o in enumerate(orcs):
-        for k in range(5):
-            o.set_body(1, k, st[e, 1, k])
-
-
 @pytest.mark.parametrize("N,streams", [(2, 1), (4, 1), (2, 2), (4, 2)])
 def test_car_car_contacts_bit_exact(torch_cuda, oracle, N, streams):
     """Rigid car<->car contacts (b2CollidePolygons + b2ContactSolver + merged islands): rear-end collisions,
     compared bit-exact with the oracle, including warm-started impulses across steps."""
     torch = torch_cuda
     B, seed = 5, 60 + N
-    env = _make(B, N, seed, contacts=True, streams=streams); env.reset()      # streams=2: contact side stream
-    orcs = _oracles(oracle, B, N, seed, contacts=True)
-    _rear_end_setup(env, orcs)
+    env = make_env(B, N, seed, contacts=True, streams=streams); env.reset()      # streams=2: contact side stream
+    orcs = oracles(oracle, B, N, seed, contacts=True)
+    rear_end_setup(env, orcs)
     rng = np.random.RandomState(4)
     touched = 0
     for k in range(160):
@@ -613,9 +555,9 @@ def test_car_car_contacts_bit_exact(torch_cuda, oracle, N, streams):
             touched += o.num_car_contacts()
             assert np.array_equal(r, rw[e]), f"step {k} env {e}"
         if k % 20 == 19:
-            _assert_state_equal(env, orcs, f"contacts step {k}"); _assert_pixels(obs.cpu().numpy(), orcs, budget=40)
+            assert_state(env, enumerate(orcs), f"contacts step {k}"); assert_pixels(obs.cpu().numpy(), orcs, budget=40)
     assert touched > 50, "scenario produced no car<->car contacts"
-    _assert_pixels(obs.cpu().numpy(), orcs, budget=40)
+    assert_pixels(obs.cpu().numpy(), orcs, budget=40)
     env.close()
 
 
@@ -627,9 +569,9 @@ def test_contacts_are_solved_in_island_dfs_order(torch_cuda, oracle, N):
     (an oracle kept in that order beside it sees a different contact order and ends up in a different state)."""
     torch = torch_cuda
     B, seed, steps = 8, 4000 + N, 140
-    env = _make(B, N, seed, contacts=True, use_random_direction=True); env.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=True, use_random_direction=True)
-    legacy = _oracles(oracle, B, N, seed, contacts=True, use_random_direction=True)
+    env = make_env(B, N, seed, contacts=True, use_random_direction=True); env.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=True, use_random_direction=True)
+    legacy = oracles(oracle, B, N, seed, contacts=True, use_random_direction=True)
     for o in legacy: o.set_island_order(0)
     order_differs = joints_differ = 0
     for k in range(steps):
@@ -642,8 +584,8 @@ def test_contacts_are_solved_in_island_dfs_order(torch_cuda, oracle, N):
             _, r, _, _ = o.step(a[e], render=False); l.step(a[e], render=False)
             assert np.array_equal(r, rw[e]), f"step {k} env {e}"
             if o.num_car_contacts() > 0: order_differs += (o.island_diff() >> 1) & 1; joints_differ += o.island_diff() & 1
-        if k % 20 == 19: _assert_state_equal(env, orcs, f"island order step {k}")
-    _assert_state_equal(env, orcs, "island order, end")
+        if k % 20 == 19: assert_state(env, enumerate(orcs), f"island order step {k}")
+    assert_state(env, enumerate(orcs), "island order, end")
     assert order_differs > 10, "the scenario never left the ascending contact order"
     assert joints_differ > 0, "no car was entered through a wheel other than 3 (joint order 3,2,1,0 throughout)"
     assert any(not np.array_equal(o.state()["bodies"], l.state()["bodies"]) for o, l in zip(orcs, legacy)), "the order made no difference"
@@ -657,8 +599,8 @@ def test_driving_policy_pile_ups_bit_exact(torch_cuda, oracle, N):
     of steps, contact chain and main launch side by side (streams=2).  State and rewards bit-exact, every step."""
     torch = torch_cuda
     B, seed, steps = (24 if N < 8 else 16), 7000 + N, 360
-    env = _make(B, N, seed, contacts=True, use_random_direction=True, streams=2); env.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=True, use_random_direction=True)
+    env = make_env(B, N, seed, contacts=True, use_random_direction=True, streams=2); env.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=True, use_random_direction=True)
     rng = np.random.RandomState(N)
     most = 0; contact_steps = 0
     for k in range(steps):
@@ -671,8 +613,8 @@ def test_driving_policy_pile_ups_bit_exact(torch_cuda, oracle, N):
         assert np.array_equal(orw, rew.cpu().numpy()), f"step {k}: envs {np.nonzero((orw != rew.cpu().numpy()).any(1))[0][:8]}"
         nc = [o.num_car_contacts() for o in orcs]
         most = max(most, max(nc)); contact_steps += sum(1 for c in nc if c > 0)
-        if k % 40 == 39: _assert_state_equal(env, orcs, f"pile-up step {k}")
-    _assert_state_equal(env, orcs, "pile-up, end")
+        if k % 40 == 39: assert_state(env, enumerate(orcs), f"pile-up step {k}")
+    assert_state(env, enumerate(orcs), "pile-up, end")
     # (the contact chain's velocity sweeps come in forms for exactly 1, 2, 3, 4 and "any number" of manifolds per env: all of them run here)
     assert contact_steps > 40 and most >= {2: 3, 4: 4, 8: 5}[N], (contact_steps, most)
     env.close()
@@ -683,8 +625,8 @@ def test_random_rollout_with_contacts_enabled(torch_cuda, oracle, streams):
     """Default configuration (contacts on), N=8 crowded start: whatever happens, HIP == oracle."""
     torch = torch_cuda
     B, N, seed = 3, 8, 300
-    env = _make(B, N, seed, contacts=True, streams=streams); env.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=True)
+    env = make_env(B, N, seed, contacts=True, streams=streams); env.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=True)
     rng = np.random.RandomState(8)
     for k in range(150):
         a = random_actions(rng, B, N, 0.1); a[..., 0] *= 1.0
@@ -694,9 +636,9 @@ def test_random_rollout_with_contacts_enabled(torch_cuda, oracle, streams):
             _, r, _, _ = o.step(a[e], render=(k % 30 == 29 or k in (3, 17, 48)))
             assert np.array_equal(r, rew[e].cpu().numpy()), f"step {k} env {e}"
         if k % 30 == 29 or k in (3, 17, 48):                             # all 8 views per env: dense car-car rasterization (k_view_many)
-            _assert_pixels(obs.cpu().numpy(), orcs, budget=40)
+            assert_pixels(obs.cpu().numpy(), orcs, budget=40)
         if k % 30 == 29:
-            _assert_state_equal(env, orcs, f"N=8 step {k}")
+            assert_state(env, enumerate(orcs), f"N=8 step {k}")
     env.close()
 
 
@@ -719,10 +661,10 @@ def test_actions_outside_the_action_space_match_oracle(torch_cuda, oracle, N, co
     them is an accident of np.clip and np.sign, not a behaviour to restate."""
     torch = torch_cuda
     B, seed = 5, 500 + 2 * N + int(contacts)
-    env = _make(B, N, seed, contacts=contacts); env.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=contacts)
+    env = make_env(B, N, seed, contacts=contacts); env.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=contacts)
     if contacts:
-        _rear_end_setup(env, orcs)
+        rear_end_setup(env, orcs)
     rng = np.random.RandomState(seed)
     touched = 0; beyond = np.zeros(3, int)
     for k in range(120):
@@ -738,7 +680,7 @@ def test_actions_outside_the_action_space_match_oracle(torch_cuda, oracle, N, co
             touched += o.num_car_contacts()
             assert np.array_equal(r, rw[e]) and bool(dn[e]) == d, f"step {k} env {e}: reward/done differ (actions {a[e].tolist()})"
         if k % 20 == 19:
-            _assert_state_equal(env, orcs, f"out-of-range actions, step {k}")
+            assert_state(env, enumerate(orcs), f"out-of-range actions, step {k}")
     assert (beyond > 50).all(), beyond
     assert not contacts or touched > 50, "the contact run produced no car<->car contacts"
     env.close()
@@ -750,8 +692,8 @@ def test_side_by_side_cars_take_shared_tiles_in_box2d_order(torch_cuda, oracle):
     gets 1000/T and who the damped share (multi_car_racing.py:113-120).  Rewards are compared exactly, step by step."""
     torch = torch_cuda
     B, N, seed = 8, 2, 410
-    env = _make(B, N, seed, contacts=True); env.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=True)
+    env = make_env(B, N, seed, contacts=True); env.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=True)
     es = env.get_env_state()
     for e, o in enumerate(orcs):
         r = o.env_state()["reward"]
@@ -771,7 +713,7 @@ def test_side_by_side_cars_take_shared_tiles_in_box2d_order(torch_cuda, oracle):
             if (r > 0).all() and r[0] != r[1]:
                 shared_steps += 1                                            # both took a new tile in this step, one of them second
     assert shared_steps > 8, f"only {shared_steps} steps in which both cars took the same new tile"
-    _assert_state_equal(env, orcs, "side by side")
+    assert_state(env, enumerate(orcs), "side by side")
     env.close()
 
 
@@ -779,7 +721,7 @@ def test_status_word_reports_a_starved_contact_pass(torch_cuda, lib):
     """No silent wrong answers: if the main dynamics gives up waiting for the contact pass running beside it (three-chain
     step), the next mcr_step fails with MCR_ERR_STATE (-> McrError) and the handle falls back to the contact pass in front."""
     torch = torch_cuda
-    env = _make(128, 2, 5, contacts=True, streams=2)
+    env = make_env(128, 2, 5, contacts=True, streams=2)
     if not env.L.mcr_concurrent_collide(env.h):
         env.close(); pytest.skip("kernels of different streams do not overlap here: the contact pass already runs in front")
     env.reset()
@@ -808,7 +750,7 @@ def test_device_sensor_predicate_is_box2d_gjk(torch_cuda, oracle, lib):
     far-field filter: >= 1e6 wheel/tile poses whose exact core separation is 0.02 +- 1e-5 (inside the f32 noise of the
     threshold), plus wider bands and clear cases, through the DEVICE predicate (mcr_debug_overlap) and the oracle's GJK
     restatement: zero differences."""
-    env = _make(1, 1, 0)
+    env = make_env(1, 1, 0)
     L = lib.load()
     total = 0
     for n, seed, band in ((1_250_000, 1, 1e-5), (300_000, 2, 1e-3), (150_000, 3, 0.015), (100_000, 4, 0.5)):
@@ -839,7 +781,7 @@ def test_device_sensor_predicate_is_box2d_gjk(torch_cuda, oracle, lib):
 
 def test_synth_actions_device_equals_host_twin(torch_cuda, lib):
     torch = torch_cuda
-    env = _make(37, 3, 0, env_offset=500)
+    env = make_env(37, 3, 0, env_offset=500)
     for t in (0, 1, 999, 2 ** 31 + 5):
         d = env.synth_actions(t, seed=9).cpu().numpy()
         h = np.zeros((37, 3, 3), np.float32)
@@ -857,9 +799,9 @@ def test_state_blob_round_trip_mid_episode(torch_cuda, oracle):
     indices of ANOTHER handle and both continue bit-identically (reward, done, pixels, full state), incl. the oracle."""
     torch = torch_cuda
     B, N, seed = 5, 2, 61
-    src = _make(B, N, seed, contacts=True, max_episode_steps=0); src.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=True)
-    _rear_end_setup(src, orcs)
+    src = make_env(B, N, seed, contacts=True, max_episode_steps=0); src.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=True)
+    rear_end_setup(src, orcs)
     rng = np.random.RandomState(4)
 
     def acts(k):
@@ -871,7 +813,7 @@ def test_state_blob_round_trip_mid_episode(torch_cuda, oracle):
         for e, o in enumerate(orcs):
             o.step(a[e], render=False)
     assert sum(o.num_car_contacts() for o in orcs) > 0, "snapshot should be taken with live car<->car contacts"
-    dst = _make(B + 2, N, 999, contacts=True, max_episode_steps=0); dst.reset()    # different seed: different tracks before restore
+    dst = make_env(B + 2, N, 999, contacts=True, max_episode_steps=0); dst.reset()    # different seed: different tracks before restore
     perm = [3, 0, 4, 1, 2]                                            # src env e -> dst env perm[e] + 1
     for e in range(B):
         blob = src.get_state_blob(e)
@@ -895,7 +837,7 @@ def test_state_blob_round_trip_mid_episode(torch_cuda, oracle):
             assert bool(d1[e].item()) == bool(d2[perm[e] + 1].item()) == d
             assert np.array_equal(o1[e], o2[perm[e] + 1]), f"obs step {k} env {e}"
         if k % 20 == 9:
-            _assert_pixels(o1, orcs, budget=40); _assert_state_equal(src, orcs, f"src step {k}")
+            assert_pixels(o1, orcs, budget=40); assert_state(src, enumerate(orcs), f"src step {k}")
     s1, s2 = src.get_state(), dst.get_state()
     for key in s1:
         for e in range(B):
@@ -908,8 +850,8 @@ def test_step_graph_replay_is_bit_identical(torch_cuda):
     included) gives the same rewards, dones, observations and state as plain launches, across auto-resets."""
     torch = torch_cuda
     B, N, seed = 256, 2, 13
-    a1 = _make(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=60, use_random_direction=True, streams=2, graph=False)
-    a2 = _make(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=60, use_random_direction=True, streams=2, graph=True)
+    a1 = make_env(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=60, use_random_direction=True, streams=2, graph=False)
+    a2 = make_env(B, N, seed, contacts=True, auto_reset=True, max_episode_steps=60, use_random_direction=True, streams=2, graph=True)
     assert torch.equal(a1.reset(), a2.reset())
     for k in range(150):
         a = a1.synth_actions(k, seed=3)
@@ -929,7 +871,7 @@ def test_status_word_reports_a_stalled_stream(torch_cuda, lib):
     posts (debug bit 13 withholds the side stream's "done") must not hang the step or pass unnoticed: the join's wait is bounded,
     the give-up is reported by the next mcr_step, and the handle orders its streams with events from then on."""
     torch = torch_cuda
-    env = _make(128, 2, 6, contacts=True, streams=2)
+    env = make_env(128, 2, 6, contacts=True, streams=2)
     if not (env.L.mcr_step_ordering(env.h) & 1):
         env.close(); pytest.skip("kernels of different streams do not overlap here: the step already uses events")
     env.reset()
@@ -968,10 +910,10 @@ def test_two_handles_on_a_device(torch_cuda, lib):
     torch = torch_cuda
     gc.collect()
     import warnings
-    a_env = _make(256, 2, 9, contacts=True, streams=2)
+    a_env = make_env(256, 2, 9, contacts=True, streams=2)
     with warnings.catch_warnings(record=True) as caught:
         warnings.simplefilter("always")
-        b_env = _make(256, 2, 9, contacts=True, streams=2)
+        b_env = make_env(256, 2, 9, contacts=True, streams=2)
     ob_ = int(b_env.L.mcr_step_ordering(b_env.h))
     if a_env.L.mcr_concurrent_collide(a_env.h):
         assert a_env.L.mcr_step_ordering(a_env.h) & 1
@@ -988,7 +930,7 @@ def test_two_handles_on_a_device(torch_cuda, lib):
         o2, r2, d2, _ = b_env.step(a)
         assert torch.equal(r1, r2) and torch.equal(d1, d2) and torch.equal(o1, o2), k
     # double-buffered: A steps on stream sa while B steps on stream sb; a third handle (one stream) is the reference
-    ref = _make(256, 2, 9, contacts=True, streams=1); ref.reset()
+    ref = make_env(256, 2, 9, contacts=True, streams=1); ref.reset()
     sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
     g2 = torch.Generator(device="cuda"); g2.manual_seed(4)
     acts = []
@@ -1013,7 +955,7 @@ def test_two_handles_on_a_device(torch_cuda, lib):
     for e in (a_env, b_env):
         lib.check(e.L.mcr_status(e.h, lib.ptr(st), 8)); assert not st[:4].any(), st
     a_env.close(); ref.close()
-    c_env = _make(64, 2, 9, contacts=True, streams=2)
+    c_env = make_env(64, 2, 9, contacts=True, streams=2)
     if c_env.L.mcr_concurrent_collide(c_env.h):
         assert c_env.L.mcr_step_ordering(c_env.h) & 1 or c_env.L.mcr_step_ordering(c_env.h) & 4
     c_env.close(); b_env.close()
@@ -1026,8 +968,8 @@ def test_phase_words_beside_a_foreign_stream_that_saturates_the_cus(torch_cuda, 
     import time
     torch = torch_cuda
     B, N, steps = 1024, 2, 400
-    env = _make(B, N, 21, contacts=True, streams=2, auto_reset=True, max_episode_steps=150)
-    ref = _make(B, N, 21, contacts=True, streams=1, auto_reset=True, max_episode_steps=150)
+    env = make_env(B, N, 21, contacts=True, streams=2, auto_reset=True, max_episode_steps=150)
+    ref = make_env(B, N, 21, contacts=True, streams=1, auto_reset=True, max_episode_steps=150)
     env.reset(); ref.reset()
     g = torch.Generator(device="cuda"); g.manual_seed(8)
     acts = []
@@ -1045,7 +987,7 @@ def test_phase_words_beside_a_foreign_stream_that_saturates_the_cus(torch_cuda, 
     if not (env.L.mcr_step_ordering_for(env.h, ctypes.c_void_p(st_main.cuda_stream)) & 1):
         env.close(); ref.close(); pytest.skip("the step uses events here")
     env.close()
-    env = _make(B, N, 21, contacts=True, streams=2, auto_reset=True, max_episode_steps=150); env.reset()
+    env = make_env(B, N, 21, contacts=True, streams=2, auto_reset=True, max_episode_steps=150); env.reset()
     load = torch.cuda.Stream()
     x = torch.randn((8192, 8192), dtype=torch.bfloat16, device="cuda")
     with torch.cuda.stream(load):
@@ -1097,8 +1039,8 @@ def test_a_busy_caller_stream_is_waited_out_not_reported(torch_cuda, lib):
     error, same results as a handle that was not kept waiting."""
     import time
     torch = torch_cuda
-    env = _make(128, 2, 12, contacts=True, streams=2)
-    ref = _make(128, 2, 12, contacts=True, streams=1)
+    env = make_env(128, 2, 12, contacts=True, streams=2)
+    ref = make_env(128, 2, 12, contacts=True, streams=1)
     if not (env.L.mcr_step_ordering(env.h) & 1):
         env.close(); ref.close(); pytest.skip("the step uses events here")
     env.reset(); ref.reset()
@@ -1137,9 +1079,9 @@ def test_switching_between_unfused_and_fused_steps_with_touching_cars(torch_cuda
     mcr_set_step_graph(1) / (0): rewards every step and the whole state bit-exact with the oracle."""
     torch = torch_cuda
     B, N, seed = 6, 2, 9100
-    env = _make(B, N, seed, contacts=True, streams=2); env.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=True)
-    _rear_end_setup(env, orcs)
+    env = make_env(B, N, seed, contacts=True, streams=2); env.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=True)
+    rear_end_setup(env, orcs)
     L = lib.load()
     unbound, bound = torch.cuda.Stream(), torch.cuda.Stream()
     env._bound_streams.add(unbound.cuda_stream)                       # VecMultiCarRacing.step will not hand this one to mcr_bind_stream
@@ -1164,9 +1106,9 @@ def test_switching_between_unfused_and_fused_steps_with_touching_cars(torch_cuda
             touched += o.num_car_contacts()
             assert np.array_equal(r, rw[e]), f"step {k} (phase {phase}) env {e}"
         if k % 14 == 13:
-            torch.cuda.synchronize(); _assert_state_equal(env, orcs, f"mode switches, step {k}")
+            torch.cuda.synchronize(); assert_state(env, enumerate(orcs), f"mode switches, step {k}")
     torch.cuda.synchronize()
-    _assert_state_equal(env, orcs, "mode switches, end")
+    assert_state(env, enumerate(orcs), "mode switches, end")
     assert touched > 100, "the scenario produced too few car<->car contacts"
     assert (0, 0) in modes and (1, 1) in modes, f"the caller never saw both orderings: {modes}"
     assert env.verdict_mismatches() == 0 and env.status_words()[:2].tolist() == [0, 0]
@@ -1179,9 +1121,9 @@ def test_configs0_flags_on_the_hip_path(torch_cuda, oracle):
     drawn; an env beside it with the flag ON differs from it in exactly that triangle."""
     torch = torch_cuda
     B, N, seed = 3, 1, 310
-    env = _make(B, N, seed, contacts=True, backwards_flag=False, use_random_direction=False, direction="CCW"); env.reset()
-    shown = _make(B, N, seed, contacts=True, backwards_flag=True, use_random_direction=False, direction="CCW"); shown.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=True, backwards_flag=False, direction="CCW")
+    env = make_env(B, N, seed, contacts=True, backwards_flag=False, use_random_direction=False, direction="CCW"); env.reset()
+    shown = make_env(B, N, seed, contacts=True, backwards_flag=True, use_random_direction=False, direction="CCW"); shown.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=True, backwards_flag=False, direction="CCW")
     rng = np.random.RandomState(6)
     backward_steps = flag_pixels = 0
     for k in range(150):
@@ -1195,10 +1137,10 @@ def test_configs0_flags_on_the_hip_path(torch_cuda, oracle):
             assert np.array_equal(es["driving_backward"][e], o.env_state()["driving_backward"]), (k, e)
             backward_steps += int(o.env_state()["driving_backward"].any())
         ob = obs.cpu().numpy()
-        _assert_pixels(ob, orcs, budget=40)
+        assert_pixels(ob, orcs, budget=40)
         diff = (ob != obs2.cpu().numpy()).any(-1)                     # [B, N, 96, 96]
         flag_pixels += int(diff.sum())
         assert not diff[:, :, :84].any() and not diff[:, :, :, :84].any(), "the two envs may differ in the flag's pixels only (rows 88..91, columns 87..90)"
-    _assert_state_equal(env, orcs, "configs[0] flags, end")
+    assert_state(env, enumerate(orcs), "configs[0] flags, end")
     assert backward_steps > 20 and flag_pixels > 0, (backward_steps, flag_pixels)
     env.close(); shown.close()

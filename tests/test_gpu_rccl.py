@@ -5,16 +5,13 @@ initialises a 1-rank RCCL group on cuda:0, all-reduces once (so the communicator
 same envs without any process group: results must be bit-identical, the step must still order its streams with phase words and
 no status word may be set."""
 import os
-import socket
 
 import numpy as np
 import pytest
 
+from tests.util import free_port
+
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
 def _actions(k, total, N):
@@ -67,7 +64,7 @@ def test_step_and_metrics_under_a_live_rccl_group():
     total, N, seed, steps = 256, 2, 23, 200
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    p = ctx.Process(target=_worker, args=(_free_port(), total, N, seed, steps, q))
+    p = ctx.Process(target=_worker, args=(free_port(), total, N, seed, steps, q))
     p.start()
     obs, rew, done, m, ordering, status, backend, episodes, ret = q.get(timeout=900)
     p.join(timeout=120)

@@ -2,16 +2,13 @@
 reproduce one full batch bit for bit (obs, reward, done) — the claim that makes the 8-GPU config (BASELINE configs[2])
 exact by construction: env g behaves the same whatever rank owns it."""
 import os
-import socket
 
 import numpy as np
 import pytest
 
+from tests.util import free_port
+
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
 def _actions(k, total, N):
@@ -53,7 +50,7 @@ def test_two_ranks_on_one_gpu_equal_one_full_batch():
     assert torch.cuda.is_available()
     world, total, N, seed, steps, L = 2, 48, 2, 17, 90, 40
     ctx = mp.get_context("spawn")
-    q = ctx.Queue(); port = _free_port()
+    q = ctx.Queue(); port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, world, port, total, N, seed, steps, L, q)) for r in range(world)]
     for p in procs: p.start()
     res = sorted([q.get(timeout=600) for _ in range(world)], key=lambda t: t[0])

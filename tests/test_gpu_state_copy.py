@@ -8,8 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_gpu_parity import _make, _oracles, _rear_end_setup
-from tests.util import random_actions
+from tests.util import make_env, oracles, random_actions, rear_end_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -53,9 +52,9 @@ CASES = {
 def scripted_rollout(torch, case):
     """the env of CASES[case] after its scripted steps, nothing synchronous behind the last one (tools/make_state_blob_golden.py runs the same)"""
     c = CASES[case]; N, B = c["N"], c["B"]
-    env = _make(B, N, 70 + N, contacts=True, **c["kw"]); env.reset()
+    env = make_env(B, N, 70 + N, contacts=True, **c["kw"]); env.reset()
     if c.get("rear"):
-        _rear_end_setup(env, [])
+        rear_end_setup(env, [])
     rng = np.random.RandomState(5)
     for k in range(c["steps"]):
         env.step(torch.from_numpy(_crash_actions(rng, B, N, k) if c.get("rear") else random_actions(rng, B, N, 0.2)).cuda())
@@ -118,16 +117,16 @@ def test_batched_restore_into_another_handle_continues_bit_identically(torch_cud
     permutation of the slots of a handle with another seed and B + 2 envs; both continue bit-identically, and like the oracle."""
     torch = torch_cuda
     B, N, seed = 5, 2, 61
-    src = _make(B, N, seed, contacts=True, max_episode_steps=0, streams=streams); src.reset()
-    orcs = _oracles(oracle, B, N, seed, contacts=True)
-    _rear_end_setup(src, orcs)
+    src = make_env(B, N, seed, contacts=True, max_episode_steps=0, streams=streams); src.reset()
+    orcs = oracles(oracle, B, N, seed, contacts=True)
+    rear_end_setup(src, orcs)
     rng = np.random.RandomState(4)
     for k in range(70):
         a = _crash_actions(rng, B, N, k); src.step(torch.from_numpy(a).cuda())
         for e, o in enumerate(orcs):
             o.step(a[e], render=False)
     assert sum(o.num_car_contacts() for o in orcs) > 0, "snapshot should be taken with live car<->car contacts"
-    dst = _make(B + 2, N, 999, contacts=True, max_episode_steps=0, streams=streams); dst.reset()
+    dst = make_env(B + 2, N, 999, contacts=True, max_episode_steps=0, streams=streams); dst.reset()
     slots = [4, 1, 5, 2, 3]                                            # src env e -> dst env slots[e]
     refused = dst.load_states(src.save_states(), env_ids=slots)
     assert int(refused.item()) == 0
@@ -155,8 +154,8 @@ def test_rewind_reproduces_the_rollout(torch_cuda):
     """save, 40 steps, load, the same 40 actions again: every reward, done flag and frame comes out bit for bit, and so does the state."""
     torch = torch_cuda
     B, N = 8, 2
-    env = _make(B, N, 61, contacts=True, max_episode_steps=0, streams=2); env.reset()
-    _rear_end_setup(env, [])
+    env = make_env(B, N, 61, contacts=True, max_episode_steps=0, streams=2); env.reset()
+    rear_end_setup(env, [])
     rng = np.random.RandomState(4)
     for k in range(45):
         env.step(torch.from_numpy(_crash_actions(rng, B, N, k)).cuda())
@@ -189,9 +188,9 @@ def test_fan_out_clone(torch_cuda, fmt):
     torch = torch_cuda
     B, N = 16, 2
     kw = dict(obs_format="gray", frame_stack=4) if fmt != "rgb" else {}
-    env = _make(B, N, 61, contacts=True, streams=2, state_obs=True, **kw); env.reset()
+    env = make_env(B, N, 61, contacts=True, streams=2, state_obs=True, **kw); env.reset()
     assert not env.auto_reset
-    _rear_end_setup(env, [])
+    rear_end_setup(env, [])
     rng = np.random.RandomState(4)
     k0 = 0
     while k0 < 50 or (k0 < 120 and _contact_counts(env)[:2].min() == 0):    # ~50 steps, and on until both sources' cars touch
@@ -219,7 +218,7 @@ def test_fan_out_clone(torch_cuda, fmt):
 def test_refused_rows_leave_their_envs_untouched(torch_cuda):
     torch = torch_cuda
     B, N = 6, 2
-    env = _make(B, N, 33, contacts=True); env.reset()
+    env = make_env(B, N, 33, contacts=True); env.reset()
     rng = np.random.RandomState(1)
     for k in range(8):
         env.step(torch.from_numpy(random_actions(rng, B, N, 0.2)).cuda())
@@ -250,7 +249,7 @@ def test_refused_rows_leave_their_envs_untouched(torch_cuda):
 def test_arguments(torch_cuda, lib):
     torch = torch_cuda
     B, N = 4, 2
-    env = _make(B, N, 33)
+    env = make_env(B, N, 33)
     L, vp = env.L, ctypes.c_void_p
     buf = torch.zeros((B, env.state_blob_pitch), dtype=torch.uint8, device=env.device)
     ids = torch.arange(B, dtype=torch.int32, device=env.device)
@@ -287,7 +286,7 @@ def test_arguments(torch_cuda, lib):
     with pytest.raises(ValueError):
         env.save_states(out=torch.zeros((B, 16), dtype=torch.uint8, device=env.device))
     env.close()
-    stacked = _make(2, 1, 33, obs_format="gray", frame_stack=4); stacked.reset()
+    stacked = make_env(2, 1, 33, obs_format="gray", frame_stack=4); stacked.reset()
     with pytest.raises(ValueError):
         stacked.load_states(stacked.save_states())
     stacked.close()

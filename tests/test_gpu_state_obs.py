@@ -5,8 +5,7 @@ import numpy as np
 import pytest
 
 from tests import state_obs_ref as R
-from tests.util import oracle_episode, random_actions
-from tests.test_gpu_world import _drive
+from tests.util import Follower, drive_actions, make_env, oracle_episode, random_actions
 
 pytestmark = pytest.mark.gpu
 
@@ -19,10 +18,7 @@ def torch_cuda():
 
 
 def _make(B, N, seed, **kw):
-    from multi_car_racing_amd.vec_env import VecMultiCarRacing
-    kw.setdefault("use_random_direction", False); kw.setdefault("auto_reset", False); kw.setdefault("max_episode_steps", 0)
-    kw.setdefault("streams", 1); kw.setdefault("state_obs", True)
-    return VecMultiCarRacing(B, N, seed=seed, car_contacts=True, async_refill=False, **kw)
+    return make_env(B, N, seed, **{"streams": 1, "state_obs": True, **kw})
 
 
 def _assert_rows(L, got, orcs, eps, what):
@@ -64,22 +60,6 @@ def test_state_bit_exact_vs_oracle(torch_cuda, oracle, lib, N, direction, obs):
         o.close()
 
 
-class _Follower:
-    """oracle of global env g through its episodes: the seeding rule of the vec_env.py docstring, ONE world for the env's life"""
-
-    def __init__(self, O, N, seed, g):
-        s = (seed + g) % 2 ** 32
-        self.O, self.N = O, N
-        self.tr, self.gr = np.random.RandomState(s), np.random.RandomState((s + 2 ** 31) % 2 ** 32)
-        self.o = O.OracleEnv(N)
-        self.new_episode()
-
-    def new_episode(self):
-        self.ep = self.O.new_episode(self.N, self.tr, self.gr, use_random_direction=True)
-        self.o.reset(self.ep, render=False)
-        self.steps = 0
-
-
 def test_state_of_auto_reset_envs_is_the_new_episodes_first(torch_cuda, oracle, lib):
     """B = 64, TimeLimit 40, 100 steps: in the rows where `done` is set the state is the restatement on a fresh oracle reset of the env's NEXT
     episode; the other rows follow the running episode (checked at the end)."""
@@ -88,7 +68,7 @@ def test_state_of_auto_reset_envs_is_the_new_episodes_first(torch_cuda, oracle, 
     B, N, seed, limit = 64, 2, 77, 40
     env = _make(B, N, seed, use_random_direction=True, auto_reset=True, max_episode_steps=limit, obs=False, streams=2)
     env.reset()
-    fol = [_Follower(oracle, N, seed, g) for g in range(B)]
+    fol = [Follower(oracle, N, seed, g, limit, render=False) for g in range(B)]
     _assert_rows(L, env.state.cpu().numpy(), [f.o for f in fol], [f.ep for f in fol], "after reset")
     rng = np.random.RandomState(5)
     ended = 0
@@ -173,7 +153,7 @@ def _touching_policy(torch, gen, B, N, k):
     straight at half throttle.  Pile-ups in EVERY env at once are not used here: the single-stream step packs 64 / G envs on a wavefront that
     share one LDS pool of contact constraints, which then overflows (status word 2, a documented capacity deviation of that path) — and the
     single-stream handle is this test's reference."""
-    a = _drive(torch, gen, B, N, k)
+    a = drive_actions(torch, gen, B, N, k)
     calm = (torch.arange(B, device="cuda") % 8) != 0
     a[calm, :, 0] = 0.0; a[calm, :, 1] = 0.5; a[calm, :, 2] = 0.0
     return a

@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_gpu_benched_config import _Follower, _cmp_pixels
+from tests.util import Follower, assert_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -29,7 +29,7 @@ def _run(torch, O, B, N, seed, steps, max_steps, make_actions, follow, render_ev
                             car_contacts=True, async_refill=True, streams=streams, terminal_obs=True, terminal_cap=cap)
     obs = env.reset()
     idx = np.asarray(follow); idx_t = torch.from_numpy(idx).cuda()
-    fol = [_Follower(O, N, seed, int(g), max_steps) for g in idx]
+    fol = [Follower(O, N, seed, int(g), max_steps) for g in idx]
     pos = {int(g): j for j, g in enumerate(idx)}
     threads = os.cpu_count() or 1
     n_term = n_checked = 0
@@ -56,9 +56,9 @@ def _run(torch, O, B, N, seed, steps, max_steps, make_actions, follow, render_ev
             assert d == dn[f.g], f"step {k} env {f.g}: done {dn[f.g]} vs oracle {d}"
             if d:
                 assert rm[j], f"step {k} env {f.g}: ended without a rendered oracle frame (test set-up)"
-                _cmp_pixels(frames[where[f.g]], o_obs[j], o_amb[j], f"step {k} env {f.g} terminal frame")
+                assert_frame(frames[where[f.g]], o_obs[j], o_amb[j], f"step {k} env {f.g} terminal frame", 14)
                 f.new_episode()
-                _cmp_pixels(got_first[j], f.first_obs, f.first_amb, f"step {k} env {f.g} first frame after auto-reset")
+                assert_frame(got_first[j], f.first_obs, f.first_amb, f"step {k} env {f.g} first frame after auto-reset", 14)
                 n_checked += 1
     frozen = int(env.debug_counters()[3])
     env.close()
@@ -147,7 +147,7 @@ def test_steps_without_terminal_frames_between_terminal_steps(torch_cuda, oracle
     env = VecMultiCarRacing(B, N, seed=seed, use_random_direction=True, auto_reset=True, max_episode_steps=max_steps, car_contacts=True,
                             async_refill=True, streams=2, terminal_obs=True)
     env.reset()
-    fol = [_Follower(oracle, N, seed, g, max_steps) for g in range(B)]
+    fol = [Follower(oracle, N, seed, g, max_steps) for g in range(B)]
     g = torch.Generator(device="cuda"); g.manual_seed(9)
     endings = 0
     for k in range(5 * max_steps + 3):
@@ -165,7 +165,7 @@ def test_steps_without_terminal_frames_between_terminal_steps(torch_cuda, oracle
             d, _ = f.after_step(bool(o_done[j]))
             assert d == dn[j], (k, j)
             if d:
-                _cmp_pixels(frames[where[j]], o_obs[j], o_amb[j], f"step {k} env {j} terminal frame")
+                assert_frame(frames[where[j]], o_obs[j], o_amb[j], f"step {k} env {j} terminal frame", 14)
                 f.new_episode(); ended = True; endings += 1
         if ended or k % 5 == 2:
             # the reference's step(None) (mcr.py:410-431 with action None: no controls, no reward decrement, the world still steps)

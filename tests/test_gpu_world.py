@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_gpu_benched_config import _Follower, _cmp_state
+from tests.util import Follower, assert_state, device_proxy_ids, drive_actions
 
 pytestmark = pytest.mark.gpu
 
@@ -19,26 +19,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return torch
-
-
-def _device_ids(env, lib, g):
-    out = np.zeros(512 + 64, np.int32)
-    n = lib.load().mcr_debug_read_proxy_ids(env.h, int(g), lib.ptr(out), len(out))
-    assert n > 0
-    return out[:n]
-
-
-def _drive(torch, gen, B, N, k, L=84):
-    """a policy that drives INTO its neighbours (bench.py --actions drive plus a bias): gas 1, steering noise +-0.05; in the first 40 steps of
-    an episode of L steps the even cars steer one way and the odd cars the other (the grid's pairs converge in half of the envs), then the
-    even cars brake for 35 steps (whoever is behind runs into them)"""
-    a = torch.zeros((B, N, 3), device="cuda")
-    a[..., 0] = torch.rand((B, N), device="cuda", generator=gen) * 0.1 - 0.05
-    a[..., 1] = 1.0
-    ke = k % L
-    if ke < 40: a[:, ::2, 0] += 0.12; a[:, 1::2, 0] -= 0.12
-    if 40 <= ke < 75: a[:, ::2, 1] = 0.0; a[:, ::2, 2] = 0.9
-    return a
 
 
 @pytest.mark.parametrize("B,N,n_sample,max_steps", [(4096, 2, 14, 84), (512, 8, 7, 84)])
@@ -52,15 +32,15 @@ def test_auto_reset_episodes_on_one_world(torch_cuda, oracle, lib, B, N, n_sampl
                             async_refill=True, streams=2, obs=False)
     env.reset()
     idx = np.sort(np.random.RandomState(seed).choice(B, n_sample, replace=False)); idx_t = torch.from_numpy(idx).cuda()
-    fol = [_Follower(oracle, N, seed, int(g), max_steps) for g in idx]                        # one world per oracle: the reference
+    fol = [Follower(oracle, N, seed, int(g), max_steps) for g in idx]                        # one world per oracle: the reference
     control = N == 2                                                                          # (the negative control doubles the oracle work: one configuration carries it)
-    fresh = [_Follower(oracle, N, seed, int(g), max_steps) for g in idx] if control else []   # rounds 1-5: a fresh world per episode
+    fresh = [Follower(oracle, N, seed, int(g), max_steps) for g in idx] if control else []   # rounds 1-5: a fresh world per episode
     for f in fresh: f.o.set_world_mode(0)
     gen = torch.Generator(device="cuda"); gen.manual_seed(seed)
     thr = os.cpu_count() or 1
     fresh_reward_differs = fresh_state_differs = contacts = ids_not_ascending = 0
     for k in range(episodes * max_steps):
-        a = _drive(torch, gen, B, N, k)
+        a = drive_actions(torch, gen, B, N, k)
         _, rew, done, _ = env.step(a)
         a_s = a[idx_t].cpu().numpy(); rw = rew[idx_t].cpu().numpy(); dn = done[idx_t].cpu().numpy().astype(bool)
         _, _, o_rew, o_done = oracle.step_batch([f.o for f in fol], a_s, None, threads=thr)
@@ -77,7 +57,7 @@ def test_auto_reset_episodes_on_one_world(torch_cuda, oracle, lib, B, N, n_sampl
             contacts += f.o.num_car_contacts() > 0
             if d: ended.append(j)
         if k % 42 == 41 and not ended:
-            _cmp_state(env, fol, idx, f"step {k}")
+            assert_state(env, zip(idx, (f.o for f in fol)), f"step {k}")
             st = env.get_state()["bodies"]
             fresh_state_differs += sum(int(not np.array_equal(st[z.g], z.o.state()["bodies"])) for z in fresh)
         for j in ended:
@@ -85,7 +65,7 @@ def test_auto_reset_episodes_on_one_world(torch_cuda, oracle, lib, B, N, n_sampl
             if control: fresh[j].new_episode()
             tid, fid = fol[j].o.proxy_ids()
             want = np.concatenate([tid, fid.ravel()])
-            got = _device_ids(env, lib, fol[j].g)
+            got = device_proxy_ids(env, lib, fol[j].g)
             assert np.array_equal(got, want), f"step {k} env {fol[j].g}: proxy ids of the new episode: {got[:6]}.. vs the oracle's tree {want[:6]}.."
             ids_not_ascending += int(not np.all(np.diff(want) > 0))
     assert int(env.debug_counters()[3]) == 0 and env.verdict_mismatches() == 0 and env.status_words()[:2].tolist() == [0, 0]
@@ -104,13 +84,13 @@ def test_masked_reset_and_snapshot_keep_the_world(torch_cuda, oracle, lib):
     env = VecMultiCarRacing(B, N, seed=seed, use_random_direction=True, auto_reset=True, max_episode_steps=0, car_contacts=True,
                             async_refill=False, streams=2, obs=False)
     env.reset()
-    fol = [_Follower(oracle, N, seed, g, 0) for g in range(B)]
+    fol = [Follower(oracle, N, seed, g, 0) for g in range(B)]
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
     L = lib.load()
 
     def steps(n, k0):
         for k in range(k0, k0 + n):
-            a = _drive(torch, gen, B, N, k)
+            a = drive_actions(torch, gen, B, N, k)
             _, rew, _, _ = env.step(a)
             _, _, o_rew, _ = oracle.step_batch([f.o for f in fol], a.cpu().numpy(), None, threads=4)
             assert np.array_equal(o_rew, rew.cpu().numpy()), f"step {k}"
@@ -121,19 +101,19 @@ def test_masked_reset_and_snapshot_keep_the_world(torch_cuda, oracle, lib):
         for g in np.nonzero(mask)[0]:
             fol[g].new_episode()
             tid, fid = fol[g].o.proxy_ids()
-            assert np.array_equal(_device_ids(env, lib, g), np.concatenate([tid, fid.ravel()])), f"round {rnd} env {g}"
+            assert np.array_equal(device_proxy_ids(env, lib, g), np.concatenate([tid, fid.ravel()])), f"round {rnd} env {g}"
         steps(40, 40 * (rnd + 1))
-    _cmp_state(env, fol, np.arange(B), "after three masked resets")
+    assert_state(env, zip(np.arange(B), (f.o for f in fol)), "after three masked resets")
     # snapshot env 0, run it through another reset, restore: the world comes back with the blob
     nb = L.mcr_state_blob_bytes(env.h)
     blob = np.zeros(nb, np.uint8)
     assert L.mcr_get_state_blob(env.h, 0, lib.ptr(blob)) == 0
-    ids_before = _device_ids(env, lib, 0).copy()
+    ids_before = device_proxy_ids(env, lib, 0).copy()
     m0 = np.zeros(B, np.uint8); m0[0] = 1
     env.reset_envs(torch.from_numpy(m0).cuda()); env.wait_refills()
-    assert not np.array_equal(_device_ids(env, lib, 0)[:8], ids_before[:8])
+    assert not np.array_equal(device_proxy_ids(env, lib, 0)[:8], ids_before[:8])
     assert L.mcr_set_state_blob(env.h, 0, lib.ptr(blob)) == 0
-    assert np.array_equal(_device_ids(env, lib, 0), ids_before)
+    assert np.array_equal(device_proxy_ids(env, lib, 0), ids_before)
     env.close()
 
 
@@ -147,13 +127,13 @@ def test_fresh_world_switch_is_rounds_1_to_5_definition(torch_cuda, oracle):
     kw = dict(seed=seed, use_random_direction=True, auto_reset=True, max_episode_steps=L, car_contacts=True, async_refill=False, streams=2, obs=False)
     fresh, one = VecMultiCarRacing(B, N, fresh_world=True, **kw), VecMultiCarRacing(B, N, **kw)
     fresh.reset(); one.reset()
-    f0 = [_Follower(oracle, N, seed, g, L) for g in range(B)]
+    f0 = [Follower(oracle, N, seed, g, L) for g in range(B)]
     for f in f0: f.o.set_world_mode(0)
-    f1 = [_Follower(oracle, N, seed, g, L) for g in range(B)]
+    f1 = [Follower(oracle, N, seed, g, L) for g in range(B)]
     gen = torch.Generator(device="cuda"); gen.manual_seed(3)
     handles_differ = 0
     for k in range(3 * L):
-        a = _drive(torch, gen, B, N, k, L)
+        a = drive_actions(torch, gen, B, N, k, L)
         _, r0, d0, _ = fresh.step(a); _, r1, d1, _ = one.step(a)
         an = a.cpu().numpy()
         _, _, o0, od0 = oracle.step_batch([f.o for f in f0], an, None, threads=4)
@@ -166,6 +146,6 @@ def test_fresh_world_switch_is_rounds_1_to_5_definition(torch_cuda, oracle):
             assert e0 == bool(d0[j].item()) and e1 == bool(d1[j].item())
             if e0: f0[j].new_episode()
             if e1: f1[j].new_episode()
-    _cmp_state(fresh, f0, np.arange(B), "fresh-world handle, end"); _cmp_state(one, f1, np.arange(B), "one-world handle, end")
+    assert_state(fresh, zip(np.arange(B), (f.o for f in f0)), "fresh-world handle, end"); assert_state(one, zip(np.arange(B), (f.o for f in f1)), "one-world handle, end")
     assert handles_differ > 0, "the two definitions never disagreed: the rollout did not exercise the ids"
     fresh.close(); one.close()

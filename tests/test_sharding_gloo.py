@@ -1,16 +1,13 @@
 """CPU, world_size 2 over gloo: env slices + the scalar metric all-reduce."""
 import ctypes
 import os
-import socket
 
 import numpy as np
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
+from tests.util import free_port
 
 
 def _worker(rank, world, port, total, N, seed, q):
@@ -37,7 +34,7 @@ def _worker(rank, world, port, total, N, seed, q):
 def test_two_rank_sharding_and_metric_allreduce(lib):
     world, total, N, seed = 2, 9, 2, 31
     ctx = mp.get_context("spawn")
-    q = ctx.Queue(); port = _free_port()
+    q = ctx.Queue(); port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, world, port, total, N, seed, q)) for r in range(world)]
     for p in procs: p.start()
     res = sorted([q.get(timeout=120) for _ in range(world)])

@@ -1,12 +1,23 @@
-"""Shared helpers for the parity tests: build the oracle's episode for the same seeds the product uses."""
+"""The parity suite's shared tools: the oracle's episodes on the seeds the product uses, envs and oracles built alike, the follower of an
+auto-resetting env, and the comparators (tests/test_compare_tools.py holds them to what they must catch).  torch and the package are imported
+inside the functions that need them, so the CPU tests can import this module."""
+import os
+import socket
+
 import numpy as np
+
+STATE_ARRAYS = ("bodies", "joints", "wheels", "limit", "on_road", "sleep")      # get_state() / OracleEnv.state()
+
+
+def env_streams(seed, g):
+    """THE seeding rule (vec_env.py docstring): the RNG streams of global env g — (track stream, global stream: car order and direction)"""
+    s = (seed + g) % 2 ** 32
+    return np.random.RandomState(s), np.random.RandomState((s + 2 ** 31) % 2 ** 32)
 
 
 def oracle_episode(O, N, seed, g, direction="CCW", use_random_direction=False):
-    """Episode of global env index g exactly as VecMultiCarRacing seeds it (vec_env.py docstring)."""
-    s = (seed + g) % 2 ** 32
-    return O.new_episode(N, np.random.RandomState(s), np.random.RandomState((s + 2 ** 31) % 2 ** 32),
-                         direction=direction, use_random_direction=use_random_direction)
+    """Episode of global env index g exactly as VecMultiCarRacing seeds it."""
+    return O.new_episode(N, *env_streams(seed, g), direction=direction, use_random_direction=use_random_direction)
 
 
 def random_actions(rng, B, N, brake_scale=1.0):
@@ -15,6 +26,134 @@ def random_actions(rng, B, N, brake_scale=1.0):
     a[..., 1] = rng.uniform(0, 1, (B, N))
     a[..., 2] = rng.uniform(0, 1, (B, N)) * brake_scale
     return a
+
+
+def drive_actions(torch, gen, B, N, k, L=84):
+    """a policy that drives INTO its neighbours (bench.py --actions drive plus a bias): gas 1, steering noise +-0.05; in the first 40 steps of
+    an episode of L steps the even cars steer one way and the odd cars the other (the grid's pairs converge in half of the envs), then the
+    even cars brake for 35 steps (whoever is behind runs into them)"""
+    a = torch.zeros((B, N, 3), device="cuda")
+    a[..., 0] = torch.rand((B, N), device="cuda", generator=gen) * 0.1 - 0.05
+    a[..., 1] = 1.0
+    ke = k % L
+    if ke < 40: a[:, ::2, 0] += 0.12; a[:, 1::2, 0] -= 0.12
+    if 40 <= ke < 75: a[:, ::2, 1] = 0.0; a[:, ::2, 2] = 0.9
+    return a
+
+
+def luma_np(rgb):
+    """OpenCV's COLOR_RGB2GRAY on 8-bit data (the formula of include/mcr.h)"""
+    x = rgb.astype(np.int64)
+    return ((4899 * x[..., 0] + 9617 * x[..., 1] + 1868 * x[..., 2] + 8192) >> 14).astype(np.uint8)
+
+
+def free_port():
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
+
+
+def device_proxy_ids(env, lib, g):
+    """the broadphase proxy ids of global env g's current episode: tiles, then the cars' fixtures"""
+    out = np.zeros(512 + 64, np.int32)
+    n = lib.load().mcr_debug_read_proxy_ids(env.h, int(g), lib.ptr(out), len(out))
+    assert n > 0
+    return out[:n]
+
+
+# ----------------------------------------------------------------------------------------------------------------- envs and their oracles
+def make_env(B, N, seed, contacts=True, **kw):
+    from multi_car_racing_amd.vec_env import VecMultiCarRacing
+    kw.setdefault("use_random_direction", False); kw.setdefault("auto_reset", False); kw.setdefault("max_episode_steps", 0)
+    kw.setdefault("streams", int(os.environ.get("MCR_TEST_STREAMS", "1")))     # 2: whole suite with the contact side stream
+    return VecMultiCarRacing(B, N, seed=seed, car_contacts=contacts, async_refill=False, **kw)
+
+
+def oracles(O, B, N, seed, contacts=True, **kw):
+    out = []
+    for e in range(B):
+        o = O.OracleEnv(N, car_contacts=contacts, h_ratio=kw.get("h_ratio", 0.25), backwards_flag=kw.get("backwards_flag", True),
+                        use_ego_color=kw.get("use_ego_color", False))
+        o.reset(oracle_episode(O, N, seed, e, direction=kw.get("direction", "CCW"), use_random_direction=kw.get("use_random_direction", False)))
+        out.append(o)
+    return out
+
+
+def rear_end_setup(env, orcs, gap=5.2):
+    """Put car 1 of every env `gap` behind car 0 (same heading) so that full gas on car 1 + brake on car 0 collide."""
+    st = env.get_state()["bodies"].copy()
+    for e in range(env.B):
+        a = st[e, 0, 0, 2]
+        fwd = np.array([-np.sin(a), np.cos(a)], np.float32)          # hull forward axis
+        delta = (st[e, 0, 0, :2] - fwd * np.float32(gap)) - st[e, 1, 0, :2]
+        st[e, 1, :, 0] += delta[0]; st[e, 1, :, 1] += delta[1]
+        st[e, 1, :, 2] = a
+    env.set_bodies(st)
+    for e, o in enumerate(orcs):
+        for k in range(5):
+            o.set_body(1, k, st[e, 1, k])
+
+
+class Follower:
+    """Per-env oracle that follows global env g of a VecMultiCarRacing through its episodes: the env's RNG streams, ONE world for the env's
+    life, TimeLimit counted here (the oracle is the bare env), next episode = next draw.  `ep` is the episode being played; with render,
+    `first_obs` / `first_amb` are its first frame and that frame's ambiguous mask."""
+
+    def __init__(self, O, N, seed, g, max_steps, use_random_direction=True, contacts=True, render=True):
+        self.O, self.N, self.g, self.max_steps, self.urd, self.render = O, N, g, max_steps, use_random_direction, render
+        self.tr, self.gr = env_streams(seed, g)
+        self.o = O.OracleEnv(N, car_contacts=contacts)
+        self.new_episode()
+
+    def new_episode(self):
+        self.ep = self.O.new_episode(self.N, self.tr, self.gr, use_random_direction=self.urd)
+        obs = self.o.reset(self.ep, render=self.render)
+        self.first_obs, self.first_amb = (obs, self.o.last_amb) if self.render else (None, None)
+        self.steps = 0
+
+    def after_step(self, done):
+        """bookkeeping after the batched oracle step: returns (done incl. TimeLimit, truncated)"""
+        self.steps += 1
+        trunc = False
+        if self.max_steps > 0 and self.steps >= self.max_steps:
+            trunc = not done
+            done = True
+        return done, trunc
+
+
+# ----------------------------------------------------------------------------------------------------------------- comparators
+def assert_frame(got, want, amb, what, budget):
+    """frames [views, 96, 96, C] against the oracle's: exact outside its "ambiguous" mask (pixel centres within 0.02 px of a drawn edge, where
+    real GL is implementation-defined too), at most `budget` differing pixels per view in all"""
+    assert want is not None, f"{what}: the oracle step was not rendered"
+    d = (got != want).any(-1)
+    bad = int((d & (amb == 0)).sum())
+    if bad:
+        where = np.argwhere(d & (amb == 0))[:6]
+        detail = "; ".join(f"view {a} row {r} col {c}: got {got[a, r, c].tolist()} want {want[a, r, c].tolist()}" for a, r, c in where)
+        raise AssertionError(f"{what}: {bad} unambiguous pixels differ: {detail}")
+    assert int(d.sum()) <= budget * len(want), f"{what}: {int(d.sum())} edge pixels differ"
+
+
+def assert_pixels(obs, orcs, budget=12):
+    """GPU obs vs the frame each oracle rendered INSIDE its last step/reset (call step(..., render=True))."""
+    for e, o in enumerate(orcs):
+        assert_frame(obs[e], o.last_obs, o.last_amb, f"env {e}", budget)
+
+
+def assert_state(env, pairs, what=""):
+    """the whole state of env index e against oracle o for every (e, o) of `pairs`, BIT-EXACT: the rigid bodies, joints and wheels, the
+    rewards and visit counts, every tile's visited and touched bits, the tile count and the episode clock"""
+    st = env.get_state(); es = env.get_env_state()
+    for e, o in pairs:
+        so = o.state(); eo = o.env_state(); T = o.T
+        for k in STATE_ARRAYS:
+            assert np.array_equal(st[k][e], so[k]), f"{what} env {e}: {k} differs (max abs {np.abs(st[k][e].astype(np.float64) - so[k]).max()})"
+        for k in ("reward", "tile_visited_count"):
+            assert np.array_equal(es[k][e], eo[k]), f"{what} env {e}: {k} {es[k][e].tolist()} vs the oracle's {eo[k].tolist()}"
+        flags = es["tile_flags"][e, :T]
+        assert np.array_equal(flags & 0xff, eo["visited"]), f"{what} env {e}: visited bits of tiles {np.nonzero((flags & 0xff) != eo['visited'])[0][:6].tolist()}"
+        assert np.array_equal((flags >> 8) & 1, eo["touched"]), f"{what} env {e}: touched bit of tiles {np.nonzero(((flags >> 8) & 1) != eo['touched'])[0][:6].tolist()}"
+        assert es["num_tiles"][e] == T, f"{what} env {e}: num_tiles {es['num_tiles'][e]} vs {T}"
+        assert es["t"][e] == eo["t"], f"{what} env {e}: t {es['t'][e]!r} vs the oracle's {eo['t']!r}"
 
 
 # ----------------------------------------------------------------------------------------------------------------- lap scenario
@@ -166,8 +305,7 @@ def lap_run(O, case, trail_car=None, env=None, envs=None):
     N, lap_car, direction, seed, B = LAP_CASES[case]
     orcs, eps, streams = [], [], []
     for e in (range(B) if envs is None else envs):
-        s = (seed + e) % 2 ** 32
-        tr, gr = np.random.RandomState(s), np.random.RandomState((s + 2 ** 31) % 2 ** 32)
+        tr, gr = env_streams(seed, e)
         ep = O.new_episode(N, tr, gr, direction=direction, use_random_direction=False)
         o = O.OracleEnv(N, car_contacts=True); o.reset(ep, render=False)
         orcs.append(o); eps.append(ep); streams.append((tr, gr))
