@@ -221,6 +221,32 @@ int mcr_set_state_obs(mcr_env* h, float* d_state, int waypoints, int stride);
  * when no buffer is set.  Only enqueues: the features read no backward / on-grass flags, so the pending flag scans (mcr_get_env_state's
  * note) are neither launched nor waited for. */
 int mcr_state_obs_now(mcr_env* h, void* stream);
+/* Scripted drivers: cars the DEVICE drives — opponents for a learner, or an expert that labels states (imitation learning, DAgger, a baseline
+ * return).  A stateless track-following controller (csrc/k_driver.h holds the definition and the arithmetic contract): pure pursuit of the
+ * track point L1 tiles ahead of the nearest one for the steering, a target speed that falls with the curvature towards the point L2 tiles
+ * ahead for gas and brake.  An action is a pure function of the env's current state, its episode and the car's parameter row, defined in
+ * IEEE f64 operations in a fixed order and rounded to f32 once: a host reproduces it bit for bit (tests/driver_ref.py), and snapshots,
+ * clones, level pools and sharding need nothing new.  It follows the track on a free road; it does NOT avoid collisions, overtake, or recover
+ * from a spin or from the grass.
+ * A parameter row is MCR_DRV_PARAMS floats: L1, L2 (integers 1..64), v_max (> 0, the speed on a straight), K_s, K_c, K_g, K_b (gains >= 0),
+ * offset (lateral offset of the line, positive = to the right of the episode's driving direction), gas_max, brake_max (in [0, 1]). */
+#define MCR_DRV_PARAMS 10
+#define MCR_DRV_DEFAULTS { 4.0f, 12.0f, 70.0f, 8.0f, 20.0f, 0.2f, 0.1f, 0.0f, 1.0f, 0.8f }
+/* the default row (host [MCR_DRV_PARAMS]); no handle, no GPU needed */
+int mcr_driver_defaults(float* out);
+/* mcr_set_drivers' validation of rows and mask without a handle (no GPU needed): MCR_OK or MCR_ERR_ARG */
+int mcr_check_drivers(int num_agents, const float* params, uint32_t agent_mask);
+/* params: host [num_agents][MCR_DRV_PARAMS], copied; agent_mask: bit a = car a is scripted (0 is legal: expert labels only); d_actions: the
+ * caller's device buffer [B, N, 3] f32 that mcr_driver_actions fills by default.  MCR_ERR_ARG: a NULL handle, rows or buffer, a value out
+ * of range or not finite, mask bits >= num_agents.  May be called again: launches enqueued later use the new rows (they travel with the
+ * launch).  No HIP call, no synchronisation.  The step entry points are unchanged: the filled buffer is simply the d_actions they are given. */
+int mcr_set_drivers(mcr_env* h, const float* params, uint32_t agent_mask, float* d_actions);
+/* One kernel on `stream`, from the CURRENT state: for every car whose bit is set in the mask the controller's action, for every other car a
+ * copy of its row of d_actions_in (zeros if that is NULL; it is only read, and may be the output buffer itself); rows of envs that are not
+ * active (never reset, frozen) are zeros.  agent_mask_override: 0xffffffff = every car, anything else = the registered mask.  d_out: the
+ * buffer to fill, NULL = the registered one.  So "merge the scripted cars into the step's buffer" is (actions, 0, NULL) and "every car's
+ * expert action into a buffer of the caller's" is (NULL, 0xffffffff, buf).  MCR_ERR_STATE without mcr_set_drivers.  Only enqueues. */
+int mcr_driver_actions(mcr_env* h, const float* d_actions_in, uint32_t agent_mask_override, float* d_out, void* stream);
 /* Rollout statistics accumulated on the device since creation / the last reset of the counters (synchronises):
  * out2[0] = episodes finished, out2[1] = sum of their returns over all agents.  These are the per-rank inputs of the
  * job-wide metric all-reduce. */

@@ -11,6 +11,9 @@ QUAD_CAP = 768
 MT_WORDS = 625
 OBS_RGB, OBS_GRAY, OBS_STACK_MAX = 0, 1, 8
 REPEAT_MAX = 16                 # include/mcr.h: MCR_REPEAT_MAX
+DRV_PARAMS = 10                 # include/mcr.h: MCR_DRV_PARAMS, floats per parameter row of a scripted driver
+DRIVER_PARAM_NAMES = ("L1", "L2", "v_max", "K_s", "K_c", "K_g", "K_b", "offset", "gas_max", "brake_max")
+DRIVER_DEFAULTS = dict(zip(DRIVER_PARAM_NAMES, (4.0, 12.0, 70.0, 8.0, 20.0, 0.2, 0.1, 0.0, 1.0, 0.8)))    # include/mcr.h: MCR_DRV_DEFAULTS
 LEVEL_ORDER = {"random": 0, "cycle": 1}      # include/mcr.h: mcr_set_episode_pool's mode
 
 # mcr_debug_set bits: the mirror of enum McrDebugBit (csrc/mcr_kernels.h, which says what each one does; tests/test_abi.py compares the two)
@@ -91,6 +94,10 @@ SYMBOLS = {
     "mcr_state_obs_dim": (_i, [_i, _i]),
     "mcr_set_state_obs": (_i, [_vp, _vp, _i, _i]),
     "mcr_state_obs_now": (_i, [_vp, _vp]),
+    "mcr_driver_defaults": (_i, [_vp]),
+    "mcr_check_drivers": (_i, [_i, _vp, ctypes.c_uint32]),
+    "mcr_set_drivers": (_i, [_vp, _vp, ctypes.c_uint32, _vp]),
+    "mcr_driver_actions": (_i, [_vp, _vp, ctypes.c_uint32, _vp, _vp]),
     "mcr_read_rollout_stats": (_i, [_vp, _vp, _i]),
     "mcr_render": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mcr_debug_read_contact_counts": (_i, [_vp, _vp]),

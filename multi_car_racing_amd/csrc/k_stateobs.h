@@ -31,16 +31,15 @@
 //
 // One wavefront per ENV, not per car: the search needs the T track points (2 x 8 x T bytes, ~5 KB) and all of an env's cars search the same
 // track — a lane keeps its 8 strided tiles in registers (coalesced 8-byte loads, once) and the env's cars take turns on them, so the track is
-// read once per env whatever N is, and "the other cars" of the last feature block are the wavefront's own env.  Per car: f32 distances of
-// the lane's tiles, wave minimum (__shfl_xor), exact f64 on the tiles within the rounding band of it (k_flags.h's band), wave argmin with the
-// lowest index winning, then lane l computes feature l (and l + 64).  No LDS, no scratch: the tile registers are indexed by unrolled constants.
+// read once per env whatever N is, and "the other cars" of the last feature block are the wavefront's own env.  Per car: the search of
+// k_nearest.h (shared with k_driver.h), then lane l computes feature l (and l + 64).  No LDS, no scratch.
 #pragma once
 #include "mcr_kernels.h"
+#include "k_nearest.h"
 
 #define MCR_SO_BASE 18             // features in front of the waypoints
 #define MCR_SO_WAYPOINTS_MAX 16
 #define MCR_SO_STRIDE_MAX 64
-#define MCR_SO_TILES_PER_LANE (MCR_TILE_CAP / 64)
 MCR_HD int mcr_so_dim(int N, int K) { return MCR_SO_BASE + 2 * K + 4 * (N - 1); }
 
 #ifndef MCR_DEVICE_FUNCTIONS_ONLY
@@ -65,13 +64,9 @@ __global__ __launch_bounds__(64) void k_stateobs(McrParams p, McrStateObs so) {
   const McrShapes& S = *p.shapes;
   const V2 lc = v2(S.hull_lcx, S.hull_lcy);
 
-  // the lane's tiles: lane, lane + 64, ..
-  double tx[MCR_SO_TILES_PER_LANE], ty[MCR_SO_TILES_PER_LANE];
-#pragma unroll
-  for (int k = 0; k < MCR_SO_TILES_PER_LANE; ++k) {
-    const int t = lane + 64 * k;
-    tx[k] = t < T ? TX[t] : 0.0; ty[k] = t < T ? TY[t] : 0.0;
-  }
+  // the lane's tiles: lane, lane + 64, .. (k_nearest.h)
+  double tx[MCR_NT_TILES_PER_LANE], ty[MCR_NT_TILES_PER_LANE];
+  mcr_nearest_load(TX, TY, T, lane, tx, ty);
 
   for (int a = 0; a < N; ++a) {
     const int ci = env * N + a;
@@ -79,32 +74,7 @@ __global__ __launch_bounds__(64) void k_stateobs(McrParams p, McrStateObs so) {
     const Xf hxf = xf_of(v2(p.carf[(CF_CX + 0) * BN + ci], p.carf[(CF_CY + 0) * BN + ci]), ha, lc);
     const float fpx = hxf.p.x, fpy = hxf.p.y;
     const double px = (double)fpx, py = (double)fpy;
-    // pass 1: f32 distances, wave minimum
-    float dmin = MCR_MAXFLT;
-#pragma unroll
-    for (int k = 0; k < MCR_SO_TILES_PER_LANE; ++k) {
-      const float ddx = fpx - (float)tx[k], ddy = fpy - (float)ty[k];
-      if (lane + 64 * k < T) dmin = fminf(dmin, ddx * ddx + ddy * ddy);
-    }
-    for (int o = 32; o > 0; o >>= 1) dmin = fminf(dmin, __shfl_xor(dmin, o));
-    // pass 2: exact f64 on the tiles within the f32 error band of the minimum; within a lane the tiles ascend, so `<` keeps the lowest index
-    const float band = sqrtf(dmin) * (1.0f + 1e-5f) + 2e-3f;
-    const float thr = band * band;
-    double bd = 1e300; int bi = 0x7fffffff;
-#pragma unroll
-    for (int k = 0; k < MCR_SO_TILES_PER_LANE; ++k) {
-      const float ddx = fpx - (float)tx[k], ddy = fpy - (float)ty[k];
-      if (lane + 64 * k < T && ddx * ddx + ddy * ddy <= thr) {
-        const double dx = px - tx[k], dy = py - ty[k];
-        const double dd = dx * dx + dy * dy;
-        if (dd < bd) { bd = dd; bi = lane + 64 * k; }
-      }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      const double od = __shfl_xor(bd, o); const int oi = __shfl_xor(bi, o);
-      if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-    }
-    if (bi >= T) bi = 0;                                       // (a non-finite pose: no tile compares; the row stays defined)
+    const int bi = mcr_nearest_tile(tx, ty, T, lane, fpx, fpy);   // (0 for a non-finite pose: no tile compares; the row stays defined)
 
     // the car's own values (the same in every lane)
     const double s = (double)hxf.q.s, c = (double)hxf.q.c;

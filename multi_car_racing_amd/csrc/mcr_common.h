@@ -16,6 +16,7 @@
 #endif
 
 #define MCR_MAX_AGENTS 8
+#define MCR_DRV_PARAMS 10     // include/mcr.h: floats per parameter row of the scripted driver (k_driver.h)
 #define MCR_TILE_CAP 512
 #define MCR_QUAD_CAP 768
 

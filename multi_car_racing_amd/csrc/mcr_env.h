@@ -68,6 +68,9 @@ struct mcr_env {
   bool flags_pending = false; // the last step left the bookkeeping of its main envs (k_flags.h) to its successor (step_phase_words): flags_P launches it
   McrParams flags_P;          // ... the launch's parameters: ROLE_MAIN with that step's partition marks (its parity's part / dpart buffers), no touch verdicts
   McrStateObs so{nullptr, 0, 0, 0};   // mcr_set_state_obs: the low-dimensional observation (k_stateobs.h); out == nullptr: off
+  McrDriver drv{};            // mcr_set_drivers: the scripted driver's parameter rows (k_driver.h) ...
+  float* drv_out = nullptr;   // ... the registered [B][N][3] buffer (nullptr: no drivers, nothing is launched) ...
+  uint32_t drv_mask = 0;      // ... and the cars it drives
   McrPool pool{nullptr, 0, 0, 0, 0, nullptr};   // mcr_set_episode_pool: the device stages the episodes itself (k_pool.h); blobs == nullptr: the host does
 };
 

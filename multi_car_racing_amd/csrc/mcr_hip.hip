@@ -9,6 +9,7 @@
 #include "k_list_chain.h"
 #include "k_render.h"
 #include "k_stateobs.h"
+#include "k_driver.h"
 #include "k_pool.h"
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -817,6 +818,47 @@ extern "C" int mcr_state_obs_now(mcr_env* h, void* stream) {
   if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
   if (!h->so.out) { g_err = "mcr_state_obs_now: no buffer set (mcr_set_state_obs)"; return MCR_ERR_STATE; }
   launch_state_obs(h, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+
+// The scripted driver (k_driver.h).  mcr_set_drivers only validates and stores: no HIP call, no device needed for its argument checks.
+static const float MCR_DRV_DEFAULT_ROW[MCR_DRV_PARAMS] = MCR_DRV_DEFAULTS;
+static const char* drv_check_row(const float* q) {
+  for (int j = 0; j < MCR_DRV_PARAMS; ++j) if (!std::isfinite(q[j])) return "a parameter is not finite";
+  for (int j = 0; j < 2; ++j) if (q[j] < 1.0f || q[j] > (float)MCR_DRV_LOOKAHEAD_MAX || q[j] != (float)(int)q[j]) return "L1, L2 must be integers 1..64";
+  if (!(q[2] > 0.0f)) return "v_max must be > 0";
+  for (int j = 3; j <= 6; ++j) if (q[j] < 0.0f) return "K_s, K_c, K_g, K_b must be >= 0";
+  for (int j = 8; j <= 9; ++j) if (q[j] < 0.0f || q[j] > 1.0f) return "gas_max, brake_max must be in [0, 1]";
+  return nullptr;
+}
+extern "C" int mcr_driver_defaults(float* out) {
+  if (!out) { g_err = "null argument"; return MCR_ERR_ARG; }
+  for (int j = 0; j < MCR_DRV_PARAMS; ++j) out[j] = MCR_DRV_DEFAULT_ROW[j];
+  return MCR_OK;
+}
+extern "C" int mcr_check_drivers(int num_agents, const float* params, uint32_t agent_mask) {
+  if (num_agents < 1 || num_agents > MCR_MAX_AGENTS) { g_err = "drivers: num_agents 1..8"; return MCR_ERR_ARG; }
+  if (!params) { g_err = "drivers: null parameter rows"; return MCR_ERR_ARG; }
+  if (agent_mask >> num_agents) { g_err = "drivers: agent_mask has bits of cars >= num_agents"; return MCR_ERR_ARG; }
+  for (int a = 0; a < num_agents; ++a)
+    if (const char* why = drv_check_row(params + (size_t)a * MCR_DRV_PARAMS)) { g_err = "drivers: car " + std::to_string(a) + ": " + why; return MCR_ERR_ARG; }
+  return MCR_OK;
+}
+extern "C" int mcr_set_drivers(mcr_env* h, const float* params, uint32_t agent_mask, float* d_actions) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!d_actions) { g_err = "mcr_set_drivers: null action buffer"; return MCR_ERR_ARG; }
+  if (int rc = mcr_check_drivers(h->P.N, params, agent_mask)) return rc;
+  for (int a = 0; a < MCR_MAX_AGENTS; ++a)
+    for (int j = 0; j < MCR_DRV_PARAMS; ++j) h->drv.prm[a][j] = a < h->P.N ? params[a * MCR_DRV_PARAMS + j] : MCR_DRV_DEFAULT_ROW[j];
+  h->drv_out = d_actions; h->drv_mask = agent_mask;
+  return MCR_OK;
+}
+extern "C" int mcr_driver_actions(mcr_env* h, const float* d_actions_in, uint32_t agent_mask_override, float* d_out, void* stream) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!h->drv_out) { g_err = "mcr_driver_actions: no drivers set (mcr_set_drivers)"; return MCR_ERR_STATE; }
+  const uint32_t mask = agent_mask_override == 0xffffffffu ? (1u << h->P.N) - 1u : h->drv_mask;
+  hipLaunchKernelGGL(k_driver, dim3(h->P.B), dim3(64), 0, (hipStream_t)stream, h->P, h->drv, d_actions_in, mask, d_out ? d_out : h->drv_out);
   HIPCHK(hipGetLastError());
   return MCR_OK;
 }

@@ -182,6 +182,12 @@ struct McrStateObs {
   int32_t K, stride, F;         // waypoints, tiles between them, features per car
 };
 
+// The scripted driver (k_driver.h): launch argument of k_driver beside McrParams, kept in the handle.  The parameter rows travel BY VALUE with
+// every launch (320 bytes of kernel arguments): a later mcr_set_drivers changes the launches enqueued after it and nothing in flight
+struct McrDriver {
+  float prm[MCR_MAX_AGENTS][MCR_DRV_PARAMS];   // per car: L1, L2, v_max, K_s, K_c, K_g, K_b, offset, gas_max, brake_max
+};
+
 // A level pool (include/mcr.h: mcr_set_episode_pool; k_pool.h): launch argument of k_pool_restage, kept in the handle (null `blobs`: no pool —
 // the host stages the episodes — and nothing is launched)
 struct McrPool {

@@ -34,8 +34,10 @@ class ShardedVecEnv:
     """This rank's slice of a job-wide batch of `total_envs` environments.  Env g (global index) behaves
     identically whatever the world size because its RNG streams are keyed by g (vec_env.py).  Every keyword of
     VecMultiCarRacing passes through (`state_obs`, `state_waypoints`, `state_stride`, `frame_skip`, `levels`, `level_seed`, `level_order`
-    included: every rank makes the same pool, and an env's levels follow its GLOBAL index) and every attribute
-    and method of the slice is reachable here (`state`, `state_shape`, `frame_skip`, `refresh_state()`: this rank's rows)."""
+    included: every rank makes the same pool, and an env's levels follow its GLOBAL index; `scripted_agents`, `driver_params`: the scripted
+    driver is a pure function of an env's state, so a car drives the same whatever rank holds its env) and every attribute
+    and method of the slice is reachable here (`state`, `state_shape`, `frame_skip`, `refresh_state()`, `actions`, `driver_params`,
+    `expert_actions()`: this rank's rows)."""
 
     def __init__(self, total_envs, num_agents=2, seed=0, rank=0, world_size=1, device=None, **kw):
         from .vec_env import VecMultiCarRacing

@@ -67,6 +67,20 @@ plays level levels.pool_level(seed, g, k, K, level_order) in its k-th episode â€
 pool row of each env's CURRENT episode; `self.level_info` the [K, 12] info rows (T, P, retries, cw, car order) of a generated pool, None
 for caller blobs.  Snapshots: clone_envs copies the `level` rows; load_states sets them to -1 (a state blob does not say which level it
 came from); either way the env goes on with its OWN next level when the restored episode ends (the staging words stay the target's).
+
+Scripted drivers: `scripted_agents=(1,)` lets the DEVICE drive the listed cars â€” opponents for a learner, or (all cars) a baseline policy â€”
+with a stateless track-following controller (csrc/k_driver.h holds the definition; `drivers.DRIVER_DEFAULTS` the default parameters;
+`driver_params` overrides them: a dict {name: scalar or per-car sequence} or a float array [N, 10]).  step(actions) then runs one kernel in
+front of the step that writes `self.actions`, a persistent float32 device tensor [B, N, 3]: the controller's action for every scripted car
+(computed from the state BEFORE the step; the caller's rows for those cars are ignored), a copy of the caller's row for every other car.
+The step is driven by that tensor, which is also info["actions"] â€” the actions the step applied; the caller's tensor is never written.
+With `frame_skip=k` the controller is evaluated once per step() call, like the learner's policy (a scripted car sits under the same
+FrameSkip wrapper).  A caller who scripts ALL N cars still passes a [B, N, 3] tensor (its contents are ignored): step(None) stays the
+reference's action-less step for every car, with no driver.  `expert_actions()` returns the controller's action for EVERY car from the
+current state ([B, N, 3], no step, no synchronisation: labels for imitation learning / DAgger); it needs `scripted_agents` or
+`driver_params` (`driver_params={}` = the defaults, no car scripted).  An action is a pure function of the env's state, its episode and
+`self.driver_params` ([N, 10]): snapshots, clones, level pools, sharding and every step path need nothing new.  The controller follows
+the track on a free road; it does not avoid collisions, overtake, or recover from a spin or from the grass.
 """
 import atexit
 import collections
@@ -81,6 +95,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import drivers as _drivers
 
 _DIRECTION_MODE = {"CCW": 0, "CW": 1}
 
@@ -107,7 +122,11 @@ class VecMultiCarRacing:
                  obs=True, auto_reset=True, max_episode_steps=1000, car_contacts=True,
                  gen_threads=None, async_refill=True, streams=None, refill_lag=64, world_size=1, graph=None,
                  skid_particles=False, terminal_obs=False, terminal_cap=None, fresh_world=False, obs_format="rgb", frame_stack=1,
-                 state_obs=False, state_waypoints=6, state_stride=5, frame_skip=1, levels=None, level_seed=None, level_order="random"):
+                 state_obs=False, state_waypoints=6, state_stride=5, frame_skip=1, levels=None, level_seed=None, level_order="random",
+                 scripted_agents=None, driver_params=None):
+        # scripted drivers (module docstring): validated on the host before anything is created
+        drv_mask = _drivers.driver_mask(num_agents, scripted_agents)
+        drv_rows = _drivers.driver_params_array(num_agents, driver_params) if (drv_mask or driver_params is not None) else None
         frame_skip = int(frame_skip)
         if not 1 <= frame_skip <= _lib.REPEAT_MAX:
             raise ValueError(f"frame_skip must be 1..{_lib.REPEAT_MAX}, got {frame_skip}")
@@ -225,6 +244,15 @@ class VecMultiCarRacing:
             self.state = torch.zeros((self.B, self.N, F), dtype=torch.float32, device=self.device)
             self.state_shape = (self.N, F)
             _lib.check(self.L.mcr_set_state_obs(self.h, ctypes.c_void_p(self.state.data_ptr()), int(state_waypoints), int(state_stride)), "mcr_set_state_obs")
+        # scripted drivers (include/mcr.h: mcr_set_drivers): self.actions [B, N, 3] f32 is what step() is driven by when cars are scripted
+        self.driver_params, self.scripted_agents = drv_rows, tuple(a for a in range(self.N) if drv_mask >> a & 1)
+        self._drv_mask = drv_mask
+        self.actions = self._drv_buf = None
+        if drv_rows is not None:
+            self._drv_buf = torch.zeros((self.B, self.N, 3), dtype=torch.float32, device=self.device)
+            if drv_mask:
+                self.actions = self._drv_buf
+            _lib.check(self.L.mcr_set_drivers(self.h, _lib.ptr(drv_rows), ctypes.c_uint32(drv_mask), ctypes.c_void_p(self._drv_buf.data_ptr())), "mcr_set_drivers")
         # RNG streams
         self.mt_track = np.zeros((self.B, _lib.MT_WORDS), np.uint32)
         self.mt_draw = np.zeros((self.B, _lib.MT_WORDS), np.uint32)
@@ -463,7 +491,9 @@ class VecMultiCarRacing:
 
     def step(self, actions):
         """actions: float32 device tensor [B,N,3] (steer, gas, brake) or None. Returns (obs, reward, done, info).
-        With frame_skip=k > 1 one call is a macro-step of up to k env steps per env (module docstring); actions must not be None then."""
+        With frame_skip=k > 1 one call is a macro-step of up to k env steps per env (module docstring); actions must not be None then.
+        With scripted_agents the rows of the scripted cars are replaced by the controller's (info["actions"] = self.actions is what the step
+        applied; `actions` itself is not written); step(None) is the action-less step for every car, scripted or not."""
         if actions is None and self.frame_skip > 1:
             raise ValueError("step(None) needs frame_skip=1: the action-less step belongs to reset()")
         st = torch.cuda.current_stream(self.device)
@@ -493,6 +523,9 @@ class VecMultiCarRacing:
             if actions.numel() != self.B * self.N * 3:
                 raise ValueError(f"actions must have {self.B * self.N * 3} elements, got {actions.numel()}")
             a_ptr = ctypes.c_void_p(actions.data_ptr())
+            if self._drv_mask:        # one kernel in front of the step: the scripted cars' rows from the current state, the others copied
+                _lib.check(self.L.mcr_driver_actions(self.h, a_ptr, ctypes.c_uint32(0), None, ctypes.c_void_p(st.cuda_stream)), "mcr_driver_actions")
+                a_ptr = ctypes.c_void_p(self.actions.data_ptr())
         _lib.check(self.L.mcr_step_repeat(self.h, a_ptr, self.frame_skip, self._obs_ptr(),
                                           ctypes.c_void_p(self.reward.data_ptr()), ctypes.c_void_p(self.done.data_ptr()),
                                           ctypes.c_void_p(self.truncated.data_ptr()), ctypes.c_void_p(st.cuda_stream)), "mcr_step_repeat")
@@ -511,7 +544,24 @@ class VecMultiCarRacing:
             info["state"] = self.state
         if self.level is not None:
             info["level"] = self.level
+        if self._drv_mask and actions is not None:
+            info["actions"] = self.actions
         return self.obs, self.reward, self.done, info
+
+    def expert_actions(self, out=None):
+        """The controller's action for EVERY car from the CURRENT state (include/mcr.h: mcr_driver_actions), float32 [B, N, 3] on the current
+        stream â€” a new tensor, or `out`.  Does not step, does not synchronise, and leaves `self.actions` alone.  Rows of envs that are not
+        active (before reset(), frozen) are zeros.  Needs scripted_agents or driver_params (McrError otherwise)."""
+        if self._drv_buf is None:
+            raise _lib.McrError("created without scripted_agents / driver_params")
+        shape = (self.B, self.N, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif (not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != self.device or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor {list(shape)} on {self.device}")
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_driver_actions(self.h, None, ctypes.c_uint32(0xffffffff), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(st.cuda_stream)), "mcr_driver_actions")
+        return out
 
     def refresh_state(self):
         """Recompute `self.state` from the CURRENT state on the current stream (include/mcr.h: mcr_state_obs_now) â€” after set_bodies() /
