@@ -221,6 +221,31 @@ int mcr_set_state_obs(mcr_env* h, float* d_state, int waypoints, int stride);
  * when no buffer is set.  Only enqueues: the features read no backward / on-grass flags, so the pending flag scans (mcr_get_env_state's
  * note) are neither launched nor waited for. */
 int mcr_state_obs_now(mcr_env* h, void* stream);
+/* Range-finder observations: what racing policies are usually trained on (TORCS's 19-ray `track` and `opponents` sensors, a lidar) — per car
+ * a fan of R rays from the hull's body origin, and per ray two ranges: channel 0 to the track's borders (the two polylines through the road
+ * quads' outer vertices; kerbs are no borders), channel 1 to the hull polygons of the env's other cars.  [B, N, 2, R] f32 in world units,
+ * clamped to max_range, written on the device by a kernel of its own (csrc/k_rangeobs.h, which holds the definition and the arithmetic
+ * contract) wherever the state vector is: after every mcr_reset, mcr_step (once per macro-step) and state restore / copy, on the caller's
+ * stream behind the step, with obs_enabled 0 or 1.  Ray k points along dirs[k][0] forward + dirs[k][1] right in the hull's frame — (cos, sin)
+ * of an angle measured from straight ahead towards the car's right; a direction is not renormalised, a range is the ray parameter.  Every
+ * value is defined in IEEE f64 operations in a fixed order and rounded to f32 once: a host reproduces it bit for bit
+ * (tests/range_obs_ref.py).  Rows of envs that are not active (never reset, frozen) are zeros; an env that re-spawned in the step shows the
+ * first state of its new episode.  With one car channel 1 is max_range.  At a folded inner hairpin the inner border can lie inside the road:
+ * channel 0 is the first border SEGMENT a ray meets. */
+#define MCR_RANGE_RAYS_MAX 32
+/* mcr_set_range_obs' validation of the table, the ray count and the range without a handle (no GPU needed): MCR_OK or MCR_ERR_ARG */
+int mcr_check_range_obs(const float* dirs, int rays, float max_range);
+/* d_ranges: the caller's device buffer [B, N, 2, rays] f32; NULL turns the feature off (the step path then does nothing new; the other
+ * arguments are ignored).  dirs: host [rays][2] f32, copied (it travels with every launch).  MCR_ERR_ARG for a NULL handle, rays outside
+ * 1..MCR_RANGE_RAYS_MAX, NULL dirs, a dirs entry that is not finite, or a max_range that is not finite or <= 0.  Allowed at any time; takes
+ * effect with the next mcr_reset / mcr_step / mcr_range_obs_now.  No HIP call, no synchronisation. */
+int mcr_set_range_obs(mcr_env* h, float* d_ranges, const float* dirs /* [rays][2] host */, int rays, float max_range);
+/* Recompute the tensor from the CURRENT state on `stream` (after mcr_set_bodies / mcr_set_state_blob, which do not; tests).  MCR_ERR_STATE
+ * when no buffer is set.  Only enqueues: the ranges read no backward / on-grass flags. */
+int mcr_range_obs_now(mcr_env* h, void* stream);
+/* the four hull fixture polygons as the kernels hold them (b2PolygonShape::Set's vertex order): out [4][8][2] f32 body-frame vertices,
+ * counts [4]; no handle, no GPU needed (tests pin the host restatement of the range-finder's channel 1 with it) */
+int mcr_hull_polygons(float* out, int32_t* counts);
 /* Scripted drivers: cars the DEVICE drives — opponents for a learner, or an expert that labels states (imitation learning, DAgger, a baseline
  * return).  A stateless track-following controller (csrc/k_driver.h holds the definition and the arithmetic contract): pure pursuit of the
  * track point L1 tiles ahead of the nearest one for the steering, a target speed that falls with the curvature towards the point L2 tiles

@@ -11,6 +11,7 @@ QUAD_CAP = 768
 MT_WORDS = 625
 OBS_RGB, OBS_GRAY, OBS_STACK_MAX = 0, 1, 8
 REPEAT_MAX = 16                 # include/mcr.h: MCR_REPEAT_MAX
+RANGE_RAYS_MAX = 32             # include/mcr.h: MCR_RANGE_RAYS_MAX, rays per car of the range-finder observation
 DRV_PARAMS = 10                 # include/mcr.h: MCR_DRV_PARAMS, floats per parameter row of a scripted driver
 DRIVER_PARAM_NAMES = ("L1", "L2", "v_max", "K_s", "K_c", "K_g", "K_b", "offset", "gas_max", "brake_max")
 DRIVER_DEFAULTS = dict(zip(DRIVER_PARAM_NAMES, (4.0, 12.0, 70.0, 8.0, 20.0, 0.2, 0.1, 0.0, 1.0, 0.8)))    # include/mcr.h: MCR_DRV_DEFAULTS
@@ -94,6 +95,10 @@ SYMBOLS = {
     "mcr_state_obs_dim": (_i, [_i, _i]),
     "mcr_set_state_obs": (_i, [_vp, _vp, _i, _i]),
     "mcr_state_obs_now": (_i, [_vp, _vp]),
+    "mcr_check_range_obs": (_i, [_vp, _i, ctypes.c_float]),
+    "mcr_set_range_obs": (_i, [_vp, _vp, _vp, _i, ctypes.c_float]),
+    "mcr_range_obs_now": (_i, [_vp, _vp]),
+    "mcr_hull_polygons": (_i, [_vp, _vp]),
     "mcr_driver_defaults": (_i, [_vp]),
     "mcr_check_drivers": (_i, [_i, _vp, ctypes.c_uint32]),
     "mcr_set_drivers": (_i, [_vp, _vp, ctypes.c_uint32, _vp]),

@@ -68,6 +68,7 @@ struct mcr_env {
   bool flags_pending = false; // the last step left the bookkeeping of its main envs (k_flags.h) to its successor (step_phase_words): flags_P launches it
   McrParams flags_P;          // ... the launch's parameters: ROLE_MAIN with that step's partition marks (its parity's part / dpart buffers), no touch verdicts
   McrStateObs so{nullptr, 0, 0, 0};   // mcr_set_state_obs: the low-dimensional observation (k_stateobs.h); out == nullptr: off
+  McrRangeObs ro{};           // mcr_set_range_obs: the range-finder observation (k_rangeobs.h); out == nullptr: off
   McrDriver drv{};            // mcr_set_drivers: the scripted driver's parameter rows (k_driver.h) ...
   float* drv_out = nullptr;   // ... the registered [B][N][3] buffer (nullptr: no drivers, nothing is launched) ...
   uint32_t drv_mask = 0;      // ... and the cars it drives
@@ -80,3 +81,4 @@ void flush_flags(mcr_env* h, hipStream_t st);          // launch the bookkeeping
 hipError_t sync_state(mcr_env* h);                     // the device's work complete, that bookkeeping included
 bool capturing(hipStream_t st);
 void launch_state_obs(mcr_env* h, hipStream_t st);     // the state vector of the current state (k_stateobs.h), where the feature is on
+void launch_range_obs(mcr_env* h, hipStream_t st);     // the range-finder tensor of the current state (k_rangeobs.h), where the feature is on

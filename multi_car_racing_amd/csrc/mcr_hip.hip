@@ -9,6 +9,7 @@
 #include "k_list_chain.h"
 #include "k_render.h"
 #include "k_stateobs.h"
+#include "k_rangeobs.h"
 #include "k_driver.h"
 #include "k_pool.h"
 #include <hip/hip_runtime.h>
@@ -345,6 +346,12 @@ static void launch_reset(mcr_env* h, McrParams P, hipStream_t st) {
 void launch_state_obs(mcr_env* h, hipStream_t st) {
   if (!h->so.out) return;
   hipLaunchKernelGGL(k_stateobs, dim3(h->P.B), dim3(64), 0, st, h->P, h->so);
+}
+
+// The range-finder observation (k_rangeobs.h): launched wherever launch_state_obs is, for the same reasons.  Off (no buffer): one test.
+void launch_range_obs(mcr_env* h, hipStream_t st) {
+  if (!h->ro.out) return;
+  hipLaunchKernelGGL(k_rangeobs, dim3(h->P.B), dim3(64), 0, st, h->P, h->ro);
 }
 
 // Level pools (k_pool.h): every env that installed its staged episode gets its next one from the pool.  Launched where launch_state_obs goes — on
@@ -704,6 +711,7 @@ extern "C" int mcr_reset(mcr_env* h, const uint8_t* d_env_mask, uint8_t* d_obs, 
   launch_reset(h, P, st);
   launch_pool_restage(h, st, 1);          // ... and every env that installed gets its next episode: up to B copies, one workgroup per env
   launch_state_obs(h, st);
+  launch_range_obs(h, st);
   HIPCHK(hipGetLastError());
   h->any_reset = true; h->verdict_fresh = false;
   return MCR_OK;
@@ -753,6 +761,7 @@ static int step_one(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* 
       h->step_parity ^= 1;                              // what launch_step does on the host side
       HIPCHK(hipGraphLaunch(G.exec, st));
       launch_state_obs(h, st);
+      launch_range_obs(h, st);
       launch_pool_restage(h, st, MCR_POOL_GROUP);
       HIPCHK(hipGetLastError());
       return MCR_OK;
@@ -766,6 +775,7 @@ static int step_one(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* 
         G.graph = graph; G.P = P; G.st = st; G.view_flags = vf; G.valid = true;
         HIPCHK(hipGraphLaunch(G.exec, st));
         launch_state_obs(h, st);
+        launch_range_obs(h, st);
         launch_pool_restage(h, st, MCR_POOL_GROUP);
         HIPCHK(hipGetLastError());
         return MCR_OK;
@@ -777,7 +787,7 @@ static int step_one(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* 
     h->step_parity = parity_before;
   }
   launch_step(h, P, st, vf);
-  if (last) { launch_state_obs(h, st); launch_pool_restage(h, st, MCR_POOL_GROUP); }
+  if (last) { launch_state_obs(h, st); launch_range_obs(h, st); launch_pool_restage(h, st, MCR_POOL_GROUP); }
   HIPCHK(hipGetLastError());
   return MCR_OK;
 }
@@ -819,6 +829,47 @@ extern "C" int mcr_state_obs_now(mcr_env* h, void* stream) {
   if (!h->so.out) { g_err = "mcr_state_obs_now: no buffer set (mcr_set_state_obs)"; return MCR_ERR_STATE; }
   launch_state_obs(h, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+
+// The range-finder observation (k_rangeobs.h).  mcr_set_range_obs only validates and stores: no HIP call, no device needed for its argument checks.
+extern "C" int mcr_check_range_obs(const float* dirs, int rays, float max_range) {
+  if (rays < 1 || rays > MCR_RANGE_RAYS_MAX) { g_err = "range_obs: rays 1..32"; return MCR_ERR_ARG; }
+  if (!dirs) { g_err = "range_obs: null direction table"; return MCR_ERR_ARG; }
+  for (int i = 0; i < 2 * rays; ++i) if (!std::isfinite(dirs[i])) { g_err = "range_obs: a direction is not finite"; return MCR_ERR_ARG; }
+  if (!std::isfinite(max_range) || !(max_range > 0.0f)) { g_err = "range_obs: max_range must be finite and > 0"; return MCR_ERR_ARG; }
+  return MCR_OK;
+}
+extern "C" int mcr_set_range_obs(mcr_env* h, float* d_ranges, const float* dirs, int rays, float max_range) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!d_ranges) { h->ro.out = nullptr; return MCR_OK; }
+  if (int rc = mcr_check_range_obs(dirs, rays, max_range)) return rc;
+  McrRangeObs ro{};
+  double umax = 0.0;
+  for (int k = 0; k < rays; ++k) {
+    ro.dir[k][0] = dirs[2 * k]; ro.dir[k][1] = dirs[2 * k + 1];
+    umax = fmax(umax, sqrt((double)dirs[2 * k] * (double)dirs[2 * k] + (double)dirs[2 * k + 1] * (double)dirs[2 * k + 1]));
+  }
+  ro.out = d_ranges; ro.R = rays; ro.max_range = max_range;
+  ro.cull = (double)max_range * umax * (1.0 + 1e-6) + 1e-2;
+  h->ro = ro;
+  return MCR_OK;
+}
+extern "C" int mcr_range_obs_now(mcr_env* h, void* stream) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!h->ro.out) { g_err = "mcr_range_obs_now: no buffer set (mcr_set_range_obs)"; return MCR_ERR_STATE; }
+  launch_range_obs(h, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+// the four hull fixture polygons as the kernels hold them (McrShapes::hull): out [4][8][2] f32 body-frame vertices, counts [4]; no handle, no GPU needed
+extern "C" int mcr_hull_polygons(float* out, int32_t* counts) {
+  if (!out || !counts) { g_err = "null argument"; return MCR_ERR_ARG; }
+  McrShapes S; mcr_build_shapes(&S);
+  for (int k = 0; k < 4; ++k) {
+    counts[k] = S.hull[k].n;
+    for (int i = 0; i < 8; ++i) { out[(k * 8 + i) * 2] = S.hull[k].vx[i]; out[(k * 8 + i) * 2 + 1] = S.hull[k].vy[i]; }
+  }
   return MCR_OK;
 }
 

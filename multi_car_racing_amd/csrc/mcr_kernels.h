@@ -182,6 +182,16 @@ struct McrStateObs {
   int32_t K, stride, F;         // waypoints, tiles between them, features per car
 };
 
+// The range-finder observation (k_rangeobs.h): launch argument of k_rangeobs beside McrParams, kept in the handle (null `out`: the feature is off and
+// nothing is launched).  The direction table travels BY VALUE with every launch, as McrDriver's rows do
+struct McrRangeObs {
+  float* out;                   // [B][N][2][R] the caller's device buffer
+  int32_t R;                    // rays per car, 1 .. MCR_RANGE_RAYS_MAX
+  float max_range;
+  double cull;                  // max_range * max_k |dir[k]| * (1 + 1e-6) + 1e-2: a tile farther than this from a car holds no hit (k_rangeobs.h)
+  float dir[MCR_RANGE_RAYS_MAX][2];   // (ck, sk): ray k points along ck forward + sk right
+};
+
 // The scripted driver (k_driver.h): launch argument of k_driver beside McrParams, kept in the handle.  The parameter rows travel BY VALUE with
 // every launch (320 bytes of kernel arguments): a later mcr_set_drivers changes the launches enqueued after it and nothing in flight
 struct McrDriver {

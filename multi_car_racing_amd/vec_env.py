@@ -38,6 +38,17 @@ nearest track point, the episode's direction, `state_waypoints` track points `st
 cars' relative positions and velocities.  The row of an env that auto-reset in the step describes the first state of its new episode, like
 its `obs` row.  After set_bodies() / set_state_blob() call refresh_state().
 
+Range-finder observation: `range_obs=True` adds what racing policies are usually trained on (TORCS's 19-ray `track` and `opponents`
+sensors, F1TENTH's lidar), with `obs=True` or `obs=False`, with or without `state_obs`: `self.ranges`, a persistent float32 device tensor
+[B, N, 2, R], also info["ranges"], that a kernel of its own (csrc/k_rangeobs.h: the definition) rewrites wherever `self.state` is rewritten.
+Per car R rays leave the hull's body origin; channel 0 is the distance along a ray to the track's border (the road's edge; kerbs do not
+count), channel 1 the distance to the nearest other car's HULL (its four polygons, so extent and orientation count), both clamped to
+`range_max` world units (TRACK_WIDTH is 6.67).  The rays are `range_rays` angles np.linspace(-range_fov / 2, range_fov / 2, range_rays) — 0 is
+straight ahead, positive angles lie towards the car's right, a single ray points ahead — or the explicit `range_angles`; `self.range_angles`
+holds them (f64), `self.range_dirs` the float32 (cos, sin) table the kernel is given, `self.range_shape` = (N, 2, R).  With one car channel
+1 is `range_max`.  At a folded inner hairpin the inner border can lie inside the road: channel 0 is the first border segment a ray meets.
+After set_bodies() / set_state_blob() call refresh_ranges().
+
 Action repeat: `frame_skip=k` (1..16) makes step() one MACRO-step, gym's FrameSkip_k(TimeLimit(env)) per env with the auto-reset outside it
 (include/mcr.h: mcr_step_repeat): the same actions drive up to k env steps of every env, an env stops at the step that ends its episode,
 `reward` is the f64 sum of the env steps' rewards in order, `done` their OR, `truncated` the ending step's; `max_episode_steps`,
@@ -85,6 +96,7 @@ the track on a free road; it does not avoid collisions, overtake, or recover fro
 import atexit
 import collections
 import ctypes
+import math
 import weakref
 import os
 import queue
@@ -116,6 +128,32 @@ def _close_all():
 atexit.register(_close_all)
 
 
+def range_obs_table(range_rays=19, range_fov=math.pi, range_angles=None, range_max=100.0):
+    """The rays of the range-finder observation (module docstring), validated on the host: (angles f64 [R], dirs f32 [R, 2] = np.cos / np.sin
+    of the angles cast to float32, max range as a float).  ValueError for a ray count outside 1..32, angles that are not finite or not a
+    1-D sequence, a field of view that is not finite, or a range_max that is not finite or <= 0."""
+    if range_angles is not None:
+        angles = np.array(range_angles, dtype=np.float64)
+        if angles.ndim != 1:
+            raise ValueError("range_angles must be a 1-D sequence of angles")
+    else:
+        if isinstance(range_rays, bool) or not isinstance(range_rays, (int, np.integer)) or not 1 <= int(range_rays) <= _lib.RANGE_RAYS_MAX:
+            raise ValueError(f"range_rays must be an int 1..{_lib.RANGE_RAYS_MAX}, got {range_rays!r}")
+        fov = float(range_fov)
+        if not math.isfinite(fov):
+            raise ValueError(f"range_fov must be finite, got {range_fov!r}")
+        angles = np.linspace(-fov / 2, fov / 2, int(range_rays)) if int(range_rays) > 1 else np.zeros(1, np.float64)
+    if not 1 <= len(angles) <= _lib.RANGE_RAYS_MAX:
+        raise ValueError(f"the range-finder takes 1..{_lib.RANGE_RAYS_MAX} rays, got {len(angles)}")
+    if not np.isfinite(angles).all():
+        raise ValueError("range_angles must be finite")
+    rmax = float(range_max)
+    if not math.isfinite(rmax) or not 0 < rmax <= float(np.finfo(np.float32).max):
+        raise ValueError(f"range_max must be finite and > 0, got {range_max!r}")
+    dirs = np.ascontiguousarray(np.stack([np.cos(angles), np.sin(angles)], axis=1).astype(np.float32))
+    return angles, dirs, rmax
+
+
 class VecMultiCarRacing:
     def __init__(self, num_envs, num_agents=2, device=None, seed=0, env_offset=0, direction="CCW",
                  use_random_direction=True, backwards_flag=True, h_ratio=0.25, use_ego_color=False,
@@ -123,10 +161,12 @@ class VecMultiCarRacing:
                  gen_threads=None, async_refill=True, streams=None, refill_lag=64, world_size=1, graph=None,
                  skid_particles=False, terminal_obs=False, terminal_cap=None, fresh_world=False, obs_format="rgb", frame_stack=1,
                  state_obs=False, state_waypoints=6, state_stride=5, frame_skip=1, levels=None, level_seed=None, level_order="random",
-                 scripted_agents=None, driver_params=None):
+                 scripted_agents=None, driver_params=None, range_obs=False, range_rays=19, range_fov=math.pi, range_angles=None,
+                 range_max=100.0):
         # scripted drivers (module docstring): validated on the host before anything is created
         drv_mask = _drivers.driver_mask(num_agents, scripted_agents)
         drv_rows = _drivers.driver_params_array(num_agents, driver_params) if (drv_mask or driver_params is not None) else None
+        range_table = range_obs_table(range_rays, range_fov, range_angles, range_max) if range_obs else None
         frame_skip = int(frame_skip)
         if not 1 <= frame_skip <= _lib.REPEAT_MAX:
             raise ValueError(f"frame_skip must be 1..{_lib.REPEAT_MAX}, got {frame_skip}")
@@ -244,6 +284,15 @@ class VecMultiCarRacing:
             self.state = torch.zeros((self.B, self.N, F), dtype=torch.float32, device=self.device)
             self.state_shape = (self.N, F)
             _lib.check(self.L.mcr_set_state_obs(self.h, ctypes.c_void_p(self.state.data_ptr()), int(state_waypoints), int(state_stride)), "mcr_set_state_obs")
+        # range-finder observation (include/mcr.h: mcr_set_range_obs): [B, N, 2, R] f32, rewritten where self.state is
+        self.ranges = self.range_shape = self.range_angles = self.range_dirs = self.range_max = None
+        if range_table is not None:
+            self.range_angles, self.range_dirs, self.range_max = range_table
+            R = len(self.range_angles)
+            self.ranges = torch.zeros((self.B, self.N, 2, R), dtype=torch.float32, device=self.device)
+            self.range_shape = (self.N, 2, R)
+            _lib.check(self.L.mcr_set_range_obs(self.h, ctypes.c_void_p(self.ranges.data_ptr()), _lib.ptr(self.range_dirs), R,
+                                                ctypes.c_float(self.range_max)), "mcr_set_range_obs")
         # scripted drivers (include/mcr.h: mcr_set_drivers): self.actions [B, N, 3] f32 is what step() is driven by when cars are scripted
         self.driver_params, self.scripted_agents = drv_rows, tuple(a for a in range(self.N) if drv_mask >> a & 1)
         self._drv_mask = drv_mask
@@ -542,6 +591,8 @@ class VecMultiCarRacing:
             info["terminal_count"] = self.terminal_count
         if self.state is not None:
             info["state"] = self.state
+        if self.ranges is not None:
+            info["ranges"] = self.ranges
         if self.level is not None:
             info["level"] = self.level
         if self._drv_mask and actions is not None:
@@ -571,6 +622,15 @@ class VecMultiCarRacing:
         st = torch.cuda.current_stream(self.device)
         _lib.check(self.L.mcr_state_obs_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_state_obs_now")
         return self.state
+
+    def refresh_ranges(self):
+        """Recompute `self.ranges` from the CURRENT state on the current stream (include/mcr.h: mcr_range_obs_now) — after set_bodies() /
+        set_state_blob(), which do not; reset() and step() keep it current by themselves.  Returns the tensor; does not synchronise."""
+        if self.ranges is None:
+            raise _lib.McrError("created without range_obs=True")
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_range_obs_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_range_obs_now")
+        return self.ranges
 
     def _obs_ptr(self):
         """the observation buffer the raster writes: the frames, or the ring of a stacked format"""
@@ -776,7 +836,7 @@ class VecMultiCarRacing:
     def clone_envs(self, src_ids, dst_ids, check=True):
         """Env dst_ids[i] becomes a copy of env src_ids[i] (a source may be listed many times): the state by one kernel (mcr_copy_states),
         then the rows of obs (the ring of a stacked format), reward, done and truncated, so that the clone is observationally equal at once;
-        `self.state` is rewritten, and with a level pool the `level` rows are copied.  Destinations must be distinct and disjoint from the sources — validated (ValueError) with check=True when
+        `self.state` and `self.ranges` are rewritten, and with a level pool the `level` rows are copied.  Destinations must be distinct and disjoint from the sources — validated (ValueError) with check=True when
         the ids are sequences, the caller's obligation otherwise.  On the current stream; does not synchronise."""
         src, n, src_h = self._env_ids(src_ids, "src_ids")
         dst, m, dst_h = self._env_ids(dst_ids, "dst_ids", distinct=check)
