@@ -10,9 +10,11 @@ LIB = os.path.join(HERE, "_lib", "libmcr_hip.so")
 # box, alternating, threshold 5 / 12 / off: N=2 18.63 / 18.67 / 18.70 M env-steps/s, N=4 12.75 / 12.76 / 13.13, N=8 7.02 / 7.04 / 7.22,
 # --actions drive 5.17 / 5.20 / 5.41 (k_collide 52 / 42 / 42 us, resume chain 72 / 69 / 68 us; the contact chains' scalar sweeps lose their
 # half-packed forms and the register shuffling that came with them).  Same IEEE operations either way (-ffp-contract=off): the parity suite is the proof.
-# mcr_state.hip (state access and snapshots: k_envcopy, k_positions) was part of mcr_hip.hip and keeps its flags.
+# mcr_state.hip (state access and snapshots: k_envcopy, k_positions), mcr_derived.hip (k_stateobs, k_rangeobs, k_driver, k_pool_restage),
+# mcr_refill.hip (host code only) and mcr_debug.hip (debug readers, bench helpers) were parts of mcr_hip.hip and keep its flags.
 HIP_FLAGS = ["-fno-slp-vectorize"] + os.environ.get("MCR_HIP_CFLAGS", "").split()
-SOURCES = [("mcr_hip.hip", HIP_FLAGS), ("mcr_state.hip", HIP_FLAGS), ("mcr_view.hip", ["-fno-slp-vectorize"]), ("mcr_host.cpp", []), ("mcr_world.cpp", [])]
+SOURCES = [("mcr_hip.hip", HIP_FLAGS), ("mcr_state.hip", HIP_FLAGS), ("mcr_derived.hip", HIP_FLAGS), ("mcr_refill.hip", HIP_FLAGS), ("mcr_debug.hip", HIP_FLAGS),
+           ("mcr_view.hip", ["-fno-slp-vectorize"]), ("mcr_host.cpp", []), ("mcr_world.cpp", [])]
 
 
 def deps():

@@ -658,6 +658,7 @@ __device__ __forceinline__ void collide_block(const McrParams& p, const int pass
   }
 }
 
+#ifndef MCR_DEVICE_FUNCTIONS_ONLY
 // one workgroup per env (the list launches call collide_block from k_list_chain.h)
 // (4 wavefronts per SIMD = 16 per CU: with one wavefront per env the 4096 envs of the bench are resident in ONE round; LDS: see lds_bytes)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_collide(McrParams p, int pass) {
@@ -667,3 +668,4 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   }
   collide_block(p, pass, (int)blockIdx.x);
 }
+#endif

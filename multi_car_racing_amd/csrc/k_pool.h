@@ -14,7 +14,7 @@
 // needs neither LDS nor a barrier in front of the copies.  The four wavefronts then copy the flagged envs one after the other, each env's
 // 97,920 bytes as 16-byte loads and stores striding over the 256 lanes, eight loads per lane ahead of their stores (32 KiB in flight per
 // workgroup: what it takes to stream from HBM / the Infinity Cache); no LDS.  After the workgroup barrier lane i of the first wavefront
-// flips env i's flag.  The launch sites pick the group size (mcr_hip.hip: launch_pool_restage):
+// flips env i's flag.  The launch sites pick the group size (mcr_derived.hip: launch_pool_restage):
 //   behind a step    MCR_POOL_GROUP = 16 envs per workgroup: at B = 4096 that is 256 workgroups, one per CU and one round.  The steady state —
 //                    ~B / 1000 envs re-spawn per step — is a launch whose workgroups read 16 words and leave, and a few that copy one slot;
 //                    a step in which EVERY env re-spawns (all envs in phase at the TimeLimit) still has the whole machine copying.

@@ -1,0 +1,146 @@
+// mcr_derived.hip — what the C ABI (include/mcr.h) DERIVES from the state a reset / a restore / a step ended with: the state vector (k_stateobs.h),
+// the range finder (k_rangeobs.h), scripted drivers (k_driver.h), level pools (k_pool.h).  Launched from mcr_hip.hip / mcr_state.hip: mcr_env.h.
+#include "mcr_env.h"
+#include "k_stateobs.h"
+#include "k_rangeobs.h"
+#include "k_driver.h"
+#include "k_pool.h"
+#include <cmath>
+
+// The low-dimensional observation of the state a reset / a step ended with (k_stateobs.h), a wavefront per env on the caller's stream: behind
+// launch_reset / launch_step (whose tail makes `st` wait for the whole step), outside the step's streams and outside a replayed step graph.
+// It reads no flags: nothing is flushed.  Off (no buffer): one test.  The range-finder observation (k_rangeobs.h) goes wherever it goes, for
+// the same reasons, behind it: launch_derived is what mcr_reset, the step's tail and a restore / clone (mcr_state.hip) call.
+static void launch_state_obs(mcr_env* h, hipStream_t st) {
+  if (!h->so.out) return;
+  hipLaunchKernelGGL(k_stateobs, dim3(h->P.B), dim3(64), 0, st, h->P, h->so);
+}
+static void launch_range_obs(mcr_env* h, hipStream_t st) {
+  if (!h->ro.out) return;
+  hipLaunchKernelGGL(k_rangeobs, dim3(h->P.B), dim3(64), 0, st, h->P, h->ro);
+}
+void launch_derived(mcr_env* h, hipStream_t st) { launch_state_obs(h, st); launch_range_obs(h, st); }
+
+// Level pools (k_pool.h): every env that installed its staged episode gets its next one from the pool.  Launched where launch_state_obs goes — on
+// the caller's stream in front of and behind launch_reset and behind the LAST sub-step of a macro-step (a parked env re-spawns only there), whose
+// tail makes `st` wait for the whole step, outside the step's streams and outside a replayed step graph.  Behind the step's tail the terminal
+// frames (mcr_set_terminal_obs), which read the slot an env just left — the slot this kernel overwrites —, are drawn.  No flush_flags: the
+// scans a phase-word step left pending (k_flags.h) read an env's record and its CURRENT slot, and return at once for an env that just
+// re-spawned; the kernel writes staged slots and `staged_ready`, which the scans load with the record and never look at — and they are
+// launched by the NEXT step, behind this kernel in stream order (W_BEGIN is posted by that step's dynamics on `st`).
+void launch_pool_restage(mcr_env* h, hipStream_t st, int envs_per_group) {
+  if (!h->pool.blobs) return;
+  const int B = h->P.B;
+  hipLaunchKernelGGL(k_pool_restage, dim3((B + envs_per_group - 1) / envs_per_group), dim3(MCR_POOL_LANES), 0, st, h->P.env, h->P.slots, B, h->pool, envs_per_group);
+}
+void launch_step_tail(mcr_env* h, hipStream_t st) { launch_derived(h, st); launch_pool_restage(h, st, MCR_POOL_GROUP); }
+
+extern "C" int mcr_state_obs_dim(int num_agents, int waypoints) {
+  if (num_agents < 1 || num_agents > MCR_MAX_AGENTS || waypoints < 0 || waypoints > MCR_SO_WAYPOINTS_MAX) { g_err = "mcr_state_obs_dim: num_agents 1..8, waypoints 0..16"; return MCR_ERR_ARG; }
+  return mcr_so_dim(num_agents, waypoints);
+}
+extern "C" int mcr_set_state_obs(mcr_env* h, float* d_state, int waypoints, int stride) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (waypoints < 0 || waypoints > MCR_SO_WAYPOINTS_MAX || stride < 1 || stride > MCR_SO_STRIDE_MAX) { g_err = "mcr_set_state_obs: waypoints 0..16, stride 1..64"; return MCR_ERR_ARG; }
+  h->so.out = d_state; h->so.K = waypoints; h->so.stride = stride; h->so.F = mcr_so_dim(h->P.N, waypoints);
+  return MCR_OK;
+}
+extern "C" int mcr_state_obs_now(mcr_env* h, void* stream) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!h->so.out) { g_err = "mcr_state_obs_now: no buffer set (mcr_set_state_obs)"; return MCR_ERR_STATE; }
+  launch_state_obs(h, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+
+// The range-finder observation (k_rangeobs.h).  mcr_set_range_obs only validates and stores: no HIP call, no device needed for its argument checks.
+extern "C" int mcr_check_range_obs(const float* dirs, int rays, float max_range) {
+  if (rays < 1 || rays > MCR_RANGE_RAYS_MAX) { g_err = "range_obs: rays 1..32"; return MCR_ERR_ARG; }
+  if (!dirs) { g_err = "range_obs: null direction table"; return MCR_ERR_ARG; }
+  for (int i = 0; i < 2 * rays; ++i) if (!std::isfinite(dirs[i])) { g_err = "range_obs: a direction is not finite"; return MCR_ERR_ARG; }
+  if (!std::isfinite(max_range) || !(max_range > 0.0f)) { g_err = "range_obs: max_range must be finite and > 0"; return MCR_ERR_ARG; }
+  return MCR_OK;
+}
+extern "C" int mcr_set_range_obs(mcr_env* h, float* d_ranges, const float* dirs, int rays, float max_range) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!d_ranges) { h->ro.out = nullptr; return MCR_OK; }
+  if (int rc = mcr_check_range_obs(dirs, rays, max_range)) return rc;
+  McrRangeObs ro{};
+  double umax = 0.0;
+  for (int k = 0; k < rays; ++k) {
+    ro.dir[k][0] = dirs[2 * k]; ro.dir[k][1] = dirs[2 * k + 1];
+    umax = fmax(umax, sqrt((double)dirs[2 * k] * (double)dirs[2 * k] + (double)dirs[2 * k + 1] * (double)dirs[2 * k + 1]));
+  }
+  ro.out = d_ranges; ro.R = rays; ro.max_range = max_range;
+  ro.cull = (double)max_range * umax * (1.0 + 1e-6) + 1e-2;
+  h->ro = ro;
+  return MCR_OK;
+}
+extern "C" int mcr_range_obs_now(mcr_env* h, void* stream) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!h->ro.out) { g_err = "mcr_range_obs_now: no buffer set (mcr_set_range_obs)"; return MCR_ERR_STATE; }
+  launch_range_obs(h, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+// the four hull fixture polygons as the kernels hold them (McrShapes::hull): out [4][8][2] f32 body-frame vertices, counts [4]; no handle, no GPU needed
+extern "C" int mcr_hull_polygons(float* out, int32_t* counts) {
+  if (!out || !counts) { g_err = "null argument"; return MCR_ERR_ARG; }
+  McrShapes S; mcr_build_shapes(&S);
+  for (int k = 0; k < 4; ++k) {
+    counts[k] = S.hull[k].n;
+    for (int i = 0; i < 8; ++i) { out[(k * 8 + i) * 2] = S.hull[k].vx[i]; out[(k * 8 + i) * 2 + 1] = S.hull[k].vy[i]; }
+  }
+  return MCR_OK;
+}
+
+// The scripted driver (k_driver.h).  mcr_set_drivers only validates and stores: no HIP call, no device needed for its argument checks.
+static const float MCR_DRV_DEFAULT_ROW[MCR_DRV_PARAMS] = MCR_DRV_DEFAULTS;
+static const char* drv_check_row(const float* q) {
+  for (int j = 0; j < MCR_DRV_PARAMS; ++j) if (!std::isfinite(q[j])) return "a parameter is not finite";
+  for (int j = 0; j < 2; ++j) if (q[j] < 1.0f || q[j] > (float)MCR_DRV_LOOKAHEAD_MAX || q[j] != (float)(int)q[j]) return "L1, L2 must be integers 1..64";
+  if (!(q[2] > 0.0f)) return "v_max must be > 0";
+  for (int j = 3; j <= 6; ++j) if (q[j] < 0.0f) return "K_s, K_c, K_g, K_b must be >= 0";
+  for (int j = 8; j <= 9; ++j) if (q[j] < 0.0f || q[j] > 1.0f) return "gas_max, brake_max must be in [0, 1]";
+  return nullptr;
+}
+extern "C" int mcr_driver_defaults(float* out) {
+  if (!out) { g_err = "null argument"; return MCR_ERR_ARG; }
+  for (int j = 0; j < MCR_DRV_PARAMS; ++j) out[j] = MCR_DRV_DEFAULT_ROW[j];
+  return MCR_OK;
+}
+extern "C" int mcr_check_drivers(int num_agents, const float* params, uint32_t agent_mask) {
+  if (num_agents < 1 || num_agents > MCR_MAX_AGENTS) { g_err = "drivers: num_agents 1..8"; return MCR_ERR_ARG; }
+  if (!params) { g_err = "drivers: null parameter rows"; return MCR_ERR_ARG; }
+  if (agent_mask >> num_agents) { g_err = "drivers: agent_mask has bits of cars >= num_agents"; return MCR_ERR_ARG; }
+  for (int a = 0; a < num_agents; ++a)
+    if (const char* why = drv_check_row(params + (size_t)a * MCR_DRV_PARAMS)) { g_err = "drivers: car " + std::to_string(a) + ": " + why; return MCR_ERR_ARG; }
+  return MCR_OK;
+}
+extern "C" int mcr_set_drivers(mcr_env* h, const float* params, uint32_t agent_mask, float* d_actions) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!d_actions) { g_err = "mcr_set_drivers: null action buffer"; return MCR_ERR_ARG; }
+  if (int rc = mcr_check_drivers(h->P.N, params, agent_mask)) return rc;
+  for (int a = 0; a < MCR_MAX_AGENTS; ++a)
+    for (int j = 0; j < MCR_DRV_PARAMS; ++j) h->drv.prm[a][j] = a < h->P.N ? params[a * MCR_DRV_PARAMS + j] : MCR_DRV_DEFAULT_ROW[j];
+  h->drv_out = d_actions; h->drv_mask = agent_mask;
+  return MCR_OK;
+}
+extern "C" int mcr_driver_actions(mcr_env* h, const float* d_actions_in, uint32_t agent_mask_override, float* d_out, void* stream) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!h->drv_out) { g_err = "mcr_driver_actions: no drivers set (mcr_set_drivers)"; return MCR_ERR_STATE; }
+  const uint32_t mask = agent_mask_override == 0xffffffffu ? (1u << h->P.N) - 1u : h->drv_mask;
+  hipLaunchKernelGGL(k_driver, dim3(h->P.B), dim3(64), 0, (hipStream_t)stream, h->P, h->drv, d_actions_in, mask, d_out ? d_out : h->drv_out);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+
+extern "C" int mcr_set_episode_pool(mcr_env* h, const void* d_pool, int K, uint64_t seed, uint32_t env_offset, int mode, int32_t* d_level) {
+  if (!h || !d_pool) { g_err = "mcr_set_episode_pool: null argument"; return MCR_ERR_ARG; }
+  if (K < 1 || ((uintptr_t)d_pool & 15u) || (mode != 0 && mode != 1)) { g_err = "mcr_set_episode_pool: K >= 1 rows, a 16-byte aligned pool, mode 0 (random) or 1 (cycle)"; return MCR_ERR_ARG; }
+  // (the staged slots have ONE owner for the life of the handle: a pool set later would meet episodes the host staged and counters it polls)
+  if (h->any_reset) { g_err = "mcr_set_episode_pool after the first mcr_reset"; return MCR_ERR_STATE; }
+  if (h->svc) { g_err = "mcr_set_episode_pool: the refill service is running"; return MCR_ERR_STATE; }
+  h->pool.blobs = (const uint8_t*)d_pool; h->pool.K = K; h->pool.mode = mode; h->pool.seed = seed; h->pool.env_offset = env_offset; h->pool.level = d_level;
+  return MCR_OK;
+}

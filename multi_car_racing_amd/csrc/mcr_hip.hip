@@ -1,5 +1,6 @@
-// mcr_hip.hip — C-ABI implementation (include/mcr.h) over the gfx950 kernels.
-// One handle owns one env slice on one device: SoA car state, per-env state, two episode slots per env.
+// mcr_hip.hip — the core of the C ABI (include/mcr.h) over the gfx950 kernels: handle creation and the stream-ordering probe, reset, the three
+// step paths, episode staging, the observation-format / terminal-obs / graph setters, render.  One handle owns one env slice on one device:
+// SoA car state, per-env state, two episode slots per env.  The other units of the ABI and what they share with this one: mcr_env.h.
 #include "mcr_env.h"
 #include "k_dynamics.h"
 #include "k_collide.h"
@@ -8,19 +9,9 @@
 #include "k_viewprep.h"
 #include "k_list_chain.h"
 #include "k_render.h"
-#include "k_stateobs.h"
-#include "k_rangeobs.h"
-#include "k_driver.h"
-#include "k_pool.h"
-#include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
-#include <string>
-#include <vector>
 #include <cstring>
-#include <cstdio>
 #include <cstdlib>
-
-void mcr_build_shapes(McrShapes* S);   // mcr_host.cpp
 
 thread_local std::string g_err;
 extern "C" const char* mcr_last_error(void) { return g_err.c_str(); }
@@ -82,7 +73,7 @@ static void select_step_ordering(mcr_env* h) {
   if (hipStreamCreateWithPriority(&h->s_side, hipStreamNonBlocking, prio_hi) != hipSuccess) { (void)hipGetLastError(); return; }
   // (the priority of the third stream — it carries the main raster, whose backlog of workgroups competes with the list raster at the
   // tail of the caller's stream for every LDS slot that frees up — makes no difference: high / normal / low 14.73 / 14.72 / 14.72 M)
-  if (hipStreamCreateWithPriority(&h->s_defer, hipStreamNonBlocking, prio_hi) != hipSuccess) { (void)hipStreamDestroy(h->s_side); (void)hipGetLastError(); return; }
+  if (hipStreamCreateWithPriority(&h->s_defer, hipStreamNonBlocking, prio_hi) != hipSuccess) { (void)hipStreamDestroy(h->s_side); h->s_side = nullptr; (void)hipGetLastError(); return; }
   const unsigned evf = hipEventDisableTiming;     // (hipEventReleaseToDevice changes nothing measurable: tools/ubench/event_gap.hip)
   for (hipEvent_t* e : {&h->ev_fork, &h->ev_join, &h->ev_fork2, &h->ev_join2, &h->ev_col}) (void)hipEventCreateWithFlags(e, evf);
   h->soft_sync = kernels_overlap(h->s_defer, h->s_side);     // (a waiting kernel needs the kernels it waits for to run beside it)
@@ -115,13 +106,26 @@ static void select_step_ordering(mcr_env* h) {
   (void)hipGetLastError();
 }
 
+// What a handle owns, given back in mcr_destroy's order — graphs, events, streams, memory — and the handle itself.  Tolerates a partly built
+// one (mcr_create's error paths): whatever is still null was never made.
+static void release_env(mcr_env* h) {
+  for (auto& g : h->sg) if (g.valid) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); g.valid = false; }
+  for (auto& t : h->pending) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
+  for (auto e : h->free_events) (void)hipEventDestroy(e);
+  for (hipStream_t st : {h->s_side, h->s_defer}) if (st) (void)hipStreamDestroy(st);
+  for (hipEvent_t e : {h->ev_fork, h->ev_join, h->ev_fork2, h->ev_join2, h->ev_col}) if (e) (void)hipEventDestroy(e);
+  for (void* d : {h->slab, h->term_slab, (void*)h->ring.fresh}) if (d) (void)hipFree(d);
+  for (void* m : {(void*)h->consumed_host, (void*)h->status_host}) if (m) (void)hipHostFree(m);
+  delete[] h->consumed_seen;
+  delete h;
+}
+
 extern "C" int mcr_create(const mcr_config* cfg, mcr_env** out) {
   if (!cfg || !out) { g_err = "null argument"; return MCR_ERR_ARG; }
   if (cfg->num_envs < 1 || cfg->num_envs > MCR_VORDER_ENV_MASK || cfg->num_agents < 1 || cfg->num_agents > MCR_MAX_AGENTS) { g_err = "num_envs/num_agents out of range"; return MCR_ERR_ARG; }
   HIPCHK(hipSetDevice(cfg->device));
   mcr_env* h = new mcr_env();
-  h->cfg = *cfg; h->timing = 0; h->any_reset = false; h->use_graph = 0; h->verdict_fresh = false; h->concurrent_collide = false; for (auto& g : h->sg) g.valid = false;
-  h->vorder_dirty[0] = h->vorder_dirty[1] = false;
+  h->cfg = *cfg;
   // A list chain is a serial solver chain per wavefront (2 envs each).  With i.i.d. random actions and two cars per env the
   // contact list holds ~15 envs of 4096, but a policy that actually drives (or N = 8: ~340 envs) fills it with hundreds, and
   // every further round of the walk adds a whole chain (~300 us) to the side stream: the grid covers 1024 envs in one round;
@@ -129,9 +133,7 @@ extern "C" int mcr_create(const mcr_config* cfg, mcr_env** out) {
   h->chain_grid = 4 * MCR_LIST_GRID;
   h->viewprep_in_flags = cfg->num_agents <= 3;     // beyond three cars per env the bookkeeping + raster chain is the step's critical path: the epilogue stays in the dynamics (round 3, phase-word path: N = 3 13.4 -> 13.7 M with it, N = 4 10.8 -> 10.6, N = 8 no difference)
   h->list_view_grid = cfg->num_agents <= 2 ? MCR_LIST_GRID : 8 * MCR_LIST_GRID;
-  h->status_host = nullptr; h->step_count = 0; h->bp_fresh = false; memset(h->status_seen, 0, sizeof(h->status_seen));
   { hipDeviceProp_t prop; h->simd_count = (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess ? prop.multiProcessorCount : 256) * 4; }
-  for (int i = 0; i < MCR_TIMING_SLOTS; ++i) { h->t_ms[i] = 0; h->t_n[i] = 0; }
   const int B = cfg->num_envs, N = cfg->num_agents;
   int G = 1; while (G < N) G <<= 1;
   const size_t BN = (size_t)B * N;
@@ -172,13 +174,13 @@ extern "C" int mcr_create(const mcr_config* cfg, mcr_env** out) {
   const size_t o_pidmeta = carve(one_world ? sizeof(int32_t) * 4 * (size_t)B : 0);
   const size_t o_slots = carve((size_t)B * 2 * MCR_SLOT_BYTES);
   h->slab_bytes = off;
-  if (hipMalloc(&h->slab, off) != hipSuccess) { g_err = "hipMalloc failed"; delete h; return MCR_ERR_HIP; }
+  if (hipMalloc(&h->slab, off) != hipSuccess) { h->slab = nullptr; g_err = "hipMalloc failed"; release_env(h); return MCR_ERR_HIP; }
   (void)hipMemset(h->slab, 0, o_slots);
   for (int par = 0; par < 2; ++par)      // raster order lists (per step parity: 2 counts, then B entries): -1 = unused entry
     (void)hipMemset((uint8_t*)h->slab + o_vorder + sizeof(int32_t) * ((size_t)par * (B + 2) + 2), 0xff, sizeof(int32_t) * (size_t)B);
   uint8_t* base = (uint8_t*)h->slab;
   McrParams& P = h->P;
-  memset(&P, 0, sizeof(P));
+  memset(&P, 0, sizeof(P));      // (padding included: step_one compares whole blocks)
   P.B = B; P.N = N; P.G = G; P.BN = (int)BN;
   P.carf = (float*)(base + o_carf); P.card = (double*)(base + o_card); P.caru = (uint32_t*)(base + o_caru);
   P.env = (McrEnvState*)(base + o_env); P.tile_touch = (uint32_t*)(base + o_touch); P.tile_flags = (uint16_t*)(base + o_tflags);
@@ -194,76 +196,64 @@ extern "C" int mcr_create(const mcr_config* cfg, mcr_env** out) {
   P.backwards_flag = cfg->backwards_flag; P.use_ego_color = cfg->use_ego_color; P.h_ratio = cfg->h_ratio;
   McrShapes S; mcr_build_shapes(&S);
   // the raster gives two record slots to hull polygon 2 (HULL_POLY3, 8 vertices) and one to every other car polygon
-  if (S.hull[0].n > 4 || S.hull[1].n > 4 || S.hull[2].n > 8 || S.hull[3].n > 4 || S.wheel.n > 4) { g_err = "unexpected car fixture vertex counts"; (void)hipFree(h->slab); delete h; return MCR_ERR_STATE; }
+  if (S.hull[0].n > 4 || S.hull[1].n > 4 || S.hull[2].n > 8 || S.hull[3].n > 4 || S.wheel.n > 4) { g_err = "unexpected car fixture vertex counts"; release_env(h); return MCR_ERR_STATE; }
   (void)hipMemcpy((void*)P.shapes, &S, sizeof(S), hipMemcpyHostToDevice);
-  if (hipHostMalloc((void**)&h->consumed_host, sizeof(int32_t) * B, hipHostMallocMapped) != hipSuccess) { g_err = "hipHostMalloc failed"; (void)hipFree(h->slab); delete h; return MCR_ERR_HIP; }
+  if (hipHostMalloc((void**)&h->consumed_host, sizeof(int32_t) * B, hipHostMallocMapped) != hipSuccess) { h->consumed_host = nullptr; g_err = "hipHostMalloc failed"; release_env(h); return MCR_ERR_HIP; }
   memset(h->consumed_host, 0, sizeof(int32_t) * B);
   void* dptr = nullptr;
   (void)hipHostGetDevicePointer(&dptr, h->consumed_host, 0);
   P.consumed_host = (int32_t*)dptr;
   h->consumed_seen = new int32_t[B]();
-  if (hipHostMalloc((void**)&h->status_host, sizeof(uint32_t) * (MCR_STATUS_WORDS + MCR_HOST_COUNTS), hipHostMallocMapped) != hipSuccess) { g_err = "hipHostMalloc failed"; (void)hipHostFree(h->consumed_host); delete[] h->consumed_seen; (void)hipFree(h->slab); delete h; return MCR_ERR_HIP; }
+  if (hipHostMalloc((void**)&h->status_host, sizeof(uint32_t) * (MCR_STATUS_WORDS + MCR_HOST_COUNTS), hipHostMallocMapped) != hipSuccess) { h->status_host = nullptr; g_err = "hipHostMalloc failed"; release_env(h); return MCR_ERR_HIP; }
   memset(h->status_host, 0, sizeof(uint32_t) * (MCR_STATUS_WORDS + MCR_HOST_COUNTS));
   (void)hipHostGetDevicePointer(&dptr, h->status_host, 0);
   P.status = (uint32_t*)dptr; P.host_counts = P.status + MCR_STATUS_WORDS;
-  P.env0 = 0; P.nenv = B; P.split = 0; P.role = ROLE_ALL;
-  h->split = false; h->step_parity = 0;
+  P.nenv = B; P.role = ROLE_ALL;
   if (cfg->num_streams == 2) select_step_ordering(h);
   (void)hipDeviceSynchronize();
   *out = h;
   return MCR_OK;
 }
 
-extern "C" int mcr_refill_stop(mcr_env* h);
 extern "C" int mcr_destroy(mcr_env* h) {
   if (!h) return MCR_ERR_ARG;
   (void)mcr_refill_stop(h);
   if (h->soft_token) { std::lock_guard<std::mutex> lk(g_soft_mu); g_soft_list.erase(std::remove(g_soft_list.begin(), g_soft_list.end(), h), g_soft_list.end()); }
   (void)hipSetDevice(h->cfg.device);
   (void)sync_state(h);
-  for (auto& g : h->sg) if (g.valid) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); g.valid = false; }
-  for (auto& t : h->pending) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
-  for (auto e : h->free_events) (void)hipEventDestroy(e);
-  if (h->split) {
-    (void)hipStreamDestroy(h->s_side); (void)hipStreamDestroy(h->s_defer);
-    (void)hipEventDestroy(h->ev_fork); (void)hipEventDestroy(h->ev_join); (void)hipEventDestroy(h->ev_fork2); (void)hipEventDestroy(h->ev_join2); (void)hipEventDestroy(h->ev_col);
-  }
-  (void)hipFree(h->slab);
-  if (h->term_slab) (void)hipFree(h->term_slab);
-  if (h->ring.fresh) (void)hipFree(h->ring.fresh);
-  (void)hipHostFree(h->consumed_host);
-  (void)hipHostFree(h->status_host);
-  delete[] h->consumed_seen;
-  delete h;
+  release_env(h);
   return MCR_OK;
 }
 
+// The one staging path (mcr_stage_episodes; the refill service, mcr_refill.hip): row i (row_by_id: row ids[i]) of `src` goes into the staged slot
+// of env ids[i] (ids null: env i), then one id upload + one tiny kernel flip the n staged_ready flags (a 4-byte copy per env from pageable
+// memory made staging a whole batch take longer than generating it).  The ids are in range (the callers' business).  On failure *what names the
+// call.  The staged slot of env e is ((installs & 1) ^ 1): slot 0 is "current" before the first install and every install flips it.  `installs`
+// is read from the mapped-host counter the install wrote; the device cannot install again before this copy lands (staged_ready is 0 until then).
+hipError_t stage_rows(mcr_env* h, const int32_t* ids, int n, const uint8_t* src, bool row_by_id, hipStream_t st, const char** what) {
+  if (n <= 0) return hipSuccess;
+  hipError_t er = hipSuccess;
+  *what = "hipMemcpyAsync (episode)";
+  for (int i = 0; i < n; ++i) {
+    const int e = ids ? ids[i] : i;
+    const int32_t installs = ((volatile int32_t*)h->consumed_host)[e];
+    uint8_t* dst = h->P.slots + ((size_t)e * 2 + ((installs & 1) ^ 1)) * MCR_SLOT_BYTES;
+    if ((er = hipMemcpyAsync(dst, src + (size_t)(row_by_id ? e : i) * MCR_SLOT_BYTES, MCR_SLOT_BYTES, hipMemcpyHostToDevice, st)) != hipSuccess) return er;
+  }
+  *what = "hipMemcpyAsync (ids)";
+  if (ids && (er = hipMemcpyAsync(h->stage_ids, ids, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st)) != hipSuccess) return er;
+  *what = "k_mark_staged";
+  hipLaunchKernelGGL(k_mark_staged, dim3((n + 255) / 256), dim3(256), 0, st, h->P, ids ? (const int32_t*)h->stage_ids : nullptr, n);
+  return hipGetLastError();
+}
+// TODO(ADVICE r06-2): not refused while the refill service runs (both would stage into the same slots)
 extern "C" int mcr_stage_episodes(mcr_env* h, const int32_t* env_ids, int n, const void* blobs, void* stream) {
   if (!h || !blobs || n < 0) { g_err = "bad argument"; return MCR_ERR_ARG; }
   if (h->pool.blobs) { g_err = "mcr_stage_episodes: the handle stages its episodes from a level pool (mcr_set_episode_pool)"; return MCR_ERR_STATE; }
-  hipStream_t st = (hipStream_t)stream;
-  const int B = h->cfg.num_envs;
-  // The staged slot of env e is ((installs & 1) ^ 1): slot 0 is "current" before the first install and every
-  // install flips it.  `installs` is read from the mapped-host counter the install wrote; the device cannot
-  // install again before this copy lands (staged_ready is 0 until then), so the slot chosen here is free.
-  for (int i = 0; i < n; ++i) {
-    const int e = env_ids ? env_ids[i] : i;
-    if (e < 0 || e >= B) { g_err = "env id out of range"; return MCR_ERR_ARG; }
-    const int32_t installs = ((volatile int32_t*)h->consumed_host)[e];
-    uint8_t* dst = h->P.slots + ((size_t)e * 2 + ((installs & 1) ^ 1)) * MCR_SLOT_BYTES;
-    HIPCHK(hipMemcpyAsync(dst, (const uint8_t*)blobs + (size_t)i * MCR_SLOT_BYTES, MCR_SLOT_BYTES, hipMemcpyHostToDevice, st));
-  }
-  // one id upload + one tiny kernel flip the n staged_ready flags (a 4-byte copy per env from pageable memory made
-  // staging a whole batch take longer than generating it)
-  if (n > 0) {
-    const int32_t* d_ids = nullptr;
-    if (env_ids) {
-      HIPCHK(hipMemcpyAsync(h->stage_ids, env_ids, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-      d_ids = h->stage_ids;
-    }
-    hipLaunchKernelGGL(k_mark_staged, dim3((n + 255) / 256), dim3(256), 0, st, h->P, d_ids, n);
-    HIPCHK(hipGetLastError());
-  }
+  for (int i = 0; i < n; ++i) { const int e = env_ids ? env_ids[i] : i; if (e < 0 || e >= h->cfg.num_envs) { g_err = "env id out of range"; return MCR_ERR_ARG; } }
+  const char* what = "";
+  const hipError_t er = stage_rows(h, env_ids, n, (const uint8_t*)blobs, false, (hipStream_t)stream, &what);
+  if (er != hipSuccess) { g_err = std::string("mcr_stage_episodes: ") + what + ": " + hipGetErrorString(er); return MCR_ERR_HIP; }
   return MCR_OK;
 }
 
@@ -272,21 +262,17 @@ static hipEvent_t get_event(mcr_env* h) {
   hipEvent_t e; (void)hipEventCreate(&e); return e;
 }
 #define LAUNCH(kid_, kernel, grid, block, st, ...) LAUNCH_LDS(kid_, kernel, grid, block, 0, st, __VA_ARGS__)
+// `launch_` between two event records where mcr_timing asks for kernel kid_'s time
+#define TIMED(kid_, st, launch_)                                                         \
+  do {                                                                                   \
+    TimedLaunch tl_; bool tm_ = (h->timing >> (kid_)) & 1;                                              \
+    if (tm_) { tl_.id = (kid_); tl_.a = get_event(h); tl_.b = get_event(h); (void)hipEventRecord(tl_.a, st); } \
+    launch_;                                                                             \
+    if (tm_) { (void)hipEventRecord(tl_.b, st); h->pending.push_back(tl_); }                   \
+  } while (0)
 // a launch that completes the event `stop_` itself (nullptr: none): see mcr_view_launch
-#define LAUNCH_LDS_STOP(kid_, kernel, grid, block, lds_, st, stop_, ...)                               \
-  do {                                                                                   \
-    TimedLaunch tl_; bool tm_ = (h->timing >> (kid_)) & 1;                                              \
-    if (tm_) { tl_.id = (kid_); tl_.a = get_event(h); tl_.b = get_event(h); (void)hipEventRecord(tl_.a, st); } \
-    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_, st, nullptr, stop_, 0, __VA_ARGS__);          \
-    if (tm_) { (void)hipEventRecord(tl_.b, st); h->pending.push_back(tl_); }                   \
-  } while (0)
-#define LAUNCH_LDS(kid_, kernel, grid, block, lds_, st, ...)                                         \
-  do {                                                                                   \
-    TimedLaunch tl_; bool tm_ = (h->timing >> (kid_)) & 1;                                              \
-    if (tm_) { tl_.id = (kid_); tl_.a = get_event(h); tl_.b = get_event(h); (void)hipEventRecord(tl_.a, st); } \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_, st, __VA_ARGS__);          \
-    if (tm_) { (void)hipEventRecord(tl_.b, st); h->pending.push_back(tl_); }                   \
-  } while (0)
+#define LAUNCH_LDS_STOP(kid_, kernel, grid, block, lds_, st, stop_, ...) TIMED(kid_, st, hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_, st, nullptr, stop_, 0, __VA_ARGS__))
+#define LAUNCH_LDS(kid_, kernel, grid, block, lds_, st, ...) TIMED(kid_, st, hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_, st, __VA_ARGS__))
 
 // a launch of the dynamics over all envs: with or without the contact code (k_dynamics.h)
 #define LAUNCH_DYN(kid_, cc_, grid, st, ...) do { if (cc_) LAUNCH(kid_, k_dynamics<true>, grid, 64, st, __VA_ARGS__); else LAUNCH(kid_, k_dynamics<false>, grid, 64, st, __VA_ARGS__); } while (0)
@@ -340,35 +326,8 @@ static void launch_reset(mcr_env* h, McrParams P, hipStream_t st) {
   if (P.obs) launch_view(h, 2, B, st, P, 1);
 }
 
-// The low-dimensional observation of the state a reset / a step ended with (k_stateobs.h), a wavefront per env on the caller's stream: behind
-// launch_reset / launch_step (whose tail makes `st` wait for the whole step), outside the step's streams and outside a replayed step graph.
-// It reads no flags: nothing is flushed.  Off (no buffer): one test.
-void launch_state_obs(mcr_env* h, hipStream_t st) {
-  if (!h->so.out) return;
-  hipLaunchKernelGGL(k_stateobs, dim3(h->P.B), dim3(64), 0, st, h->P, h->so);
-}
-
-// The range-finder observation (k_rangeobs.h): launched wherever launch_state_obs is, for the same reasons.  Off (no buffer): one test.
-void launch_range_obs(mcr_env* h, hipStream_t st) {
-  if (!h->ro.out) return;
-  hipLaunchKernelGGL(k_rangeobs, dim3(h->P.B), dim3(64), 0, st, h->P, h->ro);
-}
-
-// Level pools (k_pool.h): every env that installed its staged episode gets its next one from the pool.  Launched where launch_state_obs goes — on
-// the caller's stream in front of and behind launch_reset and behind the LAST sub-step of a macro-step (a parked env re-spawns only there), whose
-// tail makes `st` wait for the whole step, outside the step's streams and outside a replayed step graph.  Behind the step's tail the terminal
-// frames (mcr_set_terminal_obs), which read the slot an env just left — the slot this kernel overwrites —, are drawn.  No flush_flags: the
-// scans a phase-word step left pending (k_flags.h) read an env's record and its CURRENT slot, and return at once for an env that just
-// re-spawned; the kernel writes staged slots and `staged_ready`, which the scans load with the record and never look at — and they are
-// launched by the NEXT step, behind this kernel in stream order (W_BEGIN is posted by that step's dynamics on `st`).
-static void launch_pool_restage(mcr_env* h, hipStream_t st, int envs_per_group) {
-  if (!h->pool.blobs) return;
-  const int B = h->P.B;
-  hipLaunchKernelGGL(k_pool_restage, dim3((B + envs_per_group - 1) / envs_per_group), dim3(MCR_POOL_LANES), 0, st, h->P.env, h->P.slots, B, h->pool, envs_per_group);
-}
-
 // may a step launched on caller stream `st` order its streams with phase words?  (mcr_bind_stream checked it; an unbound stream: events)
-static bool stream_bound(const mcr_env* h, hipStream_t st) {
+bool stream_bound(const mcr_env* h, hipStream_t st) {
   for (const auto& b : h->bound) if (b.first == st) return b.second;
   return false;
 }
@@ -661,7 +620,7 @@ static void launch_step(mcr_env* h, McrParams P, hipStream_t st, int view_flags)
   // k_collide's per-env "done" word.  24 us + a kernel boundary off the critical path.
   // Where kernels of different streams do not overlap (mcr_create probes it: counter-collecting profilers, debuggers) the
   // contact pass simply runs first, on the caller's stream.
-  P.cc_mode = cc_active(h) ? 1 : 0; P.epoch = h->step_count; P.epoch_ptr = nullptr;
+  P.cc_mode = cc_active(h) ? 1 : 0; P.epoch = h->step_count.load(std::memory_order_relaxed); P.epoch_ptr = nullptr;
   P.fuse_collide = fused_collide(h, st) ? 1 : 0; P.flags_deferred = 0;
   if (h->use_graph > 0) {
     // a replayed graph has constant arguments: the epoch lives in a device-side counter that the first node of the step advances
@@ -710,8 +669,7 @@ extern "C" int mcr_reset(mcr_env* h, const uint8_t* d_env_mask, uint8_t* d_obs, 
   launch_pool_restage(h, st, 1);          // the first reset finds every env staged (a later one: nothing to do) ...
   launch_reset(h, P, st);
   launch_pool_restage(h, st, 1);          // ... and every env that installed gets its next episode: up to B copies, one workgroup per env
-  launch_state_obs(h, st);
-  launch_range_obs(h, st);
+  launch_derived(h, st);
   HIPCHK(hipGetLastError());
   h->any_reset = true; h->verdict_fresh = false;
   return MCR_OK;
@@ -728,7 +686,7 @@ static int step_one(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* 
   P.defer_respawn = last ? 0 : 1; P.accumulate = sub > 0 ? 1 : 0;
   P.bp_fresh = h->bp_fresh ? 1 : 0; h->bp_fresh = false;
   if (P.obs) { h->ring.j = (int)(h->obs_draws % (uint64_t)h->ring.k); ++h->obs_draws; }
-  h->step_count = (int32_t)((uint32_t)h->step_count + 1u);      // (wraps: epochs are compared as 32-bit distances, mcr_kernels.h)
+  h->step_count.store((int32_t)((uint32_t)h->step_count.load(std::memory_order_relaxed) + 1u), std::memory_order_relaxed);      // (wraps: epochs are compared as 32-bit distances, mcr_kernels.h)
   // with auto_reset, finished envs are re-spawned on the device and take the action-less first step of their
   // new episode inside this call; the view kernel always runs (it also owns the backward/on-grass flags)
   const int vf = d_actions ? 1 : 0;
@@ -750,44 +708,36 @@ static int step_one(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* 
   }
   h->verdict_fresh = vf != 0;             // this step's bookkeeping evaluates the next step's
   h->last_fused = fz && vf != 0;
+  bool replay = false;
   if (h->use_graph > 0 && !h->timing && repeat == 1) {
     // The step is a fixed sequence of ~13 launches on up to three streams whose arguments only change with the
     // contact-list parity: it can be replayed as a hipGraph (measured r02: 0.4 % faster — the gaps between the step's
     // dependent kernels are GPU-side drain/start-up, not host launch cost — so VecMultiCarRacing leaves it off).  Any change of an argument
-    // (other buffers, another stream, debug switches) re-captures.
-    const int par = h->step_parity;
-    mcr_env::StepGraph& G = h->sg[par + 2 * (P.obs ? h->ring.j : 0)];
-    if (G.valid && G.st == st && G.view_flags == vf && memcmp(&G.P, &P, sizeof(P)) == 0) {
-      h->step_parity ^= 1;                              // what launch_step does on the host side
-      HIPCHK(hipGraphLaunch(G.exec, st));
-      launch_state_obs(h, st);
-      launch_range_obs(h, st);
-      launch_pool_restage(h, st, MCR_POOL_GROUP);
-      HIPCHK(hipGetLastError());
-      return MCR_OK;
-    }
-    if (G.valid) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); G.valid = false; }
+    // (other buffers, another stream, debug switches) re-captures.  This branch only decides whether the step is replayed or launched.
     const int parity_before = h->step_parity;
-    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-      launch_step(h, P, st, vf);
-      hipGraph_t graph = nullptr;
-      if (hipStreamEndCapture(st, &graph) == hipSuccess && graph && hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-        G.graph = graph; G.P = P; G.st = st; G.view_flags = vf; G.valid = true;
-        HIPCHK(hipGraphLaunch(G.exec, st));
-        launch_state_obs(h, st);
-        launch_range_obs(h, st);
-        launch_pool_restage(h, st, MCR_POOL_GROUP);
-        HIPCHK(hipGetLastError());
-        return MCR_OK;
+    mcr_env::StepGraph& G = h->sg[parity_before + 2 * (P.obs ? h->ring.j : 0)];
+    replay = G.valid && G.st == st && G.view_flags == vf && memcmp(&G.P, &P, sizeof(P)) == 0;
+    if (replay) h->step_parity ^= 1;                    // what launch_step does on the host side
+    else {
+      if (G.valid) { (void)hipGraphExecDestroy(G.exec); (void)hipGraphDestroy(G.graph); G.valid = false; }
+      if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+        launch_step(h, P, st, vf);
+        hipGraph_t graph = nullptr;
+        if (hipStreamEndCapture(st, &graph) == hipSuccess && graph && hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+          G.graph = graph; G.P = P; G.st = st; G.view_flags = vf; G.valid = replay = true;
+        }
+        else if (graph) (void)hipGraphDestroy(graph);
       }
-      if (graph) (void)hipGraphDestroy(graph);
+      if (!replay) {
+        (void)hipGetLastError();
+        h->use_graph = -1;                               // capture is not available here: plain launches from now on
+        h->step_parity = parity_before;
+      }
     }
-    (void)hipGetLastError();
-    h->use_graph = -1;                                 // capture is not available here: plain launches from now on
-    h->step_parity = parity_before;
+    if (replay) HIPCHK(hipGraphLaunch(G.exec, st));
   }
-  launch_step(h, P, st, vf);
-  if (last) { launch_state_obs(h, st); launch_range_obs(h, st); launch_pool_restage(h, st, MCR_POOL_GROUP); }
+  if (!replay) launch_step(h, P, st, vf);
+  if (last) launch_step_tail(h, st);                    // (a replayed step is a whole call: repeat == 1)
   HIPCHK(hipGetLastError());
   return MCR_OK;
 }
@@ -812,106 +762,6 @@ extern "C" int mcr_step_repeat(mcr_env* h, const float* d_actions, int repeat, u
 }
 extern "C" int mcr_step(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* d_reward, uint8_t* d_done, uint8_t* d_trunc, void* stream) {
   return mcr_step_repeat(h, d_actions, 1, d_obs, d_reward, d_done, d_trunc, stream);
-}
-
-extern "C" int mcr_state_obs_dim(int num_agents, int waypoints) {
-  if (num_agents < 1 || num_agents > MCR_MAX_AGENTS || waypoints < 0 || waypoints > MCR_SO_WAYPOINTS_MAX) { g_err = "mcr_state_obs_dim: num_agents 1..8, waypoints 0..16"; return MCR_ERR_ARG; }
-  return mcr_so_dim(num_agents, waypoints);
-}
-extern "C" int mcr_set_state_obs(mcr_env* h, float* d_state, int waypoints, int stride) {
-  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
-  if (waypoints < 0 || waypoints > MCR_SO_WAYPOINTS_MAX || stride < 1 || stride > MCR_SO_STRIDE_MAX) { g_err = "mcr_set_state_obs: waypoints 0..16, stride 1..64"; return MCR_ERR_ARG; }
-  h->so.out = d_state; h->so.K = waypoints; h->so.stride = stride; h->so.F = mcr_so_dim(h->P.N, waypoints);
-  return MCR_OK;
-}
-extern "C" int mcr_state_obs_now(mcr_env* h, void* stream) {
-  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
-  if (!h->so.out) { g_err = "mcr_state_obs_now: no buffer set (mcr_set_state_obs)"; return MCR_ERR_STATE; }
-  launch_state_obs(h, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MCR_OK;
-}
-
-// The range-finder observation (k_rangeobs.h).  mcr_set_range_obs only validates and stores: no HIP call, no device needed for its argument checks.
-extern "C" int mcr_check_range_obs(const float* dirs, int rays, float max_range) {
-  if (rays < 1 || rays > MCR_RANGE_RAYS_MAX) { g_err = "range_obs: rays 1..32"; return MCR_ERR_ARG; }
-  if (!dirs) { g_err = "range_obs: null direction table"; return MCR_ERR_ARG; }
-  for (int i = 0; i < 2 * rays; ++i) if (!std::isfinite(dirs[i])) { g_err = "range_obs: a direction is not finite"; return MCR_ERR_ARG; }
-  if (!std::isfinite(max_range) || !(max_range > 0.0f)) { g_err = "range_obs: max_range must be finite and > 0"; return MCR_ERR_ARG; }
-  return MCR_OK;
-}
-extern "C" int mcr_set_range_obs(mcr_env* h, float* d_ranges, const float* dirs, int rays, float max_range) {
-  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
-  if (!d_ranges) { h->ro.out = nullptr; return MCR_OK; }
-  if (int rc = mcr_check_range_obs(dirs, rays, max_range)) return rc;
-  McrRangeObs ro{};
-  double umax = 0.0;
-  for (int k = 0; k < rays; ++k) {
-    ro.dir[k][0] = dirs[2 * k]; ro.dir[k][1] = dirs[2 * k + 1];
-    umax = fmax(umax, sqrt((double)dirs[2 * k] * (double)dirs[2 * k] + (double)dirs[2 * k + 1] * (double)dirs[2 * k + 1]));
-  }
-  ro.out = d_ranges; ro.R = rays; ro.max_range = max_range;
-  ro.cull = (double)max_range * umax * (1.0 + 1e-6) + 1e-2;
-  h->ro = ro;
-  return MCR_OK;
-}
-extern "C" int mcr_range_obs_now(mcr_env* h, void* stream) {
-  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
-  if (!h->ro.out) { g_err = "mcr_range_obs_now: no buffer set (mcr_set_range_obs)"; return MCR_ERR_STATE; }
-  launch_range_obs(h, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MCR_OK;
-}
-// the four hull fixture polygons as the kernels hold them (McrShapes::hull): out [4][8][2] f32 body-frame vertices, counts [4]; no handle, no GPU needed
-extern "C" int mcr_hull_polygons(float* out, int32_t* counts) {
-  if (!out || !counts) { g_err = "null argument"; return MCR_ERR_ARG; }
-  McrShapes S; mcr_build_shapes(&S);
-  for (int k = 0; k < 4; ++k) {
-    counts[k] = S.hull[k].n;
-    for (int i = 0; i < 8; ++i) { out[(k * 8 + i) * 2] = S.hull[k].vx[i]; out[(k * 8 + i) * 2 + 1] = S.hull[k].vy[i]; }
-  }
-  return MCR_OK;
-}
-
-// The scripted driver (k_driver.h).  mcr_set_drivers only validates and stores: no HIP call, no device needed for its argument checks.
-static const float MCR_DRV_DEFAULT_ROW[MCR_DRV_PARAMS] = MCR_DRV_DEFAULTS;
-static const char* drv_check_row(const float* q) {
-  for (int j = 0; j < MCR_DRV_PARAMS; ++j) if (!std::isfinite(q[j])) return "a parameter is not finite";
-  for (int j = 0; j < 2; ++j) if (q[j] < 1.0f || q[j] > (float)MCR_DRV_LOOKAHEAD_MAX || q[j] != (float)(int)q[j]) return "L1, L2 must be integers 1..64";
-  if (!(q[2] > 0.0f)) return "v_max must be > 0";
-  for (int j = 3; j <= 6; ++j) if (q[j] < 0.0f) return "K_s, K_c, K_g, K_b must be >= 0";
-  for (int j = 8; j <= 9; ++j) if (q[j] < 0.0f || q[j] > 1.0f) return "gas_max, brake_max must be in [0, 1]";
-  return nullptr;
-}
-extern "C" int mcr_driver_defaults(float* out) {
-  if (!out) { g_err = "null argument"; return MCR_ERR_ARG; }
-  for (int j = 0; j < MCR_DRV_PARAMS; ++j) out[j] = MCR_DRV_DEFAULT_ROW[j];
-  return MCR_OK;
-}
-extern "C" int mcr_check_drivers(int num_agents, const float* params, uint32_t agent_mask) {
-  if (num_agents < 1 || num_agents > MCR_MAX_AGENTS) { g_err = "drivers: num_agents 1..8"; return MCR_ERR_ARG; }
-  if (!params) { g_err = "drivers: null parameter rows"; return MCR_ERR_ARG; }
-  if (agent_mask >> num_agents) { g_err = "drivers: agent_mask has bits of cars >= num_agents"; return MCR_ERR_ARG; }
-  for (int a = 0; a < num_agents; ++a)
-    if (const char* why = drv_check_row(params + (size_t)a * MCR_DRV_PARAMS)) { g_err = "drivers: car " + std::to_string(a) + ": " + why; return MCR_ERR_ARG; }
-  return MCR_OK;
-}
-extern "C" int mcr_set_drivers(mcr_env* h, const float* params, uint32_t agent_mask, float* d_actions) {
-  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
-  if (!d_actions) { g_err = "mcr_set_drivers: null action buffer"; return MCR_ERR_ARG; }
-  if (int rc = mcr_check_drivers(h->P.N, params, agent_mask)) return rc;
-  for (int a = 0; a < MCR_MAX_AGENTS; ++a)
-    for (int j = 0; j < MCR_DRV_PARAMS; ++j) h->drv.prm[a][j] = a < h->P.N ? params[a * MCR_DRV_PARAMS + j] : MCR_DRV_DEFAULT_ROW[j];
-  h->drv_out = d_actions; h->drv_mask = agent_mask;
-  return MCR_OK;
-}
-extern "C" int mcr_driver_actions(mcr_env* h, const float* d_actions_in, uint32_t agent_mask_override, float* d_out, void* stream) {
-  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
-  if (!h->drv_out) { g_err = "mcr_driver_actions: no drivers set (mcr_set_drivers)"; return MCR_ERR_STATE; }
-  const uint32_t mask = agent_mask_override == 0xffffffffu ? (1u << h->P.N) - 1u : h->drv_mask;
-  hipLaunchKernelGGL(k_driver, dim3(h->P.B), dim3(64), 0, (hipStream_t)stream, h->P, h->drv, d_actions_in, mask, d_out ? d_out : h->drv_out);
-  HIPCHK(hipGetLastError());
-  return MCR_OK;
 }
 
 // Phase words need the caller's stream and the two internal ones on hardware queues of their own: a waiting kernel at the head of a shared
@@ -1000,30 +850,11 @@ extern "C" int mcr_set_step_graph(mcr_env* h, int enable) {
   if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
   if (enable && h->use_graph <= 0) {     // the device-side epoch counter continues the host's (both advance once per step from here on)
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(h->dev_step_ctr, &h->step_count, sizeof(int32_t), hipMemcpyHostToDevice));
+    const int32_t steps = h->step_count.load(std::memory_order_relaxed);
+    HIPCHK(hipMemcpy(h->dev_step_ctr, &steps, sizeof(int32_t), hipMemcpyHostToDevice));
   }
   h->use_graph = enable ? 1 : 0;
   return MCR_OK;
-}
-
-// blockIdx.y = step offset: out[nsteps][n_cars][3]
-__global__ void k_synth_actions(float* __restrict__ out, int n_cars, int N, unsigned long long seed, unsigned t, unsigned env_offset) {
-  const int ci = blockIdx.x * blockDim.x + threadIdx.x;
-  if (ci >= n_cars) return;
-  float a[3];
-  mcr_synth_action(seed, env_offset + (unsigned)(ci / N), (unsigned)(ci % N), t + blockIdx.y, a);
-  float* o = out + ((size_t)blockIdx.y * n_cars + ci) * 3;
-  o[0] = a[0]; o[1] = a[1]; o[2] = a[2];
-}
-extern "C" int mcr_synth_actions_block(mcr_env* h, float* d_actions, uint64_t seed, uint32_t t0, int nsteps, uint32_t env_offset, void* stream) {
-  if (!h || !d_actions || nsteps < 1 || nsteps > 65535) { g_err = "bad argument"; return MCR_ERR_ARG; }
-  hipLaunchKernelGGL(k_synth_actions, dim3((h->P.BN + 255) / 256, nsteps), dim3(256), 0, (hipStream_t)stream, d_actions, h->P.BN, h->P.N,
-                     (unsigned long long)seed, t0, env_offset);
-  HIPCHK(hipGetLastError());
-  return MCR_OK;
-}
-extern "C" int mcr_synth_actions(mcr_env* h, float* d_actions, uint64_t seed, uint32_t t, uint32_t env_offset, void* stream) {
-  return mcr_synth_actions_block(h, d_actions, seed, t, 1, env_offset, stream);
 }
 
 extern "C" int mcr_render(mcr_env* h, int env, int width, int height, uint8_t* d_out, void* stream) {
@@ -1050,377 +881,5 @@ extern "C" int mcr_read_rollout_stats(mcr_env* h, double* out2, int reset) {
 extern "C" int mcr_set_episode_stats(mcr_env* h, double* d_ep_return, int32_t* d_ep_len) {
   if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
   h->P.ep_return_out = d_ep_return; h->P.ep_len_out = d_ep_len;
-  return MCR_OK;
-}
-
-extern "C" int mcr_set_episode_pool(mcr_env* h, const void* d_pool, int K, uint64_t seed, uint32_t env_offset, int mode, int32_t* d_level) {
-  if (!h || !d_pool) { g_err = "mcr_set_episode_pool: null argument"; return MCR_ERR_ARG; }
-  if (K < 1 || ((uintptr_t)d_pool & 15u) || (mode != 0 && mode != 1)) { g_err = "mcr_set_episode_pool: K >= 1 rows, a 16-byte aligned pool, mode 0 (random) or 1 (cycle)"; return MCR_ERR_ARG; }
-  // (the staged slots have ONE owner for the life of the handle: a pool set later would meet episodes the host staged and counters it polls)
-  if (h->any_reset) { g_err = "mcr_set_episode_pool after the first mcr_reset"; return MCR_ERR_STATE; }
-  if (h->svc) { g_err = "mcr_set_episode_pool: the refill service is running"; return MCR_ERR_STATE; }
-  h->pool.blobs = (const uint8_t*)d_pool; h->pool.K = K; h->pool.mode = mode; h->pool.seed = seed; h->pool.env_offset = env_offset; h->pool.level = d_level;
-  return MCR_OK;
-}
-
-extern "C" int mcr_poll_consumed(mcr_env* h, int32_t* env_ids_out, int cap, void* stream) {
-  if (!h) return MCR_ERR_ARG;
-  if (h->pool.blobs) { g_err = "mcr_poll_consumed: the handle stages its episodes from a level pool (mcr_set_episode_pool)"; return MCR_ERR_STATE; }
-  if (h->svc) { g_err = "mcr_poll_consumed: the handle's refill service owns the counters (mcr_refill_start)"; return MCR_ERR_STATE; }
-  (void)stream;   // counters live in mapped host memory: no device synchronisation needed
-  int n = 0;
-  const int B = h->cfg.num_envs;
-  for (int e = 0; e < B; ++e) {
-    int32_t c = ((volatile int32_t*)h->consumed_host)[e];
-    if (c != h->consumed_seen[e]) {
-      if (n < cap && env_ids_out) { env_ids_out[n] = e; h->consumed_seen[e] = c; ++n; }
-      else if (!env_ids_out) ++n;
-    }
-  }
-  return n;
-}
-
-// ---------------------------------------------------------------------------- the refill service
-// What VecMultiCarRacing's Python worker did every step — poll the consumed-episode counters, generate the next episode of every env that
-// re-spawned (its own RNG streams), stage it — as native threads of the handle: a service thread (polls, queues env ids, stages finished
-// tracks) and up to six generator threads (one track at a time off the queue).  No interpreter, no GIL hand-offs, no gather / scatter of RNG
-// states, no bounce buffer (the env's row of the caller's pinned blob array is the staging source), no condition variable or per-batch barrier
-// on the path.  Host share of a rank: bench.py --emulate-world 8.  The arrays belong to the caller and must outlive the service.
-#include <thread>
-#include <deque>
-#include <condition_variable>
-#include <atomic>
-#include <unistd.h>
-#include <sys/prctl.h>
-extern "C" int mcr_episodes_generate_rows(uint32_t*, uint32_t*, const int32_t*, int, int, int, void*, int32_t*, int);   // mcr_host.cpp
-struct RefillSvc {
-  std::thread th;                      // polls the counters, hands env ids to the generators, stages what they finished
-  std::vector<std::thread> gens;       // generator threads: one track at a time each, off a queue — AWAKE while there is work (they poll with
-                                       // short sleeps and back off when idle): a batch handed to sleeping helpers through a condition variable
-                                       // cost the wake-up latency of the slowest helper per batch, and when the helpers woke late the calling
-                                       // thread generated every track itself, 0.1 ms each against 4 consumptions per 0.22 ms step — a 20-step
-                                       // bench run then ended with 8 ms of host backlog (round 6, profiles/r06_driver_style_runs.txt)
-  std::mutex m;                        // one service cycle at a time (the thread's, or a caller's inside mcr_refill_wait)
-  std::mutex qm;                       // todo / done / inflight
-  std::deque<int32_t> todo; std::vector<int32_t> done; int inflight = 0;
-  std::atomic<bool> stop{false}, hold{false};
-  uint32_t* mt_track; uint32_t* mt_draw; int direction_mode, gen_threads;
-  uint8_t* blobs; int32_t* info;
-  hipStream_t st = nullptr; hipEvent_t ev = nullptr;
-  std::vector<int32_t> ids;
-  std::atomic<long long> generated{0};
-  // the age of the oldest consumption that is not staged yet (mcr_refill_lag): consumptions are served first in, first out — near enough —, so the
-  // oldest unserved one is the `staged`-th to arrive; seen_step[k % size] = the step count when the k-th was noticed
-  std::vector<int32_t> seen_step; std::atomic<long long> arrived{0}, staged{0};
-  std::atomic<int> err{0}; std::string err_msg;
-  long long dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last mcr_refill_wait: queued / in flight / done at entry, cycles, tracks the waiter generated, us staging, us total, generator threads
-};
-// one track: env e's next episode from ITS rows of the caller's arrays (mcr_host.cpp; num_threads 1: on this thread)
-static bool refill_generate_one(mcr_env* h, RefillSvc* s, int32_t e) {
-  const int rc = mcr_episodes_generate_rows(s->mt_track, s->mt_draw, &e, 1, h->cfg.num_agents, s->direction_mode, s->blobs, s->info, 1);
-  if (rc != MCR_OK) { std::lock_guard<std::mutex> lk(s->qm); s->err_msg = "track generation failed (capacity: MCR_TILE_CAP / MCR_QUAD_CAP)"; s->err.store(rc); return false; }
-  return true;
-}
-// take one env off the queue and generate its track; false: nothing to do
-static bool refill_work_one(mcr_env* h, RefillSvc* s) {
-  int32_t e = -1;
-  { std::lock_guard<std::mutex> lk(s->qm); if (!s->todo.empty()) { e = s->todo.front(); s->todo.pop_front(); ++s->inflight; } }
-  if (e < 0) return false;
-  const bool ok = refill_generate_one(h, s, e);
-  { std::lock_guard<std::mutex> lk(s->qm); --s->inflight; if (ok) s->done.push_back(e); }
-  return true;
-}
-static void refill_gen_main(mcr_env* h, RefillSvc* s) {
-  (void)prctl(PR_SET_NAME, "mcr-gen", 0, 0, 0);
-  int idle = 0;
-  while (!s->stop.load()) {
-    if (refill_work_one(h, s)) { idle = 0; continue; }
-    ++idle;
-    usleep(idle < 400 ? 50 : 500);     // (20 ms without work: an idle env costs its generators next to nothing)
-  }
-}
-// one cycle of the service: new consumptions -> the generators' queue; finished tracks -> their envs' staged slots.  Returns what is still
-// pending afterwards (queued + being generated + consumptions not yet seen: 0 = all caught up), < 0: error.  Caller holds s->m.
-static int refill_cycle(mcr_env* h, RefillSvc* s, bool urgent = false) {
-  const int B = h->cfg.num_envs;
-  int n = 0;
-  for (int e = 0; e < B; ++e) {
-    const int32_t c = ((volatile int32_t*)h->consumed_host)[e];
-    if (c != h->consumed_seen[e]) { h->consumed_seen[e] = c; s->ids[n++] = e; }
-  }
-  int m = 0, left = 0;
-  {
-    std::lock_guard<std::mutex> lk(s->qm);
-    for (int i = 0; i < n; ++i) s->todo.push_back(s->ids[i]);
-    m = (int)s->done.size();
-    for (int i = 0; i < m; ++i) s->ids[i] = s->done[i];
-    s->done.clear();
-    left = (int)s->todo.size() + s->inflight;
-  }
-  { const long long a0 = s->arrived.load(); for (int i = 0; i < n; ++i) s->seen_step[(size_t)((a0 + i) % (long long)s->seen_step.size())] = h->step_count; s->arrived.store(a0 + n); }
-  if (s->err.load()) return s->err.load();
-  if (m > 0) {
-    auto fail = [&](const char* what, hipError_t e) { s->err_msg = std::string(what) + ": " + hipGetErrorString(e); s->err.store(MCR_ERR_HIP); return (int)MCR_ERR_HIP; };
-    for (int i = 0; i < m; ++i) {
-      const int e = s->ids[i];
-      const int32_t installs = ((volatile int32_t*)h->consumed_host)[e];
-      uint8_t* dst = h->P.slots + ((size_t)e * 2 + ((installs & 1) ^ 1)) * MCR_SLOT_BYTES;
-      const hipError_t er = hipMemcpyAsync(dst, s->blobs + (size_t)e * MCR_SLOT_BYTES, MCR_SLOT_BYTES, hipMemcpyHostToDevice, s->st);
-      if (er != hipSuccess) return fail("hipMemcpyAsync (episode)", er);
-    }
-    hipError_t er = hipMemcpyAsync(h->stage_ids, s->ids.data(), sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, s->st);
-    if (er != hipSuccess) return fail("hipMemcpyAsync (ids)", er);
-    hipLaunchKernelGGL(k_mark_staged, dim3((m + 255) / 256), dim3(256), 0, s->st, h->P, (const int32_t*)h->stage_ids, m);
-    if ((er = hipEventRecord(s->ev, s->st)) != hipSuccess) return fail("hipEventRecord", er);
-    // (polled with a sleep in between: hipEventSynchronize / hipStreamSynchronize spin on this runtime — 0.8 of a core, measured in round 3 —
-    // and a spinning thread takes a core from the track generators where the ranks of a node share few)
-    // (urgent — a caller waits in mcr_refill_wait: poll without sleeping for the first 100 us; the copies are 0.1 MB each)
-    for (int spins = 0;; ++spins) { er = hipEventQuery(s->ev); if (er == hipSuccess) break; if (er != hipErrorNotReady) return fail("hipEventQuery", er); if (!urgent || spins > 2000) usleep(30); }
-    s->generated.fetch_add(m);
-    s->staged.fetch_add(m);
-  }
-  if (left == 0) {                     // nothing queued, nothing in flight — unless a track finished meanwhile (it shows up in `done` next cycle)
-    std::lock_guard<std::mutex> lk(s->qm);
-    if (!(s->todo.empty() && s->inflight == 0 && s->done.empty())) left = 1;
-  }
-  return left;
-}
-static void refill_main(mcr_env* h, RefillSvc* s) {
-  (void)prctl(PR_SET_NAME, "mcr-refill", 0, 0, 0);
-  (void)hipSetDevice(h->cfg.device);
-  while (!s->stop.load()) {
-    if (!s->hold.load() && s->err.load() == 0) { std::lock_guard<std::mutex> lk(s->m); (void)refill_cycle(h, s); }
-    usleep(100);                       // (a step takes 0.2 ms and an env needs hundreds of steps to end its next episode: nothing is urgent here)
-  }
-}
-extern "C" int mcr_refill_start(mcr_env* h, uint32_t* mt_track, uint32_t* mt_draw, int direction_mode, int gen_threads, void* blobs_pinned, int32_t* episode_info) {
-  if (!h || !mt_track || !mt_draw || !blobs_pinned) { g_err = "mcr_refill_start: null argument"; return MCR_ERR_ARG; }
-  if (h->svc) { g_err = "mcr_refill_start: already running"; return MCR_ERR_STATE; }
-  if (h->pool.blobs) { g_err = "mcr_refill_start: the handle stages its episodes from a level pool (mcr_set_episode_pool)"; return MCR_ERR_STATE; }
-  HIPCHK(hipSetDevice(h->cfg.device));
-  RefillSvc* s = new RefillSvc();
-  s->mt_track = mt_track; s->mt_draw = mt_draw; s->direction_mode = direction_mode; s->gen_threads = std::max(1, gen_threads);
-  s->blobs = (uint8_t*)blobs_pinned; s->info = episode_info; s->ids.resize(h->cfg.num_envs); s->seen_step.assign((size_t)h->cfg.num_envs * 2, 0);
-  if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) { delete s; g_err = "mcr_refill_start: stream / event"; return MCR_ERR_HIP; }
-  h->svc = s;
-  s->th = std::thread(refill_main, h, s);
-  const int ngen = std::max(1, std::min(s->gen_threads, 6));       // (19 k tracks/s at B = 4096, N = 2 are two of them busy; 30 k at B = 32768 three)
-  for (int i = 0; i < ngen; ++i) s->gens.emplace_back(refill_gen_main, h, s);
-  return MCR_OK;
-}
-extern "C" int mcr_refill_stop(mcr_env* h) {
-  if (!h) return MCR_ERR_ARG;
-  RefillSvc* s = h->svc;
-  if (!s) return MCR_OK;
-  s->stop.store(true);
-  if (s->th.joinable()) s->th.join();
-  for (auto& g : s->gens) if (g.joinable()) g.join();
-  (void)hipSetDevice(h->cfg.device);
-  (void)hipStreamSynchronize(s->st);
-  (void)hipStreamDestroy(s->st); (void)hipEventDestroy(s->ev);
-  h->svc = nullptr;
-  delete s;
-  return MCR_OK;
-}
-// every consumption visible NOW is staged when this returns (the caller synchronised the stepping stream first if it needs "all of them");
-// honours the hold switch (tests: an env that finds no staged episode freezes)
-extern "C" int mcr_refill_wait(mcr_env* h) {
-  if (!h) return MCR_ERR_ARG;
-  RefillSvc* s = h->svc;
-  if (!s) return MCR_OK;
-  if (s->err.load()) { g_err = "the refill service failed: " + s->err_msg; return s->err.load(); }
-  if (s->hold.load()) return MCR_OK;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
-  auto us_since = [&](const timespec& a) { timespec b; clock_gettime(CLOCK_MONOTONIC, &b); return (long long)((b.tv_sec - a.tv_sec) * 1000000ll + (b.tv_nsec - a.tv_nsec) / 1000); };
-  std::lock_guard<std::mutex> lk(s->m);
-  { std::lock_guard<std::mutex> q(s->qm); s->dbg[0] = (long long)s->todo.size(); s->dbg[1] = s->inflight; s->dbg[2] = (long long)s->done.size(); }
-  s->dbg[3] = s->dbg[4] = s->dbg[5] = 0; s->dbg[7] = (long long)s->gens.size();
-  for (;;) {
-    timespec tc; clock_gettime(CLOCK_MONOTONIC, &tc);
-    const int left = refill_cycle(h, s, true);
-    s->dbg[5] += us_since(tc); ++s->dbg[3];
-    if (left < 0) { g_err = "the refill service failed: " + s->err_msg; return left; }
-    if (left == 0) break;
-    if (refill_work_one(h, s)) ++s->dbg[4]; else usleep(10);       // the waiting thread generates too: progress does not depend on how fast a sleeping generator wakes
-  }
-  s->dbg[6] = us_since(t0);
-  return MCR_OK;
-}
-// steps launched since the oldest consumption that is not staged yet was noticed (0: nothing pending); < 0: the service failed
-extern "C" int mcr_refill_lag(mcr_env* h) {
-  if (!h || !h->svc) return 0;
-  RefillSvc* s = h->svc;
-  if (s->err.load()) { g_err = "the refill service failed: " + s->err_msg; return s->err.load(); }
-  const long long st = s->staged.load(), ar = s->arrived.load();
-  if (st >= ar) return 0;
-  return std::max(0, (int32_t)((uint32_t)h->step_count - (uint32_t)s->seen_step[(size_t)(st % (long long)s->seen_step.size())]));
-}
-extern "C" int mcr_refill_debug(mcr_env* h, long long* out8) { if (!h || !h->svc || !out8) return MCR_ERR_STATE; for (int i = 0; i < 8; ++i) out8[i] = h->svc->dbg[i]; return MCR_OK; }
-extern "C" int mcr_refill_hold(mcr_env* h, int hold) { if (!h || !h->svc) return MCR_ERR_STATE; h->svc->hold.store(hold != 0); return MCR_OK; }
-extern "C" long long mcr_refill_generated(mcr_env* h) { return (h && h->svc) ? h->svc->generated.load() : 0; }
-
-__global__ void k_sincos(const float* in, float* s, float* c, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) mcr_sincosf(in[i], &s[i], &c[i]);
-}
-extern "C" int mcr_sincos_device(mcr_env* h, const float* d_in, float* d_sin, float* d_cos, int n, void* stream) {
-  if (!h || !d_in || !d_sin || !d_cos) return MCR_ERR_ARG;
-  hipLaunchKernelGGL(k_sincos, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_in, d_sin, d_cos, n);
-  HIPCHK(hipGetLastError());
-  return MCR_OK;
-}
-
-extern "C" int mcr_debug_read_view_scratch(mcr_env* h, int view, void* out, int nbytes) {
-  if (!h || !out || view < 0 || view >= h->P.BN || nbytes < 0 || nbytes > 128) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out, h->view_stamps + (size_t)view * 16, nbytes, hipMemcpyDeviceToHost));
-  return MCR_OK;
-}
-extern "C" int mcr_debug_read_counters(mcr_env* h, uint64_t* out4) {
-  if (!h || !out4) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out4, h->P.counters, sizeof(uint64_t) * 4, hipMemcpyDeviceToHost));
-  return MCR_OK;
-}
-extern "C" int mcr_debug_read_counters8(mcr_env* h, uint64_t* out8) {
-  if (!h || !out8) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out8, h->P.counters, sizeof(uint64_t) * 8, hipMemcpyDeviceToHost));
-  return MCR_OK;
-}
-extern "C" int mcr_concurrent_collide(const mcr_env* h) { return (h && h->split && h->concurrent_collide) ? 1 : 0; }
-extern "C" int mcr_step_ordering(const mcr_env* h) {
-  if (!h || !h->split) return 0;
-  return ((h->soft_sync && h->use_graph <= 0) ? 1 : 0) | 2 | (h->soft_denied ? 4 : 0);     // (bit 1: the event path always lets the launches complete the events, outside a capture)
-}
-extern "C" int mcr_step_ordering_for(const mcr_env* h, void* stream) {
-  if (!h || !h->split) return 0;
-  const int all = mcr_step_ordering(h);
-  return stream_bound(h, (hipStream_t)stream) ? all : (all & ~1);
-}
-extern "C" int mcr_debug_read_verdict_mismatches(mcr_env* h, uint64_t* out) {
-  if (!h || !out) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out, h->P.counters + 4, sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return MCR_OK;
-}
-// the last step's contact partition: part_out[B] (touch verdicts it went by), clist_out[1 + B] (its contact list: count, env ids); synchronises
-extern "C" int mcr_debug_read_partition(mcr_env* h, uint8_t* part_out, int32_t* clist_out) {
-  if (!h || !part_out || !clist_out) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
-  const size_t B = h->cfg.num_envs, par = (size_t)(h->step_parity ^ 1);
-  HIPCHK(hipMemcpy(part_out, h->P.part + par * B, B, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(clist_out, h->P.clist + par * (B + 1), sizeof(int32_t) * (B + 1), hipMemcpyDeviceToHost));
-  return MCR_OK;
-}
-// diagnostics of the verdict protocol: fill the buffer the NEXT step's verdict writers write (its part_next) with `value` / read it back after that step
-extern "C" int mcr_debug_next_verdicts(mcr_env* h, int fill_value, uint8_t* out_or_null) {
-  if (!h) return MCR_ERR_ARG;
-  if (!out_or_null && (fill_value & 0x100)) {     // (no synchronisation: the fill is enqueued on the null stream, in front of a step launched there)
-    flush_flags(h, nullptr);                      // (the pending bookkeeping reads that buffer as the last step's partition)
-    HIPCHK(hipMemsetAsync(h->P.part + (size_t)(h->step_parity ^ 1) * h->cfg.num_envs, fill_value & 0xff, h->cfg.num_envs, 0));
-    return MCR_OK;
-  }
-  HIPCHK(sync_state(h));
-  const size_t B = h->cfg.num_envs;
-  if (out_or_null) { HIPCHK(hipMemcpy(out_or_null, h->P.part + (size_t)h->step_parity * B, B, hipMemcpyDeviceToHost)); }       // (after a step: the parity has flipped)
-  else { HIPCHK(hipMemset(h->P.part + (size_t)(h->step_parity ^ 1) * B, fill_value, B)); }
-  return MCR_OK;
-}
-extern "C" int mcr_debug_read_env_records(mcr_env* h, void* out, int n_bytes) {
-  if (!h || !out || n_bytes < 0) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out, h->P.env, std::min((size_t)n_bytes, sizeof(McrEnvState) * (size_t)h->cfg.num_envs), hipMemcpyDeviceToHost));
-  return MCR_OK;
-}
-extern "C" int mcr_debug_read_contact_counts(mcr_env* h, int32_t* out) {
-  if (!h || !out) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
-  const size_t stride = MCR_CC_MAX * MCR_CC_WORDS + 4;
-  HIPCHK(hipMemcpy2D(out, sizeof(int32_t), h->P.cc_store, stride * sizeof(uint32_t), sizeof(int32_t), h->cfg.num_envs, hipMemcpyDeviceToHost));
-  return MCR_OK;
-}
-extern "C" int mcr_debug_read_proxy_ids(mcr_env* h, int env, int32_t* out, int cap) {
-  if (!h || !out || env < 0 || env >= h->cfg.num_envs) return MCR_ERR_ARG;
-  if (!h->P.pid_tab) { g_err = "mcr_debug_read_proxy_ids: the handle was created with fresh_world = 1 (ids ascend in creation order)"; return MCR_ERR_STATE; }
-  HIPCHK(hipDeviceSynchronize());
-  std::vector<uint16_t> tab(MCR_PID_TAB); int32_t meta[4];
-  HIPCHK(hipMemcpy(tab.data(), h->P.pid_tab + (size_t)env * MCR_PID_TAB, sizeof(uint16_t) * MCR_PID_TAB, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(meta, h->P.pid_meta + (size_t)env * 4, sizeof(meta), hipMemcpyDeviceToHost));
-  const int T = meta[2], F = 8 * h->cfg.num_agents;
-  int n = 0;
-  for (int t = 0; t < T && n < cap; ++t) out[n++] = tab[t];
-  for (int f = 0; f < F && n < cap; ++f) out[n++] = tab[MCR_TILE_CAP + f];
-  return n;
-}
-extern "C" int mcr_debug_read_dynamics_stamps(mcr_env* h, uint64_t* out, int n_u64) {
-  if (!h || !out) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out, h->P.dbg_stamps, sizeof(uint64_t) * (size_t)n_u64, hipMemcpyDeviceToHost));
-  return MCR_OK;
-}
-// the sensor predicate of k_collide (col::overlap: SAT far-field filter + Box2D's GJK) on caller-supplied cases
-__global__ void k_debug_overlap(const McrShapes* shapes, int fixture_arg, int n, const float4* __restrict__ va, const float4* __restrict__ vb,
-                                const float4* __restrict__ na, const float4* __restrict__ nb, const int* __restrict__ cnt,
-                                const float* __restrict__ poses, uint8_t* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const McrShapes& S = *shapes;
-  const bool fixture_first = fixture_arg >= 8;                     // b2TestOverlap(fixture, tile): the car fixture holds the lower proxy id
-  const int fixture = fixture_arg & 7;
-  const McrPoly& P = fixture < 4 ? S.hull[fixture] : S.wheel;
-  const V2 lc = fixture < 4 ? v2(S.hull_lcx, S.hull_lcy) : v2(0.0f, 0.0f);
-  // the body origin is given (b2BodyDef.position); sweep.c = xf * localCenter, then the transform k_collide derives from (c, a)
-  Xf x0; x0.q = rot_of(poses[i * 3 + 2]); x0.p = v2(poses[i * 3], poses[i * 3 + 1]);
-  const Xf xf = xf_of(xmul(x0, lc), poses[i * 3 + 2], lc);
-  float wx[8], wy[8], nx[8], ny[8];
-  for (int k = 0; k < 8; ++k) { wx[k] = wy[k] = nx[k] = ny[k] = 0.0f; }
-  for (int k = 0; k < P.n; ++k) { const V2 w = xmul(xf, v2(P.vx[k], P.vy[k])); const V2 nn = rmul(xf.q, v2(P.nx[k], P.ny[k])); wx[k] = w.x; wy[k] = w.y; nx[k] = nn.x; ny[k] = nn.y; }
-  col::TilePoly TP; const float4 a = va[i], b = vb[i], c = na[i], d = nb[i];
-  TP.n = cnt[i];
-  TP.vx[0] = a.x; TP.vy[0] = a.y; TP.vx[1] = a.z; TP.vy[1] = a.w; TP.vx[2] = b.x; TP.vy[2] = b.y; TP.vx[3] = b.z; TP.vy[3] = b.w;
-  TP.nx[0] = c.x; TP.ny[0] = c.y; TP.nx[1] = c.z; TP.ny[1] = c.w; TP.nx[2] = d.x; TP.ny[2] = d.y; TP.nx[3] = d.z; TP.ny[3] = d.w;
-  out[i] = col::overlap(wx, wy, nx, ny, P.n, TP, a, b, &P, make_float4(xf.p.x, xf.p.y, xf.q.s, xf.q.c), fixture_first) ? 1 : 0;
-}
-void mcr_tile_hull(const float* fx, const float* fy, float* aabb4, float* va4, float* vb4, float* na4, float* nb4, int* count);   // mcr_host.cpp
-extern "C" int mcr_debug_overlap(mcr_env* h, int n, const float* quads, const float* poses, int fixture, uint8_t* out) {
-  if (!h || !quads || !poses || !out || n < 0 || fixture < 0 || (fixture & 7) > 4 || fixture > 12) { g_err = "bad argument"; return MCR_ERR_ARG; }
-  if (n == 0) return MCR_OK;
-  std::vector<float> hull((size_t)n * 16); std::vector<int> cnt(n);
-  float* VA = hull.data(); float* VB = VA + (size_t)n * 4; float* NA = VB + (size_t)n * 4; float* NB = NA + (size_t)n * 4;
-  for (int i = 0; i < n; ++i) {
-    float fx[4], fy[4], box[4];
-    for (int k = 0; k < 4; ++k) { fx[k] = quads[(size_t)i * 8 + 2 * k]; fy[k] = quads[(size_t)i * 8 + 2 * k + 1]; }
-    mcr_tile_hull(fx, fy, box, VA + (size_t)i * 4, VB + (size_t)i * 4, NA + (size_t)i * 4, NB + (size_t)i * 4, &cnt[i]);
-  }
-  uint8_t* d = nullptr;
-  const size_t b_hull = sizeof(float) * 16 * (size_t)n, b_cnt = sizeof(int) * (size_t)n, b_pose = sizeof(float) * 3 * (size_t)n;
-  HIPCHK(hipMalloc(&d, b_hull + b_cnt + b_pose + (size_t)n));
-  float* d_hull = (float*)d; int* d_cnt = (int*)(d + b_hull); float* d_pose = (float*)(d + b_hull + b_cnt); uint8_t* d_out = d + b_hull + b_cnt + b_pose;
-  hipError_t e = hipMemcpy(d_hull, hull.data(), b_hull, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_cnt, cnt.data(), b_cnt, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_pose, poses, b_pose, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_debug_overlap, dim3((n + 255) / 256), dim3(256), 0, 0, h->P.shapes, fixture, n, (const float4*)d_hull, (const float4*)(d_hull + (size_t)n * 4),
-                       (const float4*)(d_hull + (size_t)n * 8), (const float4*)(d_hull + (size_t)n * 12), d_cnt, d_pose, d_out);
-    e = hipMemcpy(out, d_out, (size_t)n, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d);
-  if (e != hipSuccess) { g_err = std::string("mcr_debug_overlap: ") + hipGetErrorString(e); return MCR_ERR_HIP; }
-  return MCR_OK;
-}
-extern "C" int mcr_debug_set(mcr_env* h, int value) { if (!h) return MCR_ERR_ARG; h->P.debug = value; return MCR_OK; }
-extern "C" int mcr_timing_enable(mcr_env* h, int enable) { if (!h) return MCR_ERR_ARG; h->timing = enable; return MCR_OK; }
-extern "C" int mcr_timing_read(mcr_env* h, double* ms_out, int64_t* launches_out) {
-  if (!h) return MCR_ERR_ARG;
-  HIPCHK(hipDeviceSynchronize());
-  for (auto& t : h->pending) {
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) { h->t_ms[t.id] += ms; h->t_n[t.id] += 1; }
-    h->free_events.push_back(t.a); h->free_events.push_back(t.b);
-  }
-  h->pending.clear();
-  for (int i = 0; i < MCR_TIMING_SLOTS; ++i) { if (ms_out) ms_out[i] = h->t_ms[i]; if (launches_out) launches_out[i] = h->t_n[i]; h->t_ms[i] = 0; h->t_n[i] = 0; }
   return MCR_OK;
 }

@@ -326,7 +326,7 @@ inline int wrap(int i, int n) { i %= n; return i < 0 ? i + n : i; }
 
 // The sensor fixture of one tile as the device slot stores it: b2PolygonShape::Set of its 4 points -> tight AABB, hull
 // vertices v0 v1 | v2 v3 (CCW), normals n0 n1 | n2 n3, vertex count (3 or 4; a triangle repeats vertex 0 / normal 2).
-// (also used by mcr_debug_overlap, mcr_hip.hip)
+// (also used by mcr_debug_overlap, mcr_debug.hip)
 void mcr_tile_hull(const float* fx, const float* fy, float* aabb4, float* va4, float* vb4, float* na4, float* nb4, int* count) {
   HostPoly hp;
   if (!hull_from_points(fx, fy, 4, hp)) { hp.n = 3; for (int k = 0; k < 3; ++k) { hp.x[k] = fx[k]; hp.y[k] = fy[k]; hp.nx[k] = hp.ny[k] = 0; } }
@@ -549,7 +549,7 @@ extern "C" int mcr_episodes_generate(uint32_t* mt_track, uint32_t* mt_global, in
   return err.load();
 }
 
-// the same for rows ids[0..n) of PER-ENV arrays, in place: what the refill service (mcr_hip.hip) asks for — no gather / scatter of RNG states
+// the same for rows ids[0..n) of PER-ENV arrays, in place: what the refill service (mcr_refill.hip) asks for — no gather / scatter of RNG states
 extern "C" int mcr_episodes_generate_rows(uint32_t* mt_track_all, uint32_t* mt_global_all, const int32_t* ids, int n, int num_agents,
                                           int direction_mode, void* blobs_all, int32_t* info_all, int num_threads) {
   if (!mt_track_all || !mt_global_all || !blobs_all || !ids || n < 0) return MCR_ERR_ARG;

@@ -247,7 +247,7 @@ int envcopy(mcr_env* h, McrEnvCopyMode mode, const char* who, const int32_t* d_i
   if (mode == ENV_TO_BLOB) hipLaunchKernelGGL(k_envcopy<ENV_TO_BLOB>, dim3(n), dim3(MCR_EC_LANES), 0, st, a);
   else if (mode == BLOB_TO_ENV) hipLaunchKernelGGL(k_envcopy<BLOB_TO_ENV>, dim3(n), dim3(MCR_EC_LANES), 0, st, a);
   else hipLaunchKernelGGL(k_envcopy<ENV_TO_ENV>, dim3(n), dim3(MCR_EC_LANES), 0, st, a);
-  if (mode != ENV_TO_BLOB) { h->any_reset = true; h->verdict_fresh = false; launch_state_obs(h, st); launch_range_obs(h, st); }
+  if (mode != ENV_TO_BLOB) { h->any_reset = true; h->verdict_fresh = false; launch_derived(h, st); }
   HIPCHK(hipGetLastError());
   return MCR_OK;
 }

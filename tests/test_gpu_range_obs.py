@@ -146,6 +146,68 @@ def test_ranges_of_auto_reset_envs_are_the_new_episodes_first(torch_cuda, oracle
         f.o.close()
 
 
+_TAIL_REF = {}
+
+
+def _tail_reference(oracle, L, dirs, max_range):
+    """B = 8 followers, TimeLimit 12, reset + 30 random-action steps, made once for both cases of the test below: the actions [30, B, N, 3],
+    `done` [30, B] and, after reset (row 0) and after every step, the restatements of every env's ranges and state rows — those of an env
+    that ended in the step on the fresh reset of its next episode"""
+    if not _TAIL_REF:
+        B, N, seed, limit, steps = 8, 2, 123, 12, 30
+        fol = [Follower(oracle, N, seed, g, limit, render=False) for g in range(B)]
+        rows = lambda: (np.stack([R.of_oracle(L, f.o, f.ep, dirs, max_range) for f in fol]), np.stack([S.of_oracle(L, f.o, f.ep) for f in fol]))
+        rng = np.random.RandomState(6)
+        actions = np.stack([random_actions(rng, B, N, brake_scale=0.3) for _ in range(steps)])
+        done, ranges, state = np.zeros((steps, B), bool), [None] * (steps + 1), [None] * (steps + 1)
+        ranges[0], state[0] = rows()
+        for k in range(steps):
+            _, _, _, o_done = oracle.step_batch([f.o for f in fol], actions[k], None, threads=4)
+            for g, f in enumerate(fol):
+                f.steps += 1
+                done[k, g] = bool(o_done[g]) or f.steps >= limit
+                if done[k, g]:
+                    f.new_episode()
+            ranges[k + 1], state[k + 1] = rows()
+        for f in fol:
+            f.o.close()
+        _TAIL_REF.update(seed=seed, limit=limit, actions=actions, done=done, ranges=np.stack(ranges), state=np.stack(state), dirs=np.array(dirs), max_range=max_range)
+    assert np.array_equal(_TAIL_REF["dirs"], dirs) and _TAIL_REF["max_range"] == max_range
+    return _TAIL_REF
+
+
+@pytest.mark.parametrize("graph", [False, True])
+def test_ranges_and_state_behind_a_replayed_step_graph_with_auto_reset(torch_cuda, oracle, lib, graph):
+    """B = 8, N = 2, streams=2, TimeLimit 12, 30 steps, the step launched plainly or replayed from the handle's step graph (the replay-hit
+    branch from the third step on, once both parities are captured): after reset and after EVERY step every row of `ranges` and of `state`
+    is the restatement on the oracle — for an env whose `done` is set, on the fresh reset of its next episode.  `done` agrees with the
+    followers every step and every env ends twice at the limit, so the re-spawned rows are really compared."""
+    torch = torch_cuda
+    L = lib.load()
+    B, N = 8, 2
+    env = _make(B, N, 123, use_random_direction=True, auto_reset=True, max_episode_steps=12, streams=2, state_obs=True, graph=graph)
+    ref = _tail_reference(oracle, L, env.range_dirs, env.range_max)       # (the handle's ray table: the same for both cases, checked there)
+    assert (ref["seed"], ref["limit"]) == (123, 12)
+
+    def compare(row, what):
+        got_r, got_s = env.ranges.cpu().numpy(), env.state.cpu().numpy()
+        for e in range(B):
+            _assert_ranges(got_r[e], ref["ranges"][row, e], f"{what} env {e}")
+            assert np.array_equal(got_s[e], ref["state"][row, e]), f"{what} env {e}: state row"
+
+    env.reset()
+    compare(0, "after reset")
+    a = torch.empty((B, N, 3), dtype=torch.float32, device="cuda")       # ONE action buffer: a graph is replayed only while no argument changes
+    for k in range(30):
+        a.copy_(torch.from_numpy(ref["actions"][k]))
+        _, _, done, _ = env.step(a)
+        assert np.array_equal(done.cpu().numpy().astype(bool), ref["done"][k]), f"step {k}: done"
+        compare(k + 1, f"step {k}")
+    assert int(ref["done"].sum()) >= 16
+    assert env.status_words()[:5].tolist() == [0] * 5
+    env.close()
+
+
 def test_ranges_do_not_depend_on_the_batch(torch_cuda):
     """env g at B = 64 equals env g at B = 4 after 50 steps, and is non-zero"""
     torch = torch_cuda
