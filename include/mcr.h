@@ -136,6 +136,44 @@ int mcr_stage_episodes(mcr_env* h, const int32_t* env_ids, int n, const void* bl
  * staging words of the target's record and its staged slot are not touched, so a restored env goes on with the TARGET's next level. */
 int32_t mcr_pool_level(uint64_t seed, uint32_t global_env, uint32_t episode, int32_t K, int mode);
 int mcr_set_episode_pool(mcr_env* h, const void* d_pool, int K, uint64_t seed, uint32_t env_offset, int mode, int32_t* d_level);
+/* Level curricula, part 1 — weighted level sampling (Prioritized Level Replay and its kin: the learner scores the levels, the env draws the
+ * next level in proportion to the score).  A switch on a pool created with mode 0; mcr_set_episode_pool and mcr_pool_level keep their two modes.
+ *   uniform   u = (mcr_mix64(mcr_mix64(seed + 0x9e3779b97f4a7c15 * ((k << 32) | global env))) >> 11) * 2^-53: mode 0's hash with mode 0's key,
+ *             an exact f64 in [0, 1)
+ *   CDF       from weights w[0 .. K) (f64): a weight that is not finite or is negative counts as 0; S_j is the running f64 sum in index order;
+ *             cdf[j] = S_j / S_{K-1}.  If S_{K-1} is 0 or not finite the CDF is the uniform one, cdf[j] = (double)(j + 1) / (double)K, and the
+ *             "fell back" flag is raised.  A new sampler starts with the uniform CDF — bit for bit the CDF of all-ones weights.
+ *   level     the smallest j with u < cdf[j] (K - 1 if there is none).  A level of weight 0 is never drawn.
+ * mcr_level_cdf (returns 1 if it fell back, 0 otherwise; MCR_ERR_ARG for NULL or K < 1) and mcr_pool_level_weighted (MCR_ERR_ARG for a NULL
+ * cdf or K < 1) are these definitions on the host: no handle, no GPU.  The kernels evaluate the same code (csrc/mcr_common.h).
+ * WHEN a level is drawn: an env's NEXT episode is staged behind the reset or step in which it installed its current one (mcr_set_episode_pool),
+ * and the level is drawn there, from the CDF in force at that point of the stream; it is kept per env in d_staged_level and becomes the
+ * env's d_level row when the env installs that episode.  New weights therefore act with a lag of ONE EPISODE per env.  Rollouts remain a
+ * pure function of (seed, global env, episode ordinal, the sequence of mcr_level_weights calls in stream order): independent of the batch
+ * size and of the sharding, provided every rank sets the same weights at the same points.  d_staged_level is staging state like the staged
+ * slot: mcr_load_states / mcr_copy_states / mcr_set_state_blob leave it the target's, and the state blob does not change.
+ * mcr_set_level_sampler: d_cdf [K] f64 and d_staged_level [num_envs] int32 are the caller's device memory for the life of the handle; writes
+ * the uniform CDF into d_cdf (a blocking copy).  MCR_ERR_ARG: a NULL argument.  MCR_ERR_STATE: no pool, a mode-1 pool, after the first mcr_reset.
+ * mcr_level_weights: one small kernel on `stream` — the stepping stream — rebuilds d_cdf from d_weights [K] f64 (device) in the order above
+ * and stores the fell-back flag into *d_fell_back (int32 on the device; may be NULL).  Only enqueues.  MCR_ERR_STATE without a sampler. */
+int mcr_level_cdf(const double* w, int K, double* cdf_out);
+int32_t mcr_pool_level_weighted(uint64_t seed, uint32_t global_env, uint32_t episode, const double* cdf, int32_t K);
+int mcr_set_level_sampler(mcr_env* h, double* d_cdf /*[K]*/, int32_t* d_staged_level /*[B]*/);
+int mcr_level_weights(mcr_env* h, const double* d_weights, int32_t* d_fell_back, void* stream);
+/* Level curricula, part 2 — per-level episode statistics, what the weights are computed from.  Behind every mcr_step / mcr_step_repeat, on
+ * the caller's stream, a kernel (csrc/k_levelstats.h: definition and arithmetic contract) rewrites d_finished_level [num_envs] int32 — -1 for
+ * an env whose d_done row is 0, else the pool row of the episode that ENDED (d_level as it stood before the re-stage) if that is in 0 .. K-1,
+ * else K: the "unattributed" row, e.g. a level row of -1 after mcr_load_states — and adds the episode to row d_finished_level[e] of d_stats
+ * [K + 1][mcr_level_stats_dim(num_agents) = 3 + 2N] f64: col 0 episodes, 1 those with d_trunc set, 2 sum of d_ep_len, 3 .. 3+N sum of
+ * d_ep_return per car, 3+N .. 3+2N sum of its squares.  Per row and column the additions happen in step order and within a step in
+ * ascending env index, one f64 add each (the square: one f64 multiply first): a host reproduces every bit; no floating-point atomics.
+ * Counting rule (mcr_read_rollout_stats'): a done row counts once per step CALL that reports it — once per macro-step; an env of an
+ * auto_reset = 0 handle that is stepped past its end reports done, and counts, again in every call until it is reset.
+ * The caller zeroes d_stats (and may zero it again at any point of the stream).  Needs a pool with a d_level buffer and the
+ * mcr_set_episode_stats buffers (MCR_ERR_STATE otherwise); NULL pointers switch it off; takes effect with the next step.  No HIP call.
+ * Per handle, hence per rank: a job may all-reduce d_stats, after which the sums depend on the world size in their last bits. */
+int mcr_level_stats_dim(int num_agents);
+int mcr_set_level_stats(mcr_env* h, int32_t* d_finished_level, double* d_stats /*[K+1][3+2N]*/);
 /* reset() (:340-408): installs the staged episode for every env whose d_env_mask byte != 0 (NULL = all),
  * spawns the cars, runs the no-action step of :408 and writes the first observation.
  * d_obs: [B,N,96,96,3] u8 or NULL; with mcr_set_obs_format the layout that call describes. */

@@ -15,7 +15,7 @@ RANGE_RAYS_MAX = 32             # include/mcr.h: MCR_RANGE_RAYS_MAX, rays per ca
 DRV_PARAMS = 10                 # include/mcr.h: MCR_DRV_PARAMS, floats per parameter row of a scripted driver
 DRIVER_PARAM_NAMES = ("L1", "L2", "v_max", "K_s", "K_c", "K_g", "K_b", "offset", "gas_max", "brake_max")
 DRIVER_DEFAULTS = dict(zip(DRIVER_PARAM_NAMES, (4.0, 12.0, 70.0, 8.0, 20.0, 0.2, 0.1, 0.0, 1.0, 0.8)))    # include/mcr.h: MCR_DRV_DEFAULTS
-LEVEL_ORDER = {"random": 0, "cycle": 1}      # include/mcr.h: mcr_set_episode_pool's mode
+LEVEL_ORDER = {"random": 0, "cycle": 1}      # include/mcr.h: mcr_set_episode_pool's mode ("weighted" is no mode: vec_env.py puts a sampler on a mode-0 pool)
 
 # mcr_debug_set bits: the mirror of enum McrDebugBit (csrc/mcr_kernels.h, which says what each one does; tests/test_abi.py compares the two)
 DEBUG_VIEW_CLOCKS = 1 << 5
@@ -66,6 +66,12 @@ SYMBOLS = {
     "mcr_stage_episodes": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mcr_pool_level": (ctypes.c_int32, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _i]),
     "mcr_set_episode_pool": (_i, [_vp, _vp, _i, ctypes.c_uint64, ctypes.c_uint32, _i, _vp]),
+    "mcr_level_cdf": (_i, [_vp, _i, _vp]),
+    "mcr_pool_level_weighted": (ctypes.c_int32, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp, ctypes.c_int32]),
+    "mcr_set_level_sampler": (_i, [_vp, _vp, _vp]),
+    "mcr_level_weights": (_i, [_vp, _vp, _vp, _vp]),
+    "mcr_level_stats_dim": (_i, [_i]),
+    "mcr_set_level_stats": (_i, [_vp, _vp, _vp]),
     "mcr_reset": (_i, [_vp, _vp, _vp, _vp]),
     "mcr_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcr_step_repeat": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

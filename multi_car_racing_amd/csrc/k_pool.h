@@ -20,6 +20,12 @@
 //                    a step in which EVERY env re-spawns (all envs in phase at the TimeLimit) still has the whole machine copying.
 //   around a reset   1: one workgroup per env, up to eight per CU — 4096 copies of 96 KB are a memory-bound 0.8 GB of traffic.
 // The kernel computes nothing: like k_envcopy it is judged by the width of its accesses and how many are in flight.
+//
+// Weighted sampling (include/mcr.h: mcr_set_level_sampler; `pool.cdf` set).  The row is mcr_pool_level_cdf's — the same hash, mapped through
+// the CDF in force at THIS launch — so it cannot be recomputed when the env installs the episode (other weights may be in force then): the
+// lane that flips the flag keeps it in staged_level[env], and an env that needs a copy first hands staged_level[env] — what the launch that
+// staged the episode it just installed drew — to level[env].  staged_level is staging state like `staged_ready`: snapshots leave it alone.
+// k_level_cdf (below) rewrites the CDF in stream order: one wavefront, the running sum in index order (mcr_common.h has the definition).
 #pragma once
 #include "mcr_kernels.h"
 
@@ -37,12 +43,16 @@ __global__ __launch_bounds__(MCR_POOL_LANES) void k_pool_restage(McrEnvState* __
   const int mine = e0 + lane;
   const bool in_group = lane < envs_per_group && mine < B;
   int need = 0, slot = 0, consumed = 0;
+  int32_t drawn = 0;           // weighted: the row this launch stages for the lane's env
   if (in_group) { need = env[mine].staged_ready == 0; slot = env[mine].slot & 1; consumed = env[mine].consumed; }
   for (unsigned long long m = __ballot(need); m; m &= m - 1ull) {
     const int i = (int)__builtin_ctzll(m);
     const int e = e0 + i;
     const int staged = __shfl(slot, i) ^ 1;
-    const int32_t lv = mcr_pool_level_of(pool.seed, pool.env_offset + (uint32_t)e, (uint32_t)__shfl(consumed, i), pool.K, pool.mode);
+    const uint32_t ordinal = (uint32_t)__shfl(consumed, i);
+    const int32_t lv = pool.cdf ? mcr_pool_level_cdf(pool.seed, pool.env_offset + (uint32_t)e, ordinal, pool.cdf, pool.K)
+                                : mcr_pool_level_of(pool.seed, pool.env_offset + (uint32_t)e, ordinal, pool.K, pool.mode);
+    if (lane == i) drawn = lv;
     const uint4* __restrict__ s = (const uint4*)(pool.blobs + (size_t)lv * MCR_SLOT_BYTES);
     uint4* __restrict__ d = (uint4*)(slots + ((size_t)e * 2 + staged) * MCR_SLOT_BYTES);
     const uint32_t n = MCR_SLOT_BYTES / 16;
@@ -58,8 +68,34 @@ __global__ __launch_bounds__(MCR_POOL_LANES) void k_pool_restage(McrEnvState* __
   }
   __syncthreads();           // every wavefront's stores of the group's copies are issued (and every wavefront has read the flags) before a flag flips
   if (threadIdx.x < 64 && need) {
-    if (pool.level && consumed >= 1) pool.level[mine] = mcr_pool_level_of(pool.seed, pool.env_offset + (uint32_t)mine, (uint32_t)(consumed - 1), pool.K, pool.mode);
+    if (pool.cdf) {
+      if (pool.level && consumed >= 1) pool.level[mine] = pool.staged_level[mine];
+      pool.staged_level[mine] = drawn;
+    }
+    else if (pool.level && consumed >= 1) pool.level[mine] = mcr_pool_level_of(pool.seed, pool.env_offset + (uint32_t)mine, (uint32_t)(consumed - 1), pool.K, pool.mode);
     env[mine].staged_ready = 1;
   }
+}
+
+// mcr_level_weights: cdf[0 .. K) from weights[0 .. K), one wavefront.  64 weights per round are loaded side by side; the running sum then takes
+// them in index order, one f64 add each, in every lane alike (mcr_lane_f64), and lane i keeps the sum as it stood behind its weight.  The
+// second pass divides what the same lane stored by the total — or writes the uniform CDF and raises *fell_back.
+__global__ __launch_bounds__(64) void k_level_cdf(const double* __restrict__ weights, double* __restrict__ cdf, int K, int32_t* __restrict__ fell_back) {
+  const int lane = threadIdx.x;
+  double S = 0.0;
+  for (int j0 = 0; j0 < K; j0 += 64) {
+    const int j = j0 + lane;
+    const double w = j < K ? mcr_level_weight(weights[j]) : 0.0;
+    const int n = K - j0 < 64 ? K - j0 : 64;
+    double mine = 0.0;
+    for (int i = 0; i < n; ++i) {
+      S += mcr_lane_f64(w, i);
+      if (i == lane) mine = S;
+    }
+    if (j < K) cdf[j] = mine;
+  }
+  const bool ok = mcr_level_total_ok(S);
+  for (int j = lane; j < K; j += 64) cdf[j] = ok ? cdf[j] / S : mcr_level_cdf_uniform(j, K);
+  if (lane == 0 && fell_back) *fell_back = ok ? 0 : 1;
 }
 #endif

@@ -180,6 +180,29 @@ MCR_HD int32_t mcr_pool_level_of(uint64_t seed, uint32_t g, uint32_t k, int32_t 
   const uint64_t ctr = ((uint64_t)k << 32) | (uint64_t)g;
   return (int32_t)(mcr_mix64(mcr_mix64(seed + 0x9e3779b97f4a7c15ull * ctr)) % (uint64_t)K);
 }
+// Weighted level sampling (include/mcr.h: mcr_set_level_sampler): the k-th episode of global env g draws the f64 uniform below — mode 0's
+// hash with mode 0's key, its top 53 bits, so an exact f64 in [0, 1) — and plays the smallest row j with u < cdf[j] (K - 1 if there is none;
+// the CDF is non-decreasing, so the binary search finds the row a linear scan would).  A row of weight 0 has cdf[j] == cdf[j - 1] (or 0) and is
+// never drawn.  One pair of functions for the kernel (k_pool.h) and the host (mcr_pool_level_weighted).
+MCR_HD double mcr_pool_uniform(uint64_t seed, uint32_t g, uint32_t k) {
+  const uint64_t ctr = ((uint64_t)k << 32) | (uint64_t)g;
+  return (double)(mcr_mix64(mcr_mix64(seed + 0x9e3779b97f4a7c15ull * ctr)) >> 11) * (1.0 / 9007199254740992.0);
+}
+MCR_HD int32_t mcr_pool_level_cdf(uint64_t seed, uint32_t g, uint32_t k, const double* cdf, int32_t K) {
+  const double u = mcr_pool_uniform(seed, g, k);
+  int32_t lo = 0, hi = K - 1;
+  while (lo < hi) {
+    const int32_t mid = lo + ((hi - lo) >> 1);
+    if (u < cdf[mid]) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+// The CDF of weights w[0 .. K): a weight that is not finite or is negative counts as 0 (so does -0), S_j is the running f64 sum in index order,
+// cdf[j] = S_j / S_{K-1}; a total that is 0 or not finite means "uniform", cdf[j] = (j + 1) / K — which all-ones weights give bit for bit.
+// The three pieces below are all there is to it: the host loop (mcr_level_cdf) and the kernel (k_pool.h: k_level_cdf) put them together.
+MCR_HD double mcr_level_weight(double w) { return (w > 0.0 && w <= 1.7976931348623157e308) ? w : 0.0; }
+MCR_HD bool mcr_level_total_ok(double S) { return S > 0.0 && S <= 1.7976931348623157e308; }
+MCR_HD double mcr_level_cdf_uniform(int32_t j, int32_t K) { return (double)(j + 1) / (double)K; }
 MCR_HD float mcr_synth_uniform(uint64_t seed, uint32_t g, uint32_t agent, uint32_t t, uint32_t comp) {
   const uint64_t ctr = ((uint64_t)t << 32) | ((uint64_t)g * 8u + agent);
   const uint64_t x = mcr_mix64(mcr_mix64(seed + 0x9e3779b97f4a7c15ull * ctr) + comp);

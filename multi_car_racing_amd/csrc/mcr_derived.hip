@@ -5,6 +5,7 @@
 #include "k_rangeobs.h"
 #include "k_driver.h"
 #include "k_pool.h"
+#include "k_levelstats.h"
 #include <cmath>
 
 // The low-dimensional observation of the state a reset / a step ended with (k_stateobs.h), a wavefront per env on the caller's stream: behind
@@ -33,7 +34,18 @@ void launch_pool_restage(mcr_env* h, hipStream_t st, int envs_per_group) {
   const int B = h->P.B;
   hipLaunchKernelGGL(k_pool_restage, dim3((B + envs_per_group - 1) / envs_per_group), dim3(MCR_POOL_LANES), 0, st, h->P.env, h->P.slots, B, h->pool, envs_per_group);
 }
-void launch_step_tail(mcr_env* h, hipStream_t st) { launch_derived(h, st); launch_pool_restage(h, st, MCR_POOL_GROUP); }
+// Per-level episode statistics (k_levelstats.h): one launch, a wavefront per stats row, from the done / truncated rows the step just wrote.  It
+// reads level[] and must see the rows of the episodes that ENDED: in front of the re-stage, which hands an env that installed its next
+// episode that episode's row.  Behind the last sub-step of a macro-step only, like everything here: once per step call.
+static void launch_level_stats(mcr_env* h, hipStream_t st, const uint8_t* d_done, const uint8_t* d_trunc) {
+  if (!h->ls.stats) return;
+  const int waves = h->pool.K + 1, per_group = MCR_LS_LANES / 64;
+  hipLaunchKernelGGL(k_levelstats, dim3((waves + per_group - 1) / per_group), dim3(MCR_LS_LANES), 0, st, h->ls, d_done, d_trunc,
+                     (const double*)h->P.ep_return_out, (const int32_t*)h->P.ep_len_out, (const int32_t*)h->pool.level, h->P.B, h->P.N, h->pool.K);
+}
+void launch_step_tail(mcr_env* h, hipStream_t st, const uint8_t* d_done, const uint8_t* d_trunc) {
+  launch_derived(h, st); launch_level_stats(h, st, d_done, d_trunc); launch_pool_restage(h, st, MCR_POOL_GROUP);
+}
 
 extern "C" int mcr_state_obs_dim(int num_agents, int waypoints) {
   if (num_agents < 1 || num_agents > MCR_MAX_AGENTS || waypoints < 0 || waypoints > MCR_SO_WAYPOINTS_MAX) { g_err = "mcr_state_obs_dim: num_agents 1..8, waypoints 0..16"; return MCR_ERR_ARG; }
@@ -142,5 +154,37 @@ extern "C" int mcr_set_episode_pool(mcr_env* h, const void* d_pool, int K, uint6
   if (h->any_reset) { g_err = "mcr_set_episode_pool after the first mcr_reset"; return MCR_ERR_STATE; }
   if (h->svc) { g_err = "mcr_set_episode_pool: the refill service is running"; return MCR_ERR_STATE; }
   h->pool.blobs = (const uint8_t*)d_pool; h->pool.K = K; h->pool.mode = mode; h->pool.seed = seed; h->pool.env_offset = env_offset; h->pool.level = d_level;
+  return MCR_OK;
+}
+
+// Weighted level sampling on a mode-0 pool (k_pool.h).  The uniform CDF goes into the caller's buffer with a blocking copy: set-up time, before the first reset.
+extern "C" int mcr_set_level_sampler(mcr_env* h, double* d_cdf, int32_t* d_staged_level) {
+  if (!h || !d_cdf || !d_staged_level) { g_err = "mcr_set_level_sampler: null argument"; return MCR_ERR_ARG; }
+  if (!h->pool.blobs) { g_err = "mcr_set_level_sampler: no level pool (mcr_set_episode_pool)"; return MCR_ERR_STATE; }
+  if (h->pool.mode != 0) { g_err = "mcr_set_level_sampler: the pool was created with mode 1 (cycle); weighted sampling replaces mode 0's hash"; return MCR_ERR_STATE; }
+  if (h->any_reset) { g_err = "mcr_set_level_sampler after the first mcr_reset"; return MCR_ERR_STATE; }
+  std::vector<double> uniform((size_t)h->pool.K);
+  for (int j = 0; j < h->pool.K; ++j) uniform[j] = mcr_level_cdf_uniform(j, h->pool.K);
+  HIPCHK(hipMemcpy(d_cdf, uniform.data(), uniform.size() * sizeof(double), hipMemcpyHostToDevice));
+  h->pool.cdf = d_cdf; h->pool.staged_level = d_staged_level;
+  return MCR_OK;
+}
+extern "C" int mcr_level_weights(mcr_env* h, const double* d_weights, int32_t* d_fell_back, void* stream) {
+  if (!h || !d_weights) { g_err = "mcr_level_weights: null argument"; return MCR_ERR_ARG; }
+  if (!h->pool.cdf) { g_err = "mcr_level_weights: no sampler set (mcr_set_level_sampler)"; return MCR_ERR_STATE; }
+  hipLaunchKernelGGL(k_level_cdf, dim3(1), dim3(64), 0, (hipStream_t)stream, d_weights, const_cast<double*>(h->pool.cdf), h->pool.K, d_fell_back);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+extern "C" int mcr_level_stats_dim(int num_agents) {
+  if (num_agents < 1 || num_agents > MCR_MAX_AGENTS) { g_err = "mcr_level_stats_dim: num_agents 1..8"; return MCR_ERR_ARG; }
+  return MCR_LS_COLS(num_agents);
+}
+extern "C" int mcr_set_level_stats(mcr_env* h, int32_t* d_finished_level, double* d_stats) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!d_finished_level || !d_stats) { h->ls.finished = nullptr; h->ls.stats = nullptr; return MCR_OK; }
+  if (!h->pool.blobs || !h->pool.level) { g_err = "mcr_set_level_stats: needs a level pool with a level buffer (mcr_set_episode_pool)"; return MCR_ERR_STATE; }
+  if (!h->P.ep_return_out || !h->P.ep_len_out) { g_err = "mcr_set_level_stats: needs the episode statistics buffers (mcr_set_episode_stats)"; return MCR_ERR_STATE; }
+  h->ls.finished = d_finished_level; h->ls.stats = d_stats;
   return MCR_OK;
 }

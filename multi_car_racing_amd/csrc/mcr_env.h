@@ -1,6 +1,6 @@
 // mcr_env.h — the handle behind include/mcr.h's mcr_env and what the library's translation units share: mcr_hip.hip (creation, reset, the
 // step, staging, observation format), mcr_derived.hip (what is derived from the state a reset / step ended with: state vector, range finder,
-// scripted drivers, level pools), mcr_refill.hip (the refill service), mcr_debug.hip (debug readers, bench helpers) and mcr_state.hip (state
+// scripted drivers, level pools and their statistics), mcr_refill.hip (the refill service), mcr_debug.hip (debug readers, bench helpers) and mcr_state.hip (state
 // access and snapshots).  The shared surface is listed ONCE, at the end, under the unit that defines it.  Internal: nothing outside csrc/ includes it.
 #pragma once
 #include "../../include/mcr.h"
@@ -75,7 +75,8 @@ struct mcr_env {
   McrDriver drv{};            // mcr_set_drivers: the scripted driver's parameter rows (k_driver.h) ...
   float* drv_out = nullptr;   // ... the registered [B][N][3] buffer (nullptr: no drivers, nothing is launched) ...
   uint32_t drv_mask = 0;      // ... and the cars it drives
-  McrPool pool{nullptr, 0, 0, 0, 0, nullptr};   // mcr_set_episode_pool: the device stages the episodes itself (k_pool.h); blobs == nullptr: the host does
+  McrPool pool{nullptr, 0, 0, 0, 0, nullptr, nullptr, nullptr};   // mcr_set_episode_pool: the device stages the episodes itself (k_pool.h); blobs == nullptr: the host does
+  McrLevelStats ls{nullptr, nullptr};   // mcr_set_level_stats: per-level episode statistics (k_levelstats.h); stats == nullptr: off
 };
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -90,5 +91,7 @@ hipError_t stage_rows(mcr_env* h, const int32_t* ids, int n, const uint8_t* src,
 // mcr_derived.hip: the launches behind a reset, a restore and a step, on the caller's stream; each returns at once where its feature is off
 void launch_derived(mcr_env* h, hipStream_t st);       // the outputs derived from the current state: state vector (k_stateobs.h), then range finder (k_rangeobs.h)
 void launch_pool_restage(mcr_env* h, hipStream_t st, int envs_per_group);   // level pools (k_pool.h): the next episode of every env that installed its staged one
-void launch_step_tail(mcr_env* h, hipStream_t st);     // behind the last sub-step of a macro-step: launch_derived, then the pool re-stage with MCR_POOL_GROUP
+// behind the last sub-step of a macro-step: launch_derived, the per-level statistics (k_levelstats.h) from the step's done / truncated rows while
+// `level` still names the episodes that ended, then the pool re-stage with MCR_POOL_GROUP
+void launch_step_tail(mcr_env* h, hipStream_t st, const uint8_t* d_done, const uint8_t* d_trunc);
 // mcr_refill.hip, mcr_debug.hip: ABI entry points only (mcr_destroy calls mcr_refill_stop first).

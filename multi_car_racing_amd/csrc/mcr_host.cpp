@@ -598,6 +598,19 @@ extern "C" int32_t mcr_pool_level(uint64_t seed, uint32_t global_env, uint32_t e
   if (K < 1 || (mode != 0 && mode != 1)) return MCR_ERR_ARG;
   return mcr_pool_level_of(seed, global_env, episode, K, mode);
 }
+// weighted sampling: the CDF of a weight vector and the level it gives (mcr_common.h: the pieces the kernels k_level_cdf / k_pool_restage use)
+extern "C" int mcr_level_cdf(const double* w, int K, double* cdf_out) {
+  if (!w || !cdf_out || K < 1) return MCR_ERR_ARG;
+  double S = 0.0;
+  for (int j = 0; j < K; ++j) { S += mcr_level_weight(w[j]); cdf_out[j] = S; }
+  const bool ok = mcr_level_total_ok(S);
+  for (int j = 0; j < K; ++j) cdf_out[j] = ok ? cdf_out[j] / S : mcr_level_cdf_uniform(j, K);
+  return ok ? 0 : 1;
+}
+extern "C" int32_t mcr_pool_level_weighted(uint64_t seed, uint32_t global_env, uint32_t episode, const double* cdf, int32_t K) {
+  if (!cdf || K < 1) return MCR_ERR_ARG;
+  return mcr_pool_level_cdf(seed, global_env, episode, cdf, K);
+}
 
 // host twin of mcr_synth_actions (same counter-based stream; the CPU baseline and the tests consume it)
 extern "C" void mcr_synth_actions_host(float* out, int num_envs, int num_agents, uint64_t seed, uint32_t t, uint32_t env_offset) {

@@ -206,6 +206,16 @@ struct McrPool {
   uint64_t seed;
   uint32_t env_offset;          // global index of env 0
   int32_t* level;               // [B] the pool row of each env's current episode, or null
+  // weighted sampling (include/mcr.h: mcr_set_level_sampler; both null: the level is mcr_pool_level_of's)
+  const double* cdf;            // [K] the CDF in force (k_level_cdf rewrites it in stream order)
+  int32_t* staged_level;        // [B] the row copied into each env's STAGED slot: drawn when it was staged, `level` takes it at the install
+};
+
+// Per-level episode statistics (include/mcr.h: mcr_set_level_stats; k_levelstats.h): launch argument of k_levelstats, kept in the handle (null
+// `stats`: off, nothing is launched).  The step's done / truncated rows travel with the launch (launch_step_tail)
+struct McrLevelStats {
+  int32_t* finished;            // [B] the caller's: -1, or the stats row of the episode the env ended in this step
+  double* stats;                // [K + 1][3 + 2N] the caller's: episodes, truncated, sum of lengths, per car sum of returns, sum of squares
 };
 
 // status words (mapped host memory).  FATAL ones (give-up, verdict) make the next mcr_step return MCR_ERR_STATE; an OVERFLOW truncated a
@@ -220,6 +230,10 @@ enum { ST_SPIN_GIVEUP = 0,     // a kernel gave up waiting for another stream's 
        HC_CONTACT_ENVS = 0,    // the length of the last step's contact list
        MCR_HOST_COUNTS = 8 };
 __device__ __forceinline__ int mcr_epoch(const McrParams& p) { return p.epoch_ptr ? *p.epoch_ptr : p.epoch; }
+// lane i's f64 in every lane, i wave-uniform (two v_readlane: no LDS crossbar, the value lands in scalar registers)
+__device__ __forceinline__ double mcr_lane_f64(double v, int i) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), i), __builtin_amdgcn_readlane(__double2loint(v), i));
+}
 // Report condition `w` (ST_*): counted in device memory, the new count then STORED (system scope) into the mapped host word mcr_step polls —
 // no atomic on host memory, which needs PCIe atomics and is silently dropped where the platform lacks them.  (Two reports racing may land
 // out of order: the host word then holds the smaller of two non-zero counts until the next report; what mcr_step acts on is "it changed".)

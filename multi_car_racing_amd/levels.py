@@ -7,6 +7,11 @@ depend on how many are made — and level j can be compared with what env j of a
 
 Which level an env plays in which episode is `pool_level` (include/mcr.h: mcr_pool_level), the function the device evaluates when it
 re-stages an env (csrc/k_pool.h): a pure function of (seed, global env index, episode ordinal), independent of batch size and sharding.
+
+Curricula (`level_order="weighted"`, include/mcr.h: mcr_set_level_sampler): `level_cdf(weights)` is the CDF that
+VecMultiCarRacing.set_level_weights builds on the device and `weighted_level(seed, g, k, cdf)` the level it gives — the same hash as
+"random", mapped through the CDF in force when the episode was STAGED, one episode before the env plays it.  `pool_level` cannot answer for
+"weighted": it has no CDF.
 """
 import ctypes
 
@@ -42,8 +47,47 @@ def make_levels(K, num_agents=2, seed=0, direction_mode=2, threads=None):
 
 def pool_level(seed, global_env, episode, K, order="random"):
     """the pool row that the env with global index `global_env` plays in its `episode`-th episode (0: the first)"""
+    if order == "weighted":
+        raise ValueError("pool_level: the level of a weighted pool depends on the CDF in force when it was staged: use weighted_level(seed, g, k, cdf)")
     r = int(_lib.load().mcr_pool_level(ctypes.c_uint64(int(seed) % 2 ** 64), ctypes.c_uint32(int(global_env)), ctypes.c_uint32(int(episode)),
                                        int(K), _lib.LEVEL_ORDER[order]))
     if r < 0:
         raise ValueError(f"pool_level: K must be >= 1, got {K}")
     return r
+
+
+def level_cdf(weights):
+    """(cdf float64 [K], fell_back bool) of a weight vector (include/mcr.h: mcr_level_cdf): a weight that is not finite or is negative counts
+    as 0, the running sum goes in index order, and a total that is 0 or not finite gives the uniform CDF with fell_back set."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.ndim != 1 or len(w) < 1:
+        raise ValueError("level_cdf: weights must be a 1-D sequence of K >= 1 values")
+    cdf = np.zeros(len(w), np.float64)
+    return cdf, bool(_lib.check(_lib.load().mcr_level_cdf(_lib.ptr(w), len(w), _lib.ptr(cdf)), "mcr_level_cdf"))
+
+
+def weighted_level(seed, global_env, episode, cdf):
+    """the pool row that `cdf` (level_cdf) gives the env with global index `global_env` for its `episode`-th episode (0: the first)"""
+    c = np.ascontiguousarray(cdf, dtype=np.float64)
+    if c.ndim != 1 or len(c) < 1:
+        raise ValueError("weighted_level: cdf must be a 1-D sequence of K >= 1 values")
+    return int(_lib.load().mcr_pool_level_weighted(ctypes.c_uint64(int(seed) % 2 ** 64), ctypes.c_uint32(int(global_env)),
+                                                   ctypes.c_uint32(int(episode)), _lib.ptr(c), len(c)))
+
+
+def check_weights(weights, K):
+    """Host validation of a weight vector for K levels, as set_level_weights(check=True) applies it: float64 [K], every value finite and
+    >= 0, sum > 0 and finite.  Returns the float64 array; ValueError otherwise."""
+    try:
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"level weights must be numbers: {exc}") from None
+    if w.ndim != 1 or len(w) != int(K):
+        raise ValueError(f"level weights must have shape [{int(K)}], got {list(w.shape)}")
+    if not np.isfinite(w).all():
+        raise ValueError("level weights must be finite")
+    if (w < 0).any():
+        raise ValueError("level weights must be >= 0")
+    if level_cdf(w)[1]:
+        raise ValueError("level weights must have a finite sum > 0")
+    return w

@@ -79,6 +79,29 @@ pool row of each env's CURRENT episode; `self.level_info` the [K, 12] info rows 
 for caller blobs.  Snapshots: clone_envs copies the `level` rows; load_states sets them to -1 (a state blob does not say which level it
 came from); either way the env goes on with its OWN next level when the restored episode ends (the staging words stay the target's).
 
+Level curricula: the two halves of a loop that stays on the device — `w = f(vec.level_stats); vec.set_level_weights(w)` — with no
+synchronisation and no host work per step (include/mcr.h: mcr_set_level_stats, mcr_set_level_sampler).
+`level_stats=True` (needs `levels`): behind every step() a kernel (csrc/k_levelstats.h) rewrites `self.finished_level` (int32 [B], also
+info["finished_level"]): -1 where `done` is 0, else the level of the episode that just ENDED — `self.level` already names the new one —
+or K, the "unattributed" row, when that level is unknown (a `level` row of -1 after load_states; after clone_envs a clone's episode counts
+for the source's level, whose row was copied).  The same kernel adds the episode to row `finished_level[e]` of `self.level_stats`
+(float64 [K + 1, 3 + 2N], also level_stats_now()): column 0 episodes, 1 those with `truncated` set, 2 the sum of `episode_length`,
+3..3+N the sum of `episode_return` per car, 3+N..3+2N the sum of its squares; row K collects the unattributed episodes, so nothing is
+dropped silently.  Counting rule, rollout_stats()'s: a `done` row counts once per step() call that reports it — once per macro-step with
+`frame_skip`; with `auto_reset=False` an env that keeps being stepped past its end reports `done`, and counts, again in every call until
+reset_envs().  Per row and column the additions happen in step order and within a step in ascending env index, one f64 add each: a host
+reproduces every bit (tests/level_stats_ref.py); no floating-point atomics.  reset_level_stats() zeroes the tensor in stream order.  The
+statistics are per handle, hence per rank (sharded.py): a job may all_reduce `level_stats`; the sums then depend on the world size in
+their last bits.
+`level_order="weighted"`: env g plays in its k-th episode level levels.weighted_level(seed, g, k, cdf) — "random"'s hash as an f64 uniform
+in [0, 1), mapped through the CDF of the weights (levels.level_cdf: running f64 sum in index order over the total; a weight that is not
+finite or is negative counts as 0; a zero-weight level is never drawn).  A new handle draws uniformly; set_level_weights(w) rebuilds the CDF
+(`self.level_cdf`, float64 [K]) with one small kernel on the stepping stream.  An env's NEXT episode is staged — and its level drawn, from
+the CDF in force at that point of the stream — behind the reset or step in which it installed its current one: new weights act with a
+LAG OF ONE EPISODE per env (Prioritized Level Replay tolerates that).  Rollouts stay a pure function of (seed, g, k, the sequence of
+set_level_weights calls in stream order): independent of B and of sharding, provided every rank sets the same weights at the same steps.
+The drawn level is staging state, like the staged episode: load_states and clone_envs leave it the target's.
+
 Scripted drivers: `scripted_agents=(1,)` lets the DEVICE drive the listed cars — opponents for a learner, or (all cars) a baseline policy —
 with a stateless track-following controller (csrc/k_driver.h holds the definition; `drivers.DRIVER_DEFAULTS` the default parameters;
 `driver_params` overrides them: a dict {name: scalar or per-car sequence} or a float array [N, 10]).  step(actions) then runs one kernel in
@@ -161,6 +184,7 @@ class VecMultiCarRacing:
                  gen_threads=None, async_refill=True, streams=None, refill_lag=64, world_size=1, graph=None,
                  skid_particles=False, terminal_obs=False, terminal_cap=None, fresh_world=False, obs_format="rgb", frame_stack=1,
                  state_obs=False, state_waypoints=6, state_stride=5, frame_skip=1, levels=None, level_seed=None, level_order="random",
+                 level_stats=False,
                  scripted_agents=None, driver_params=None, range_obs=False, range_rays=19, range_fov=math.pi, range_angles=None,
                  range_max=100.0):
         # scripted drivers (module docstring): validated on the host before anything is created
@@ -173,14 +197,16 @@ class VecMultiCarRacing:
         if frame_skip > 1 and terminal_obs:
             raise ValueError("frame_skip > 1 cannot be combined with terminal_obs=True (the terminal frame would belong to an env step that draws nothing)")
         if levels is not None:            # (checked before anything is created)
-            if level_order not in _lib.LEVEL_ORDER:
-                raise ValueError(f"level_order must be one of {sorted(_lib.LEVEL_ORDER)}, got {level_order!r}")
+            if level_order not in _lib.LEVEL_ORDER and level_order != "weighted":
+                raise ValueError(f"level_order must be one of {sorted(_lib.LEVEL_ORDER) + ['weighted']}, got {level_order!r}")
             if isinstance(levels, (int, np.integer)) and not isinstance(levels, bool):
                 if int(levels) < 1:
                     raise ValueError(f"levels must be at least 1, got {levels}")
             elif (not isinstance(levels, np.ndarray) or levels.dtype != np.uint8 or levels.ndim != 2 or levels.shape[0] < 1
                   or levels.shape[1] != _lib.episode_bytes()):
                 raise ValueError(f"levels must be an int K >= 1 or a uint8 array [K, {_lib.episode_bytes()}] of episode blobs")
+        elif level_stats:
+            raise ValueError("level_stats=True needs a level pool (levels=...)")
         if not torch.cuda.is_available():
             raise _lib.McrError("VecMultiCarRacing needs a HIP device: the step path has no CPU fallback")
         self.L = _lib.load()
@@ -331,9 +357,12 @@ class VecMultiCarRacing:
         self._has_reset = False
         # level pool (module docstring): K resident episodes the device re-stages from; the host generates nothing after this
         self.level = self.level_info = self._pool = self._pool_np = None
+        self.level_cdf = self._staged_level = self.finished_level = self.level_stats = None
         self.num_levels = 0
         if levels is not None:
             self._init_levels(levels, seed if level_seed is None else level_seed, level_order, seed)
+            if level_stats:
+                self._init_level_stats()
         _LIVE.add(self)
 
     def _init_levels(self, levels, level_seed, level_order, seed):
@@ -350,11 +379,71 @@ class VecMultiCarRacing:
         self._level_buf = torch.full((self.B + 1,), -1, dtype=torch.int32, device=self.device)
         self.level = self._level_buf[:self.B]
         _lib.check(self.L.mcr_set_episode_pool(self.h, ctypes.c_void_p(self._pool.data_ptr()), self.num_levels, ctypes.c_uint64(int(seed) % 2 ** 64),
-                                               ctypes.c_uint32(self.env_offset), _lib.LEVEL_ORDER[level_order],
+                                               ctypes.c_uint32(self.env_offset), _lib.LEVEL_ORDER["random" if level_order == "weighted" else level_order],
                                                ctypes.c_void_p(self.level.data_ptr())), "mcr_set_episode_pool")
+        if level_order == "weighted":     # a sampler on the mode-0 pool (include/mcr.h: mcr_set_level_sampler); starts uniform
+            self.level_cdf = torch.zeros((self.num_levels,), dtype=torch.float64, device=self.device)
+            self._staged_level = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
+            _lib.check(self.L.mcr_set_level_sampler(self.h, ctypes.c_void_p(self.level_cdf.data_ptr()), ctypes.c_void_p(self._staged_level.data_ptr())),
+                       "mcr_set_level_sampler")
         torch.cuda.synchronize(self.device)                    # the upload is complete whichever stream the first reset() runs on
         self._episodes_generated = self.num_levels
         self._async = self._native = False                     # nobody polls, generates or stages: the kernel owns the staged slots
+
+    def _init_level_stats(self):
+        """per-level episode statistics (module docstring; include/mcr.h: mcr_set_level_stats)"""
+        cols = _lib.check(self.L.mcr_level_stats_dim(self.N), "mcr_level_stats_dim")
+        self.finished_level = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
+        self.level_stats = torch.zeros((self.num_levels + 1, cols), dtype=torch.float64, device=self.device)
+        _lib.check(self.L.mcr_set_level_stats(self.h, ctypes.c_void_p(self.finished_level.data_ptr()), ctypes.c_void_p(self.level_stats.data_ptr())),
+                   "mcr_set_level_stats")
+        torch.cuda.synchronize(self.device)                    # the zeros are in place whichever stream the first step() runs on
+
+    def level_stats_now(self):
+        """`self.level_stats`, float64 [K + 1, 3 + 2N] on the device (module docstring): a plain accessor — no copy, no synchronisation; the
+        values are those of the last step() once that step is complete on its stream."""
+        if self.level_stats is None:
+            raise _lib.McrError("level_stats_now() needs level_stats=True")
+        return self.level_stats
+
+    def reset_level_stats(self):
+        """Zero `self.level_stats` on the current stream (the stepping stream): steps enqueued later start from zero.  No synchronisation."""
+        if self.level_stats is None:
+            raise _lib.McrError("reset_level_stats() needs level_stats=True")
+        self.level_stats.zero_()
+
+    def set_level_weights(self, weights, check=True):
+        """New level weights for `level_order="weighted"` (module docstring): a sequence, a numpy array or a float64 / float32 device tensor
+        [K].  One small kernel rebuilds the CDF (`self.level_cdf`) on the current stream — the stepping stream; episodes STAGED from then on
+        are drawn from it, so every env plays one more episode drawn from the old weights first.  May be called before the first reset().
+        check=True validates on the host — shape, finite, >= 0, sum > 0: ValueError, nothing changed — which synchronises when `weights`
+        is a device tensor.  check=False never synchronises, treats a weight that is not finite or is negative as 0, falls back to the
+        uniform CDF if the sum is 0 or not finite, and returns the int32 device flag [1] "fell back to uniform"."""
+        if self.level_cdf is None:
+            raise _lib.McrError('set_level_weights() needs levels=... with level_order="weighted"')
+        K = self.num_levels
+        if torch.is_tensor(weights):
+            if weights.dtype not in (torch.float64, torch.float32) or weights.dim() != 1 or weights.shape[0] != K:
+                raise ValueError(f"level weights must be a float64 / float32 tensor [{K}], got {weights.dtype} {list(weights.shape)}")
+            if check:
+                from .levels import check_weights
+                check_weights(weights.detach().to(torch.float64).cpu().numpy(), K)
+            w = weights.detach().to(device=self.device, dtype=torch.float64).contiguous()
+        else:
+            from .levels import check_weights
+            if check:
+                host = check_weights(weights, K)
+            else:
+                host = np.ascontiguousarray(weights, dtype=np.float64)
+                if host.ndim != 1 or len(host) != K:
+                    raise ValueError(f"level weights must have shape [{K}], got {list(host.shape)}")
+            w = torch.from_numpy(host).to(self.device)
+        fell_back = torch.zeros(1, dtype=torch.int32, device=self.device)
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_level_weights(self.h, ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(fell_back.data_ptr()),
+                                            ctypes.c_void_p(st.cuda_stream)), "mcr_level_weights")
+        w.record_stream(st)
+        return fell_back
 
     # ------------------------------------------------------------------ episode generation / staging
     def _generate(self, ids):
@@ -595,6 +684,8 @@ class VecMultiCarRacing:
             info["ranges"] = self.ranges
         if self.level is not None:
             info["level"] = self.level
+        if self.level_stats is not None:
+            info["finished_level"] = self.finished_level
         if self._drv_mask and actions is not None:
             info["actions"] = self.actions
         return self.obs, self.reward, self.done, info
