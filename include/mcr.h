@@ -496,6 +496,17 @@ int mcr_status(mcr_env* h, uint32_t* out, int n_words);
  * whose origin and angle are poses[i][3]; out[i] = touching (host).  fixture + 8: the car fixture is fixtureA (b2TestOverlap(fixture, tile):
  * what a world that lives across reset() can ask for, mcr_world above).  Synchronous. */
 int mcr_debug_overlap(mcr_env* h, int n, const float* quads, const float* poses, int fixture, uint8_t* out);
+/* The step tail's launch of the per-level statistics kernel (mcr_set_level_stats above: definition and arithmetic contract) on
+ * caller-supplied rows, for differential tests: the same launch function, hence the same grid, block size and argument order, fed with the
+ * caller's device buffers instead of a handle's — d_done [num_envs] u8 (non-zero: the env ended), d_trunc [num_envs] u8 (may be NULL:
+ * nothing truncated), d_ep_return [num_envs][num_agents] f64, d_ep_len and d_level [num_envs] int32, K levels.  Rewrites d_finished
+ * [num_envs] and adds to d_stats [K + 1][3 + 2 num_agents]; every buffer naturally aligned, nothing more (16-byte aligned ones take the
+ * vector loads).  Takes no handle.  MCR_ERR_ARG, before any HIP call: a NULL required pointer, num_envs < 1, num_agents outside 1..8,
+ * K < 1.  Otherwise one launch on `stream`, no synchronisation. */
+int mcr_debug_level_stats(const uint8_t* d_done, const uint8_t* d_trunc /* may be NULL */,
+                          const double* d_ep_return /* [num_envs][num_agents] */, const int32_t* d_ep_len,
+                          const int32_t* d_level, int num_envs, int num_agents, int K,
+                          int32_t* d_finished /* [num_envs] */, double* d_stats /* [K+1][3+2N] */, void* stream);
 #define MCR_TIMING_SLOTS 8
 int mcr_timing_read(mcr_env* h, double* ms_out /*[MCR_TIMING_SLOTS]*/, int64_t* launches_out /*[MCR_TIMING_SLOTS]*/);
 

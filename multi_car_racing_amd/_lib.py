@@ -124,6 +124,7 @@ SYMBOLS = {
     "mcr_step_ordering_for": (_i, [_vp, _vp]),
     "mcr_bind_stream": (_i, [_vp, _vp]),
     "mcr_debug_overlap": (_i, [_vp, _i, _vp, _vp, _i, _vp]),
+    "mcr_debug_level_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "mcr_status": (_i, [_vp, _vp, _i]),
     "mcr_world_create": (_vp, [_i]),
     "mcr_world_destroy": (None, [_vp]),

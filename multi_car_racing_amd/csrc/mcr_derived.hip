@@ -37,14 +37,20 @@ void launch_pool_restage(mcr_env* h, hipStream_t st, int envs_per_group) {
 // Per-level episode statistics (k_levelstats.h): one launch, a wavefront per stats row, from the done / truncated rows the step just wrote.  It
 // reads level[] and must see the rows of the episodes that ENDED: in front of the re-stage, which hands an env that installed its next
 // episode that episode's row.  Behind the last sub-step of a macro-step only, like everything here: once per step call.
-static void launch_level_stats(mcr_env* h, hipStream_t st, const uint8_t* d_done, const uint8_t* d_trunc) {
-  if (!h->ls.stats) return;
-  const int waves = h->pool.K + 1, per_group = MCR_LS_LANES / 64;
-  hipLaunchKernelGGL(k_levelstats, dim3((waves + per_group - 1) / per_group), dim3(MCR_LS_LANES), 0, st, h->ls, d_done, d_trunc,
-                     (const double*)h->P.ep_return_out, (const int32_t*)h->P.ep_len_out, (const int32_t*)h->pool.level, h->P.B, h->P.N, h->pool.K);
+// launch_level_stats is THE launch — grid, block size, argument order — on plain device pointers: the step tail hands it the handle's, and
+// mcr_debug_level_stats the caller's (what tests/test_gpu_level_stats_kernel.py runs is this geometry, not a copy of it).
+static void launch_level_stats(hipStream_t st, const uint8_t* d_done, const uint8_t* d_trunc, const double* d_ep_return, const int32_t* d_ep_len,
+                               const int32_t* d_level, int B, int N, int K, int32_t* d_finished, double* d_stats) {
+  const int waves = K + 1, per_group = MCR_LS_LANES / 64;
+  hipLaunchKernelGGL(k_levelstats, dim3((waves + per_group - 1) / per_group), dim3(MCR_LS_LANES), 0, st, McrLevelStats{d_finished, d_stats}, d_done, d_trunc,
+                     d_ep_return, d_ep_len, d_level, B, N, K);
 }
 void launch_step_tail(mcr_env* h, hipStream_t st, const uint8_t* d_done, const uint8_t* d_trunc) {
-  launch_derived(h, st); launch_level_stats(h, st, d_done, d_trunc); launch_pool_restage(h, st, MCR_POOL_GROUP);
+  launch_derived(h, st);
+  if (h->ls.stats)
+    launch_level_stats(st, d_done, d_trunc, (const double*)h->P.ep_return_out, (const int32_t*)h->P.ep_len_out, (const int32_t*)h->pool.level,
+                       h->P.B, h->P.N, h->pool.K, h->ls.finished, h->ls.stats);
+  launch_pool_restage(h, st, MCR_POOL_GROUP);
 }
 
 extern "C" int mcr_state_obs_dim(int num_agents, int waypoints) {
@@ -186,5 +192,14 @@ extern "C" int mcr_set_level_stats(mcr_env* h, int32_t* d_finished_level, double
   if (!h->pool.blobs || !h->pool.level) { g_err = "mcr_set_level_stats: needs a level pool with a level buffer (mcr_set_episode_pool)"; return MCR_ERR_STATE; }
   if (!h->P.ep_return_out || !h->P.ep_len_out) { g_err = "mcr_set_level_stats: needs the episode statistics buffers (mcr_set_episode_stats)"; return MCR_ERR_STATE; }
   h->ls.finished = d_finished_level; h->ls.stats = d_stats;
+  return MCR_OK;
+}
+// the step tail's launch on caller-supplied rows: no handle, the argument checks in front of any HIP call, one launch, no synchronisation
+extern "C" int mcr_debug_level_stats(const uint8_t* d_done, const uint8_t* d_trunc, const double* d_ep_return, const int32_t* d_ep_len,
+                                     const int32_t* d_level, int num_envs, int num_agents, int K, int32_t* d_finished, double* d_stats, void* stream) {
+  if (!d_done || !d_ep_return || !d_ep_len || !d_level || !d_finished || !d_stats) { g_err = "mcr_debug_level_stats: null argument (only d_trunc may be NULL)"; return MCR_ERR_ARG; }
+  if (num_envs < 1 || num_agents < 1 || num_agents > MCR_MAX_AGENTS || K < 1) { g_err = "mcr_debug_level_stats: num_envs >= 1, num_agents 1..8, K >= 1"; return MCR_ERR_ARG; }
+  launch_level_stats((hipStream_t)stream, d_done, d_trunc, d_ep_return, d_ep_len, d_level, num_envs, num_agents, K, d_finished, d_stats);
+  HIPCHK(hipGetLastError());
   return MCR_OK;
 }

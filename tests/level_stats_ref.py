@@ -49,11 +49,16 @@ def weighted_level(seed, g, k, cdf_):
 
 class LevelStats:
     """the accumulator behind `vec.level_stats`: feed it the host copies of one step() — the `level` rows from BEFORE the step, the step's
-    done / truncated rows and the episode_return / episode_length buffers after it"""
+    done / truncated rows and the episode_return / episode_length buffers after it.  `start`: the [K + 1][3 + 2N] sums to go on from
+    (zeros without; reset() zeroes as the caller of mcr_set_level_stats does).  `truncated=None` in step(): nothing was truncated."""
 
-    def __init__(self, K, N):
+    def __init__(self, K, N, start=None):
         self.K, self.N = K, N
         self.stats = [[0.0] * (3 + 2 * N) for _ in range(K + 1)]
+        if start is not None:
+            start = np.asarray(start, np.float64)
+            assert start.shape == (K + 1, 3 + 2 * N)
+            self.stats = [[float(x) for x in row] for row in start]
         self.finished = None
 
     def reset(self):
@@ -70,7 +75,7 @@ class LevelStats:
             fin[e] = r
             row = self.stats[r]
             row[0] = row[0] + 1.0
-            row[1] = row[1] + (1.0 if truncated[e] else 0.0)
+            row[1] = row[1] + (1.0 if (truncated is not None and truncated[e]) else 0.0)
             row[2] = row[2] + float(int(episode_length[e]))
             for a in range(N):
                 x = float(episode_return[e][a])

@@ -4,7 +4,8 @@ host-staged control (the construction of tests/test_gpu_level_pool.py: a handle 
 hands out the pool rows the definition prescribes).
 
 TimeLimit 7 throughout: the envs end in phase, so many envs add to the same stats row in the same step — where the order of the additions
-shows in the last bits."""
+shows in the last bits.  (test_stats_with_staggered_endings_at_B_2118 puts them out of phase on purpose; the kernel alone, on synthetic rows
+at every batch size and ending pattern: tests/test_gpu_level_stats_kernel.py.)"""
 import ctypes
 
 import numpy as np
@@ -100,6 +101,74 @@ def test_stats_match_the_host_accumulator_bit_for_bit(torch_cuda, B, N, K, kw):
     assert (s[:, 1] == s[:, 0]).all() and (s[:, 2] == 7 * s[:, 0]).all()           # all truncated, 7 steps each
     assert (s[:K, 0] > 0).sum() >= 2
     assert abs(s[:, 3:3 + N].sum() - ret_sum) <= 1e-9 * max(1.0, abs(ret_sum))     # (rollout_stats adds with atomics: not bit-exact)
+    env.close()
+
+
+@pytest.mark.parametrize("N", [3, 8])
+def test_stats_with_many_cars(torch_cuda, N):
+    """B5_N2_K3 above at the car counts whose columns (C = 9, C = 19) a rollout had never stored"""
+    B, K = 5, 3
+    env = _env(B, N, K, level_stats=True, obs=False)
+    t = _Tracked(torch_cuda, env)
+    env.reset()
+    for _ in range(16):
+        t.step()
+    s = env.level_stats.cpu().numpy()
+    assert s.shape == (K + 1, 3 + 2 * N) and t.done_rows == 2 * B == s[:, 0].sum() == env.rollout_stats()[0]
+    assert (s[K] == 0).all() and (s[:, 2] == 7 * s[:, 0]).all() and (s[:K, 3 + N:][s[:K, 0] > 0] > 0).all()      # every car's square column took something
+    env.close()
+
+
+@pytest.mark.parametrize("streams", [1, 2])
+def test_stats_at_the_bench_level_count(torch_cuda, streams):
+    """B = 1100, K = 256 (the pool: one level row tiled, as test_set_level_weights does): 257 wavefronts, `done` rows the step itself wrote,
+    one full round on the row pass's 16-byte path plus a tail of 76; streams=2 is the default topology"""
+    from multi_car_racing_amd.vec_env import VecMultiCarRacing
+    B, K = 1100, 256
+    blobs = np.tile(_pool(1)[0][:1], (K, 1))
+    env = VecMultiCarRacing(B, 1, seed=SEED, levels=blobs, level_stats=True, obs=False, streams=streams, max_episode_steps=7)
+    t = _Tracked(torch_cuda, env)
+    env.reset()
+    for k in range(15):
+        d = t.step()
+        assert d.all() == d.any() == (k % 7 == 6)
+    s = env.level_stats.cpu().numpy()
+    assert t.done_rows == 2 * B == s[:K, 0].sum() and (s[K] == 0).all() and (s[:K, 0] > 0).sum() > K // 2
+    env.close()
+
+
+def test_stats_with_staggered_endings_at_B_2118(torch_cuda):
+    """B = 2118 — two full rounds of the row pass and a tail of 70 — with `done` rows the step wrote.  All envs reach the TimeLimit together
+    in step 6; reset_envs() on three subsets behind steps 7, 8 and 9 then puts them out of phase for good (an env reset behind step k ends in
+    step k + 7): envs 0 .. 1022 end in steps 13, 20, 27, the tail (>= 2048) in 14, 21, 28, envs 1025 .. 2047 in 15, 22, 29 and the pair
+    {1023, 1024} — the last env of round 0 and the first of round 1 — in step 16 and 23.  The step kinds this was built for are asserted."""
+    torch = torch_cuda
+    B, K = 2118, 3
+    env = _env(B, 1, K, level_stats=True, obs=False)
+    t = _Tracked(torch, env, rng_seed=5)
+    env.reset()
+    e = np.arange(B)
+    groups = {7: e >= 2048, 8: (e >= 1025) & (e < 2048), 9: (e == 1023) | (e == 1024)}
+    kinds = set()
+    for k in range(30):
+        d = t.step()
+        if not d.any():
+            kinds.add("none")
+        elif d.all():
+            kinds.add("all")
+        elif not d[:2048].any():
+            kinds.add("tail_only")
+        elif np.array_equal(np.flatnonzero(d), [1023, 1024]):
+            kinds.add("pair_1023_1024")
+        elif d[1024:2048].any() and not d[:1024].any():
+            kinds.add("round_1_not_round_0")
+        elif d[:1024].any() and not d[1024:].any():
+            kinds.add("round_0_only")
+        if k in groups:
+            env.reset_envs(torch.from_numpy(groups[k].astype(np.uint8)).to(env.device))
+    assert kinds == {"none", "all", "tail_only", "pair_1023_1024", "round_1_not_round_0", "round_0_only"}, kinds
+    s = env.level_stats.cpu().numpy()
+    assert s[:, 0].sum() == t.done_rows and (s[K] == 0).all() and (s[:K, 0] > 0).all()
     env.close()
 
 

@@ -21,6 +21,10 @@ NEW = {
     "mcr_level_weights": r"\bint\s+mcr_level_weights\s*\(\s*mcr_env\s*\*\s*h\s*,\s*const\s+double\s*\*\s*d_weights\s*,\s*int32_t\s*\*\s*d_fell_back\s*,\s*void\s*\*\s*stream\s*\)",
     "mcr_set_level_stats": r"\bint\s+mcr_set_level_stats\s*\(\s*mcr_env\s*\*\s*h\s*,\s*int32_t\s*\*\s*d_finished_level\s*,\s*double\s*\*\s*d_stats\s*\)",
     "mcr_level_stats_dim": r"\bint\s+mcr_level_stats_dim\s*\(\s*int\s+num_agents\s*\)",
+    "mcr_debug_level_stats": r"\bint\s+mcr_debug_level_stats\s*\(\s*const\s+uint8_t\s*\*\s*d_done\s*,\s*const\s+uint8_t\s*\*\s*d_trunc\s*,"
+                             r"\s*const\s+double\s*\*\s*d_ep_return\s*,\s*const\s+int32_t\s*\*\s*d_ep_len\s*,\s*const\s+int32_t\s*\*\s*d_level\s*,"
+                             r"\s*int\s+num_envs\s*,\s*int\s+num_agents\s*,\s*int\s+K\s*,\s*int32_t\s*\*\s*d_finished\s*,\s*double\s*\*\s*d_stats\s*,"
+                             r"\s*void\s*\*\s*stream\s*\)",
 }
 
 
@@ -195,3 +199,28 @@ def test_abi_errors_that_need_no_device(lib):
     assert [L.mcr_level_stats_dim(n) for n in range(1, 9)] == [3 + 2 * n for n in range(1, 9)]
     # mcr_pool_level keeps its two modes: "weighted" is no third one
     assert L.mcr_pool_level(ctypes.c_uint64(0), 0, 0, 4, 2) == MCR_ERR_ARG
+
+
+def test_debug_level_stats_argument_errors(lib):
+    """mcr_debug_level_stats refuses a NULL required pointer, num_envs < 1, num_agents outside 1..8 and K < 1 with MCR_ERR_ARG and a message —
+    before any HIP call: this box has no device, and the pointers are host memory no launch could take"""
+    L = lib.load()
+    assert lib.SYMBOLS["mcr_debug_level_stats"] == (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 3)
+    buf = np.zeros(64)
+    p = lib.ptr(buf)
+    good = dict(done=p, trunc=p, ret=p, len=p, level=p, B=4, N=2, K=3, fin=p, stats=p)
+
+    def call(**kw):
+        a = dict(good, **kw)
+        L.mcr_level_stats_dim(1)                               # (an OK call does not touch the message: put a known one there first)
+        assert L.mcr_level_stats_dim(0) == MCR_ERR_ARG and b"mcr_level_stats_dim" in L.mcr_last_error()
+        return L.mcr_debug_level_stats(a["done"], a["trunc"], a["ret"], a["len"], a["level"], a["B"], a["N"], a["K"], a["fin"], a["stats"], None)
+
+    for name in ("done", "ret", "len", "level", "fin", "stats"):
+        assert call(**{name: None}) == MCR_ERR_ARG, name
+        assert b"mcr_debug_level_stats" in L.mcr_last_error() and b"null" in L.mcr_last_error(), name
+    for kw in (dict(B=0), dict(B=-5), dict(N=0), dict(N=9), dict(N=-1), dict(K=0), dict(K=-1)):
+        assert call(**kw) == MCR_ERR_ARG, kw
+        assert b"mcr_debug_level_stats" in L.mcr_last_error() and b"num_agents 1..8" in L.mcr_last_error(), kw
+    # (d_trunc alone may be NULL: with every other argument good that call launches, which is the GPU tests' business)
+    assert call(trunc=None, K=0) == MCR_ERR_ARG and b"K >= 1" in L.mcr_last_error()
