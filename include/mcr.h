@@ -281,6 +281,28 @@ int mcr_set_range_obs(mcr_env* h, float* d_ranges, const float* dirs /* [rays][2
 /* Recompute the tensor from the CURRENT state on `stream` (after mcr_set_bodies / mcr_set_state_blob, which do not; tests).  MCR_ERR_STATE
  * when no buffer is set.  Only enqueues: the ranges read no backward / on-grass flags. */
 int mcr_range_obs_now(mcr_env* h, void* stream);
+/* Car-contact observations: who touched whom in the step, and how hard — what Box2D's PostSolve would report, reduced on the device from the
+ * car<->car manifold store every env keeps for warm starting (csrc/k_contactobs.h holds the definition and the arithmetic contract;
+ * csrc/k_carcontacts.h the record layout).  Two tensors, written by a kernel of its own on the caller's stream behind every mcr_reset, every env
+ * step of mcr_step / mcr_step_repeat and every state restore / copy, with obs_enabled 0 or 1:
+ *   d_mask    [B, N] int32: bit j (0..7) car j shared a stored touching manifold with this car; bit 8 this car's fixture in such a record is a
+ *             hull polygon (fixture index < 4), bit 9 it is a wheel (index >= 4)
+ *   d_impulse [B, N, N] f64: entry [a][j] the sum of the normal impulses of every manifold point between cars a and j, one f64 add per point
+ *             in store order — a host reproduces every bit (tests/contact_obs_ref.py); [a][j] and [j][a] are the same bits, the diagonal is 0.
+ * mcr_step_repeat: the kernel runs behind every sub-step; sub-step 0 starts from zero, the later ones continue the chain of adds from the
+ * value in the buffer and OR the masks.  An env that is not live at that point (never reset, frozen, parked behind the end of its episode)
+ * contributes nothing, so the env step in which an episode ends is never reported: with repeat = 1 and auto_reset a `done` row shows the
+ * first state of the new episode (no contacts).  After mcr_reset / mcr_load_states / mcr_copy_states every row is recomputed, without
+ * accumulation, from the env's store: what that state's last env step produced (a clone shows its source's).  Where the store overflowed
+ * (mcr_status word 2) the outputs describe the MCR_CC_MAX records that were kept: the store's documented deviation.
+ * Both pointers NULL turn the feature off (nothing is launched).  MCR_ERR_ARG: exactly one pointer NULL, a NULL handle, num_agents < 2, a
+ * handle created with car_contacts = 0.  Allowed at any time; takes effect with the next mcr_reset / mcr_step.  No HIP call. */
+int mcr_set_contact_obs(mcr_env* h, int32_t* d_mask /* [B][N] */, double* d_impulse /* [B][N][N] */);
+/* Recompute both tensors, without accumulation, from the stores as they stand, on `stream`.  MCR_ERR_STATE when no buffers are set.  Only enqueues. */
+int mcr_contact_obs_now(mcr_env* h, void* stream);
+/* the manifold store's sizes in u32 words, per env and per record (either pointer may be NULL); returns the records kept per env (MCR_CC_MAX).
+ * An env's store: word 0 the record count, 1 the overflow mark, 2-3 the joint order, then the records.  No handle, no GPU needed. */
+int mcr_contact_store_words(int32_t* words_per_env, int32_t* words_per_record);
 /* the four hull fixture polygons as the kernels hold them (b2PolygonShape::Set's vertex order): out [4][8][2] f32 body-frame vertices,
  * counts [4]; no handle, no GPU needed (tests pin the host restatement of the range-finder's channel 1 with it) */
 int mcr_hull_polygons(float* out, int32_t* counts);
@@ -475,6 +497,9 @@ int mcr_debug_read_partition(mcr_env* h, uint8_t* part_out, int32_t* clist_out);
 int mcr_debug_next_verdicts(mcr_env* h, int fill_value, uint8_t* out_or_null);
 /* number of touching car<->car fixture pairs (stored manifolds) per env after the last collide pass */
 int mcr_debug_read_contact_counts(mcr_env* h, int32_t* out /*[num_envs]*/);
+/* the raw manifold stores of all envs after the last step (mcr_contact_store_words: the sizes; csrc/k_carcontacts.h: the record layout);
+ * synchronises.  The input of the car-contact observation's host reference. */
+int mcr_debug_read_contacts(mcr_env* h, uint32_t* out /*[num_envs][words per env]*/);
 /* fresh_world = 0: the broadphase proxy ids of env `env`'s live episode on its one world (csrc/k_world.h) — out[0 .. T) tiles in track order,
  * then num_agents * 8 car fixtures (car * 8 + fixture; 0..3 hull polygons, 4..7 wheels); returns the count written; synchronises.  Tests
  * hold it against the oracle's literal b2DynamicTree (what mcr_world_proxy_ids is for the host-side twin). */
@@ -507,6 +532,13 @@ int mcr_debug_level_stats(const uint8_t* d_done, const uint8_t* d_trunc /* may b
                           const double* d_ep_return /* [num_envs][num_agents] */, const int32_t* d_ep_len,
                           const int32_t* d_level, int num_envs, int num_agents, int K,
                           int32_t* d_finished /* [num_envs] */, double* d_stats /* [K+1][3+2N] */, void* stream);
+/* The step's launch of the car-contact observation kernel (mcr_set_contact_obs above) on caller-made stores, for differential tests: the same
+ * launch function, hence the same grid and block size, fed with the caller's device buffers — d_store [num_envs][words per env] u32 — and
+ * no env records (every env is live).  accumulate != 0: continue from the contents of d_mask / d_impulse.  Buffers naturally aligned,
+ * nothing more.  Takes no handle.  MCR_ERR_ARG, before any HIP call: a NULL pointer, num_envs < 1, num_agents outside 2..8.  Otherwise one
+ * launch on `stream`, no synchronisation. */
+int mcr_debug_contact_obs(const uint32_t* d_store, int num_envs, int num_agents, int accumulate,
+                          int32_t* d_mask /* [num_envs][N] */, double* d_impulse /* [num_envs][N][N] */, void* stream);
 #define MCR_TIMING_SLOTS 8
 int mcr_timing_read(mcr_env* h, double* ms_out /*[MCR_TIMING_SLOTS]*/, int64_t* launches_out /*[MCR_TIMING_SLOTS]*/);
 

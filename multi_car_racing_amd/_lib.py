@@ -104,6 +104,9 @@ SYMBOLS = {
     "mcr_check_range_obs": (_i, [_vp, _i, ctypes.c_float]),
     "mcr_set_range_obs": (_i, [_vp, _vp, _vp, _i, ctypes.c_float]),
     "mcr_range_obs_now": (_i, [_vp, _vp]),
+    "mcr_set_contact_obs": (_i, [_vp, _vp, _vp]),
+    "mcr_contact_obs_now": (_i, [_vp, _vp]),
+    "mcr_contact_store_words": (_i, [_vp, _vp]),
     "mcr_hull_polygons": (_i, [_vp, _vp]),
     "mcr_driver_defaults": (_i, [_vp]),
     "mcr_check_drivers": (_i, [_i, _vp, ctypes.c_uint32]),
@@ -112,6 +115,8 @@ SYMBOLS = {
     "mcr_read_rollout_stats": (_i, [_vp, _vp, _i]),
     "mcr_render": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mcr_debug_read_contact_counts": (_i, [_vp, _vp]),
+    "mcr_debug_read_contacts": (_i, [_vp, _vp]),
+    "mcr_debug_contact_obs": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "mcr_debug_read_proxy_ids": (_i, [_vp, _i, _vp, _i]),
     "mcr_debug_read_env_records": (_i, [_vp, _vp, _i]),
     "mcr_debug_read_partition": (_i, [_vp, _vp, _vp]),
@@ -219,6 +224,13 @@ def episode_bytes():
 def state_obs_dim(num_agents, waypoints=6):
     """features per car of the state-vector observation (include/mcr.h: mcr_state_obs_dim): 18 + 2 * waypoints + 4 * (num_agents - 1)"""
     return check(load().mcr_state_obs_dim(int(num_agents), int(waypoints)), "mcr_state_obs_dim")
+
+
+def contact_store_words():
+    """(records kept per env, u32 words of an env's car<->car manifold store, words per record) — include/mcr.h: mcr_contact_store_words"""
+    per_env, per_rec = ctypes.c_int32(), ctypes.c_int32()
+    cap = load().mcr_contact_store_words(ctypes.byref(per_env), ctypes.byref(per_rec))
+    return int(cap), per_env.value, per_rec.value
 
 
 def unpack_episode(blob):

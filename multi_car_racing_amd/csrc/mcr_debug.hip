@@ -3,6 +3,7 @@
 #define MCR_DEVICE_FUNCTIONS_ONLY          // k_collide.h: col::overlap for k_debug_overlap, not the kernel (it lives in mcr_hip.hip)
 #include "mcr_env.h"
 #include "k_collide.h"
+#include "k_contactobs.h"
 #include <algorithm>
 
 // blockIdx.y = step offset: out[nsteps][n_cars][3]
@@ -101,6 +102,11 @@ extern "C" int mcr_debug_read_contact_counts(mcr_env* h, int32_t* out) {
   const size_t stride = MCR_CC_MAX * MCR_CC_WORDS + 4;
   HIPCHK(hipMemcpy2D(out, sizeof(int32_t), h->P.cc_store, stride * sizeof(uint32_t), sizeof(int32_t), h->cfg.num_envs, hipMemcpyDeviceToHost));
   return MCR_OK;
+}
+// the raw manifold stores (k_carcontacts.h: the record layout; mcr_contact_store_words: the sizes), the input of the car-contact observation's host reference
+extern "C" int mcr_debug_read_contacts(mcr_env* h, uint32_t* out) {
+  if (!h || !out) return MCR_ERR_ARG;
+  return read_back(out, h->P.cc_store, sizeof(uint32_t) * MCR_CC_STORE_WORDS * (size_t)h->cfg.num_envs);
 }
 extern "C" int mcr_debug_read_proxy_ids(mcr_env* h, int env, int32_t* out, int cap) {
   if (!h || !out || env < 0 || env >= h->cfg.num_envs) return MCR_ERR_ARG;

@@ -6,6 +6,7 @@
 #include "k_driver.h"
 #include "k_pool.h"
 #include "k_levelstats.h"
+#include "k_contactobs.h"
 #include <cmath>
 
 // The low-dimensional observation of the state a reset / a step ended with (k_stateobs.h), a wavefront per env on the caller's stream: behind
@@ -20,7 +21,24 @@ static void launch_range_obs(mcr_env* h, hipStream_t st) {
   if (!h->ro.out) return;
   hipLaunchKernelGGL(k_rangeobs, dim3(h->P.B), dim3(64), 0, st, h->P, h->ro);
 }
-void launch_derived(mcr_env* h, hipStream_t st) { launch_state_obs(h, st); launch_range_obs(h, st); }
+// The car-contact observation (k_contactobs.h): a wavefront per env over the manifold store as the last step left it.  run_contact_obs is THE
+// launch — grid, block size, argument order — on plain device pointers: launch_contact_obs hands it the handle's, mcr_debug_contact_obs the
+// caller's (what tests/test_gpu_contact_obs_kernel.py runs is this geometry, not a copy of it).  On the caller's stream behind launch_step, like
+// k_stateobs, outside the step's streams and outside a replayed step graph; it reads neither CU_FLAGS nor anything k_flags writes: no flush.
+// Nobody rewrites the store before it has run: the next step's contact pass starts behind something that step enqueues on the caller's
+// stream (its own launch there, W_BEGIN's post by its main dynamics, the fork event), hence behind this kernel (k_contactobs.h: Ordering).
+static void run_contact_obs(hipStream_t st, const uint32_t* d_store, const McrEnvState* d_env, int B, int N, bool accumulate, int32_t* d_mask, double* d_impulse) {
+  const int per_group = MCR_CO_LANES / 64;
+  hipLaunchKernelGGL(k_contactobs, dim3((B + per_group - 1) / per_group), dim3(MCR_CO_LANES), 0, st, d_store, d_env, B, N, accumulate ? 1 : 0,
+                     McrContactObs{d_mask, d_impulse});
+}
+void launch_contact_obs(mcr_env* h, hipStream_t st, bool accumulate) {
+  if (!h->co.mask) return;
+  run_contact_obs(st, h->P.cc_store, h->P.env, h->P.B, h->P.N, accumulate, h->co.mask, h->co.impulse);
+}
+// (the step's tail takes the first two only: step_one has launched the contact observation behind every sub-step, mcr_env.h)
+static void launch_state_range(mcr_env* h, hipStream_t st) { launch_state_obs(h, st); launch_range_obs(h, st); }
+void launch_derived(mcr_env* h, hipStream_t st) { launch_state_range(h, st); launch_contact_obs(h, st, false); }
 
 // Level pools (k_pool.h): every env that installed its staged episode gets its next one from the pool.  Launched where launch_state_obs goes — on
 // the caller's stream in front of and behind launch_reset and behind the LAST sub-step of a macro-step (a parked env re-spawns only there), whose
@@ -46,7 +64,7 @@ static void launch_level_stats(hipStream_t st, const uint8_t* d_done, const uint
                      d_ep_return, d_ep_len, d_level, B, N, K);
 }
 void launch_step_tail(mcr_env* h, hipStream_t st, const uint8_t* d_done, const uint8_t* d_trunc) {
-  launch_derived(h, st);
+  launch_state_range(h, st);
   if (h->ls.stats)
     launch_level_stats(st, d_done, d_trunc, (const double*)h->P.ep_return_out, (const int32_t*)h->P.ep_len_out, (const int32_t*)h->pool.level,
                        h->P.B, h->P.N, h->pool.K, h->ls.finished, h->ls.stats);
@@ -109,6 +127,38 @@ extern "C" int mcr_hull_polygons(float* out, int32_t* counts) {
     counts[k] = S.hull[k].n;
     for (int i = 0; i < 8; ++i) { out[(k * 8 + i) * 2] = S.hull[k].vx[i]; out[(k * 8 + i) * 2 + 1] = S.hull[k].vy[i]; }
   }
+  return MCR_OK;
+}
+
+// The car-contact observation (k_contactobs.h).  mcr_set_contact_obs only validates and stores: no HIP call; the pairing of the two pointers is
+// checked in front of the handle, so that it can be tested without a device.
+extern "C" int mcr_set_contact_obs(mcr_env* h, int32_t* d_mask, double* d_impulse) {
+  if ((d_mask == nullptr) != (d_impulse == nullptr)) { g_err = "mcr_set_contact_obs: the mask and the impulse buffer are set together or not at all (exactly one is null)"; return MCR_ERR_ARG; }
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!d_mask) { h->co = McrContactObs{nullptr, nullptr}; return MCR_OK; }
+  if (h->P.N < 2) { g_err = "mcr_set_contact_obs: needs num_agents >= 2"; return MCR_ERR_ARG; }
+  if (!h->P.car_contacts) { g_err = "mcr_set_contact_obs: the handle was created with car_contacts = 0 (no manifold store is kept)"; return MCR_ERR_ARG; }
+  h->co = McrContactObs{d_mask, d_impulse};
+  return MCR_OK;
+}
+extern "C" int mcr_contact_obs_now(mcr_env* h, void* stream) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!h->co.mask) { g_err = "mcr_contact_obs_now: no buffers set (mcr_set_contact_obs)"; return MCR_ERR_STATE; }
+  launch_contact_obs(h, (hipStream_t)stream, false);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+extern "C" int mcr_contact_store_words(int32_t* words_per_env, int32_t* words_per_record) {
+  if (words_per_env) *words_per_env = MCR_CC_STORE_WORDS;
+  if (words_per_record) *words_per_record = MCR_CC_WORDS;
+  return MCR_CC_MAX;
+}
+// the step's launch on caller-made stores: no handle (every env is live), the argument checks in front of any HIP call, one launch, no synchronisation
+extern "C" int mcr_debug_contact_obs(const uint32_t* d_store, int num_envs, int num_agents, int accumulate, int32_t* d_mask, double* d_impulse, void* stream) {
+  if (!d_store || !d_mask || !d_impulse) { g_err = "mcr_debug_contact_obs: null argument"; return MCR_ERR_ARG; }
+  if (num_envs < 1 || num_agents < 2 || num_agents > MCR_MAX_AGENTS) { g_err = "mcr_debug_contact_obs: num_envs >= 1, num_agents 2..8"; return MCR_ERR_ARG; }
+  run_contact_obs((hipStream_t)stream, d_store, nullptr, num_envs, num_agents, accumulate != 0, d_mask, d_impulse);
+  HIPCHK(hipGetLastError());
   return MCR_OK;
 }
 

@@ -218,6 +218,13 @@ struct McrLevelStats {
   double* stats;                // [K + 1][3 + 2N] the caller's: episodes, truncated, sum of lengths, per car sum of returns, sum of squares
 };
 
+// The car-contact observation (include/mcr.h: mcr_set_contact_obs; k_contactobs.h): launch argument of k_contactobs, kept in the handle (null
+// `mask`: off, nothing is launched).  Both pointers are set or neither is
+struct McrContactObs {
+  int32_t* mask;                // [B][N] the caller's: bit j car j was touched, bit 8 with the own hull, bit 9 with an own wheel
+  double* impulse;              // [B][N][N] the caller's: sum of the normal impulses between two cars
+};
+
 // status words (mapped host memory).  FATAL ones (give-up, verdict) make the next mcr_step return MCR_ERR_STATE; an OVERFLOW truncated a
 // capacity-bound list (documented deviation): the step goes on, mcr_status shows the count
 enum { ST_SPIN_GIVEUP = 0,     // a kernel gave up waiting for another stream's kernels (three-chain step: the contact pass of an env, a phase word)

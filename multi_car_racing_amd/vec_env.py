@@ -49,6 +49,20 @@ holds them (f64), `self.range_dirs` the float32 (cos, sin) table the kernel is g
 1 is `range_max`.  At a folded inner hairpin the inner border can lie inside the road: channel 0 is the first border segment a ray meets.
 After set_bodies() / set_state_blob() call refresh_ranges().
 
+Car-contact observation: `contact_obs=True` (needs `num_agents >= 2` and `car_contacts=True`) reports the one thing that makes the simulator
+multi-car — who touched whom in the step, and how hard — with `obs=True` or `obs=False`: `self.contact_mask`, a persistent int32 device
+tensor [B, N], also info["contact_mask"], and `self.contact_impulse`, float64 [B, N, N], also info["contact_impulse"], that a kernel of its
+own (csrc/k_contactobs.h: the definition) rewrites wherever `self.state` is rewritten, from the car<->car manifolds the env keeps for warm
+starting — what Box2D's PostSolve would report.  Bit j of `contact_mask[e, a]` (j < 8): a fixture of car a touched one of car j in the
+step; bit 8: with its hull; bit 9: with a wheel.  `contact_impulse[e, a, j]` is the sum of the normal impulses of all manifold points
+between the two cars, one f64 add per point in a fixed order (bit for bit reproducible: tests/contact_obs_ref.py); the matrix is symmetric to
+the bit and its diagonal is 0.  With `frame_skip=k` the kernel runs behind every env step: impulses are summed in step order, masks OR-ed.
+The env step in which an episode ends is never reported: the row of an env that auto-reset in the step describes the first state of its new
+episode (no contacts), like its `state` row, and with `frame_skip > 1` an env that ended early keeps what the env steps before the ending
+one summed.  After reset() / reset_envs() / load_states() / clone_envs() a row shows what the state's last env step produced (a clone: its
+source's).  Where an env's store overflowed (status word 2: more than 24 touching fixture pairs) the outputs describe the 24 kept records.
+refresh_contacts() recomputes both tensors from the stores as they stand.
+
 Action repeat: `frame_skip=k` (1..16) makes step() one MACRO-step, gym's FrameSkip_k(TimeLimit(env)) per env with the auto-reset outside it
 (include/mcr.h: mcr_step_repeat): the same actions drive up to k env steps of every env, an env stops at the step that ends its episode,
 `reward` is the f64 sum of the env steps' rewards in order, `done` their OR, `truncated` the ending step's; `max_episode_steps`,
@@ -186,11 +200,13 @@ class VecMultiCarRacing:
                  state_obs=False, state_waypoints=6, state_stride=5, frame_skip=1, levels=None, level_seed=None, level_order="random",
                  level_stats=False,
                  scripted_agents=None, driver_params=None, range_obs=False, range_rays=19, range_fov=math.pi, range_angles=None,
-                 range_max=100.0):
+                 range_max=100.0, contact_obs=False):
         # scripted drivers (module docstring): validated on the host before anything is created
         drv_mask = _drivers.driver_mask(num_agents, scripted_agents)
         drv_rows = _drivers.driver_params_array(num_agents, driver_params) if (drv_mask or driver_params is not None) else None
         range_table = range_obs_table(range_rays, range_fov, range_angles, range_max) if range_obs else None
+        if contact_obs and (int(num_agents) < 2 or not car_contacts):
+            raise ValueError("contact_obs=True needs num_agents >= 2 and car_contacts=True (there is no car<->car manifold store otherwise)")
         frame_skip = int(frame_skip)
         if not 1 <= frame_skip <= _lib.REPEAT_MAX:
             raise ValueError(f"frame_skip must be 1..{_lib.REPEAT_MAX}, got {frame_skip}")
@@ -319,6 +335,14 @@ class VecMultiCarRacing:
             self.range_shape = (self.N, 2, R)
             _lib.check(self.L.mcr_set_range_obs(self.h, ctypes.c_void_p(self.ranges.data_ptr()), _lib.ptr(self.range_dirs), R,
                                                 ctypes.c_float(self.range_max)), "mcr_set_range_obs")
+        # car-contact observation (include/mcr.h: mcr_set_contact_obs): [B, N] int32 and [B, N, N] f64, rewritten where self.state is and behind
+        # every env step of a macro-step
+        self.contact_mask = self.contact_impulse = None
+        if contact_obs:
+            self.contact_mask = torch.zeros((self.B, self.N), dtype=torch.int32, device=self.device)
+            self.contact_impulse = torch.zeros((self.B, self.N, self.N), dtype=torch.float64, device=self.device)
+            _lib.check(self.L.mcr_set_contact_obs(self.h, ctypes.c_void_p(self.contact_mask.data_ptr()),
+                                                  ctypes.c_void_p(self.contact_impulse.data_ptr())), "mcr_set_contact_obs")
         # scripted drivers (include/mcr.h: mcr_set_drivers): self.actions [B, N, 3] f32 is what step() is driven by when cars are scripted
         self.driver_params, self.scripted_agents = drv_rows, tuple(a for a in range(self.N) if drv_mask >> a & 1)
         self._drv_mask = drv_mask
@@ -682,6 +706,9 @@ class VecMultiCarRacing:
             info["state"] = self.state
         if self.ranges is not None:
             info["ranges"] = self.ranges
+        if self.contact_mask is not None:
+            info["contact_mask"] = self.contact_mask
+            info["contact_impulse"] = self.contact_impulse
         if self.level is not None:
             info["level"] = self.level
         if self.level_stats is not None:
@@ -722,6 +749,16 @@ class VecMultiCarRacing:
         st = torch.cuda.current_stream(self.device)
         _lib.check(self.L.mcr_range_obs_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_range_obs_now")
         return self.ranges
+
+    def refresh_contacts(self):
+        """Recompute `self.contact_mask` and `self.contact_impulse`, without accumulation, from the envs' manifold stores as they stand, on the
+        current stream (include/mcr.h: mcr_contact_obs_now); reset(), step() and the snapshot calls keep them current by themselves.  Returns
+        the two tensors; does not synchronise."""
+        if self.contact_mask is None:
+            raise _lib.McrError("created without contact_obs=True")
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_contact_obs_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_contact_obs_now")
+        return self.contact_mask, self.contact_impulse
 
     def _obs_ptr(self):
         """the observation buffer the raster writes: the frames, or the ring of a stacked format"""
