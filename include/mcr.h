@@ -90,6 +90,12 @@ int mcr_episodes_generate(uint32_t* mt_track, uint32_t* mt_global, int n, int nu
  * info_all [num_envs][12] or NULL), in place. */
 int mcr_episodes_generate_rows(uint32_t* mt_track_all, uint32_t* mt_global_all, const int32_t* ids, int n, int num_agents,
                                int direction_mode, void* blobs_all, int32_t* info_all, int num_threads);
+/* The blob of a CALLER's track: rows (alpha, beta, x, y) as mcr_episode_unpack hands them out, through everything mcr_episode_generate does
+ * behind its track walk (kerb flags, arrays, quads, tile hulls, block boxes, spawn poses) — a generated track fed back gives the generated blob
+ * byte for byte.  info_out[0..3] = T, P, 0, cw, or NULL.  MCR_ERR_ARG: a null argument, num_agents outside 1..8, T outside 20..MCR_TILE_CAP (the
+ * generator's own rule), an entry that is not finite, more than MCR_QUAD_CAP quads (road tiles + kerbs). */
+int mcr_episode_from_track(const double* track /*[T][4]*/, int T, int num_agents, int cw, const int32_t* car_order,
+                           void* blob_out, int32_t* info_out);
 /* Read-only views into a blob (tests / facade attributes such as env.track). */
 int mcr_episode_unpack(const void* blob, int32_t* T, int32_t* P, int32_t* cw, double* track_xyb /*[T*3]*/,
                        float* quads /*[P*8]*/, uint32_t* quad_meta /*[P]*/, double* spawn /*[8*3]*/,

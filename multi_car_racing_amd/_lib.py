@@ -62,6 +62,7 @@ SYMBOLS = {
     "mcr_episode_generate": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "mcr_episodes_generate": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i]),
     "mcr_episodes_generate_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i]),
+    "mcr_episode_from_track": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "mcr_episode_unpack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcr_stage_episodes": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mcr_pool_level": (ctypes.c_int32, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _i]),

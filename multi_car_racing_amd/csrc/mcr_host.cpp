@@ -343,34 +343,27 @@ void mcr_tile_hull(const float* fx, const float* fy, float* aabb4, float* va4, f
 
 extern "C" size_t mcr_episode_bytes(void) { return MCR_SLOT_BYTES; }
 
-extern "C" int mcr_episode_generate(uint32_t* mt_track, int num_agents, int cw, const int32_t* car_order,
-                                    void* blob_out, int32_t* info_out) {
-  if (!mt_track || !blob_out || !car_order || num_agents < 1 || num_agents > MCR_MAX_AGENTS) return MCR_ERR_ARG;
-  std::vector<TrackPt> lap;
-  int retries = 0;
-  int T = 0, P = 0;
-  std::vector<uint8_t> kerb;
-  for (;;) {
-    if (track_attempt(mt_track, lap)) {
-      T = (int)lap.size();
-      // kerb flags (:293-307)
-      kerb.assign(T, 0);
-      for (int i = 0; i < T; ++i) {
-        bool good = true; double oneside = 0;
-        for (int neg = 0; neg < kBorderMinCount; ++neg) {
-          double b1 = lap[wrap(i - neg, T)].beta, b2 = lap[wrap(i - neg - 1, T)].beta;
-          good = good && (fabs(b1 - b2) > kTurnRate * 0.2);
-          oneside += sgn(b1 - b2);
-        }
-        good = good && (fabs(oneside) == kBorderMinCount);
-        kerb[i] = good;
-      }
-      for (int i = 0; i < T; ++i) for (int neg = 0; neg < kBorderMinCount; ++neg) { int j = wrap(i - neg, T); kerb[j] = kerb[j] | kerb[i]; }
-      P = T; for (int i = 0; i < T; ++i) P += kerb[i];
-      if (T <= MCR_TILE_CAP && P <= MCR_QUAD_CAP && T >= 20) break;   // capacity overflow == failed attempt (never observed)
+// The episode blob of a finished lap, from the kerb flags onward (:293-406): kerb flags, the track arrays, the road / kerb quads, the tiles'
+// sensor hulls, the block boxes and the spawn poses.  false (nothing written) when the lap does not fit a slot: T outside
+// 20..MCR_TILE_CAP or more than MCR_QUAD_CAP quads.  Shared by mcr_episode_generate and mcr_episode_from_track.
+static bool episode_from_lap(const std::vector<TrackPt>& lap, int cw, const int32_t* car_order, int num_agents, void* blob_out, int* P_out) {
+  const int T = (int)lap.size();
+  if (T > MCR_TILE_CAP || T < 20) return false;
+  // kerb flags (:293-307)
+  std::vector<uint8_t> kerb(T, 0);
+  for (int i = 0; i < T; ++i) {
+    bool good = true; double oneside = 0;
+    for (int neg = 0; neg < kBorderMinCount; ++neg) {
+      double b1 = lap[wrap(i - neg, T)].beta, b2 = lap[wrap(i - neg - 1, T)].beta;
+      good = good && (fabs(b1 - b2) > kTurnRate * 0.2);
+      oneside += sgn(b1 - b2);
     }
-    ++retries;
+    good = good && (fabs(oneside) == kBorderMinCount);
+    kerb[i] = good;
   }
+  for (int i = 0; i < T; ++i) for (int neg = 0; neg < kBorderMinCount; ++neg) { int j = wrap(i - neg, T); kerb[j] = kerb[j] | kerb[i]; }
+  int P = T; for (int i = 0; i < T; ++i) P += kerb[i];
+  if (P > MCR_QUAD_CAP) return false;
   uint8_t* blob = (uint8_t*)blob_out;
   memset(blob, 0, MCR_SLOT_BYTES);
   McrSlotHeader* H = (McrSlotHeader*)(blob + MCR_OFF_HDR);
@@ -451,7 +444,31 @@ extern "C" int mcr_episode_generate(uint32_t* mt_track, int num_agents, int cw, 
     H->spawn[car][1] = pos_x + dx + (3 * sin(nt) * side);
     H->spawn[car][2] = pos_y + dy + (3 * cos(nt) * side);
   }
-  if (info_out) { info_out[0] = T; info_out[1] = P; info_out[2] = retries; info_out[3] = cw ? 1 : 0; }
+  *P_out = P;
+  return true;
+}
+
+extern "C" int mcr_episode_generate(uint32_t* mt_track, int num_agents, int cw, const int32_t* car_order,
+                                    void* blob_out, int32_t* info_out) {
+  if (!mt_track || !blob_out || !car_order || num_agents < 1 || num_agents > MCR_MAX_AGENTS) return MCR_ERR_ARG;
+  std::vector<TrackPt> lap;
+  int retries = 0, P = 0;
+  // capacity overflow == failed attempt (never observed)
+  while (!(track_attempt(mt_track, lap) && episode_from_lap(lap, cw, car_order, num_agents, blob_out, &P))) ++retries;
+  if (info_out) { info_out[0] = (int)lap.size(); info_out[1] = P; info_out[2] = retries; info_out[3] = cw ? 1 : 0; }
+  return MCR_OK;
+}
+
+// the blob of a caller's track: rows (alpha, beta, x, y) as mcr_episode_unpack hands them out (needs no GPU)
+extern "C" int mcr_episode_from_track(const double* track, int T, int num_agents, int cw, const int32_t* car_order,
+                                      void* blob_out, int32_t* info_out) {
+  if (!track || !blob_out || !car_order || num_agents < 1 || num_agents > MCR_MAX_AGENTS || T < 20 || T > MCR_TILE_CAP) return MCR_ERR_ARG;
+  for (int i = 0; i < T * 4; ++i) if (!std::isfinite(track[i])) return MCR_ERR_ARG;
+  std::vector<TrackPt> lap(T);
+  for (int i = 0; i < T; ++i) lap[i] = {track[i * 4 + 0], track[i * 4 + 1], track[i * 4 + 2], track[i * 4 + 3]};
+  int P = 0;
+  if (!episode_from_lap(lap, cw, car_order, num_agents, blob_out, &P)) return MCR_ERR_ARG;
+  if (info_out) { info_out[0] = T; info_out[1] = P; info_out[2] = 0; info_out[3] = cw ? 1 : 0; }
   return MCR_OK;
 }
 

@@ -45,6 +45,34 @@ def make_levels(K, num_agents=2, seed=0, direction_mode=2, threads=None):
     return blobs, info
 
 
+def from_tracks(tracks, num_agents=2, direction="CCW", car_order=None):
+    """Episode blobs of the caller's own tracks (include/mcr.h: mcr_episode_from_track): uint8 [K, episode_bytes] for `levels=`.
+    tracks: K arrays [T, 4] float64, rows (alpha, beta, x, y) — beta the heading of the tile's edge, the track running along (-sin beta, cos beta);
+    direction: 'CCW' / 'CW', or one per track; car_order: the grid order of the cars (default 0 .. num_agents-1)."""
+    tracks = list(tracks)
+    if len(tracks) < 1:
+        raise ValueError("from_tracks needs at least one track")
+    N = int(num_agents)
+    if not 1 <= N <= _lib.MAX_AGENTS:
+        raise ValueError(f"num_agents must be 1..{_lib.MAX_AGENTS}, got {num_agents}")
+    dirs = [direction] * len(tracks) if isinstance(direction, str) else list(direction)
+    if len(dirs) != len(tracks) or any(d not in ("CCW", "CW") for d in dirs):
+        raise ValueError("direction must be 'CCW' or 'CW', or one of them per track")
+    order = np.ascontiguousarray(np.arange(N) if car_order is None else car_order, dtype=np.int32)
+    if order.shape != (N,):
+        raise ValueError(f"car_order must have shape [{N}], got {list(order.shape)}")
+    L = _lib.load()
+    blobs = np.zeros((len(tracks), _lib.episode_bytes()), np.uint8)
+    for j, (tr, d) in enumerate(zip(tracks, dirs)):
+        tr = np.ascontiguousarray(tr, dtype=np.float64)
+        if tr.ndim != 2 or tr.shape[1] != 4:
+            raise ValueError(f"track {j} must have shape [T, 4] (alpha, beta, x, y), got {list(tr.shape)}")
+        rc = L.mcr_episode_from_track(_lib.ptr(tr), len(tr), N, int(d == "CW"), _lib.ptr(order), _lib.ptr(blobs[j]), None)
+        if rc != 0:
+            raise ValueError(f"track {j}: T must be 20..{_lib.TILE_CAP}, every entry finite, and tiles plus kerbs at most {_lib.QUAD_CAP} (T = {len(tr)})")
+    return blobs
+
+
 def pool_level(seed, global_env, episode, K, order="random"):
     """the pool row that the env with global index `global_env` plays in its `episode`-th episode (0: the first)"""
     if order == "weighted":

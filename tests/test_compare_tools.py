@@ -1,9 +1,9 @@
 """CPU: the comparators of tests/util.py that the GPU suite's "bit-exact against the oracle" rests on must BITE — assert_state on a stand-in
-env stacked from oracles with exactly one element changed, assert_frame around its edge budget, Follower against the seeding rule."""
+env stacked from oracles with exactly one element changed, assert_frame around its edge budget, Follower against the seeding rule, hull_positions against the oracle's positions(), assert_f32_bits on single bits and on NaNs."""
 import numpy as np
 import pytest
 
-from tests.util import Follower, STATE_ARRAYS, assert_frame, assert_state, oracle_episode, random_actions
+from tests.util import Follower, STATE_ARRAYS, assert_f32_bits, assert_frame, assert_state, hull_positions, oracle_episode, random_actions
 
 TILE_CAP = 512
 
@@ -109,3 +109,40 @@ def test_follower_plays_the_episodes_of_the_seeding_rule(oracle):
     f.new_episode()
     assert f.ep is not first and not np.array_equal(f.ep["track"][:50], first["track"][:50]), "the second episode is the streams' next draw"
     f.o.close()
+
+
+def test_hull_positions_equals_the_oracles_positions(lib, oracle):
+    """bit for bit along a short N = 3 rollout (cars turning and moving: the rotation of the local centre matters)"""
+    L = lib.load()
+    N = 3
+    o = oracle.OracleEnv(N)
+    o.reset(oracle_episode(oracle, N, 11, 0), render=False)
+    rng = np.random.RandomState(2)
+    for k in range(25):
+        got = hull_positions(L, o.state()["bodies"]); want = o.positions()
+        assert got.dtype == np.float32 and got.shape == (N, 2)
+        assert np.array_equal(got.view(np.uint32), want.astype(np.float32).view(np.uint32)), f"step {k}: {got.tolist()} vs {want.tolist()}"
+        o.step(random_actions(rng, 1, N)[0], render=False)
+    assert np.abs(o.state()["bodies"][:, 0, 2] - o.state()["bodies"][0, 0, 2]).max() > 0, "the cars never turned differently"
+    stacked = np.stack([o.state()["bodies"]] * 2)
+    assert np.array_equal(hull_positions(L, stacked)[1], o.positions().astype(np.float32)), "batched input"
+    o.close()
+
+
+def test_assert_f32_bits_bites():
+    rng = np.random.RandomState(4)
+    want = rng.randn(3, 2, 2, 5).astype(np.float32)
+    want[1, 0, 1, 2] = np.nan; want[2, 1, 0, 0] = 0.0
+    assert_f32_bits(want.copy(), want, "identical")
+    other_nan = want.copy(); other_nan.view(np.uint32)[1, 0, 1, 2] = 0xffc01234          # another payload, the sign set: the same class
+    assert np.isnan(other_nan[1, 0, 1, 2])
+    assert_f32_bits(other_nan, want, "NaN payloads")
+    for idx, value, flat in (((2, 1, 1, 4), None, 9), ((2, 1, 0, 0), np.float32(-0.0), 0), ((1, 0, 1, 2), np.float32(1.0), 7), ((0, 1, 0, 3), np.float32(np.nan), 3)):
+        got = want.copy()
+        got[idx] = np.nextafter(want[idx], np.float32(np.inf)) if value is None else value
+        with pytest.raises(AssertionError, match=f"first at env {idx[0]} car {idx[1]} index {flat}: got "):
+            assert_f32_bits(got, want, "one value")
+    with pytest.raises(AssertionError, match="float32 expected"):
+        assert_f32_bits(want.astype(np.float64), want, "dtype")
+    with pytest.raises(AssertionError, match="shapes"):
+        assert_f32_bits(want[:2], want, "shape")

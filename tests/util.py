@@ -349,3 +349,43 @@ def lap_touching_pair(run, front, back, gap=4.9):
 def playfield_ok(o, playfield=2000 / 6.0):
     """no hull of oracle env `o` outside the playfield (multi_car_racing.py:503-507)"""
     return bool((np.abs(o.positions()) <= playfield).all())
+
+
+# ----------------------------------------------------------------------------------------------------------------- derived observations
+def hull_positions(L, bodies):
+    """The hull's body origin of every car, xf_of (csrc/mcr_common.h) restated in numpy float32: p = c - R(a) lc, with (s, c) =
+    mcr_sincos_host(a), lc the hull's local centre (mcr_mass_props), every product, sum and difference rounded to float32 on its own (no
+    contraction).  bodies [..., 5, 6] f32 (cx cy a vx vy w; body 0 is the hull) -> [..., 2] f32: what mcr_get_positions / the oracle's
+    positions() return, from get_state() alone.  L: the loaded libmcr_hip.so."""
+    import ctypes
+    f32 = np.float32
+    mp = np.zeros(6, f32)
+    L.mcr_mass_props(mp.ctypes.data_as(ctypes.c_void_p))
+    lx, ly = f32(mp[2]), f32(mp[3])
+    b = np.asarray(bodies, f32)
+    hull = b[..., 0, :].reshape(-1, 6)
+    out = np.zeros((len(hull), 2), f32)
+    s, c = ctypes.c_float(), ctypes.c_float()
+    with np.errstate(all="ignore"):
+        for i, h in enumerate(hull):
+            L.mcr_sincos_host(ctypes.c_float(float(h[2])), ctypes.byref(s), ctypes.byref(c))
+            qs, qc = f32(s.value), f32(c.value)
+            out[i, 0] = f32(h[0]) - f32(f32(qc * lx) - f32(qs * ly))
+            out[i, 1] = f32(h[1]) - f32(f32(qs * lx) + f32(qc * ly))
+    return out.reshape(b.shape[:-2] + (2,))
+
+
+def assert_f32_bits(got, want, what=""):
+    """float32 tensors [envs, cars, ...] compared BY BITS: +0.0 and -0.0 differ, one ulp differs.  NaN is a class: the NaN positions must
+    coincide, their payloads and signs are ignored.  Names the first differing (env, car, index within the car's row) with both values."""
+    got = np.asarray(got); want = np.asarray(want)
+    assert got.dtype == np.float32 and want.dtype == np.float32, f"{what}: dtypes {got.dtype} / {want.dtype}, float32 expected"
+    assert got.shape == want.shape and got.ndim >= 2, f"{what}: shapes {got.shape} / {want.shape}"
+    gn, wn = np.isnan(got), np.isnan(want)
+    bad = (gn != wn) | (~gn & ~wn & (np.ascontiguousarray(got).view(np.uint32) != np.ascontiguousarray(want).view(np.uint32)))
+    if bad.any():
+        flat = bad.reshape(bad.shape[0], bad.shape[1], -1)
+        e, a, i = (int(v) for v in np.argwhere(flat)[0])
+        g = got.reshape(flat.shape)[e, a, i]; w = want.reshape(flat.shape)[e, a, i]
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} values differ; first at env {e} car {a} index {i}: got {g!r} "
+                             f"(0x{int(np.float32(g).view(np.uint32)):08x}) want {w!r} (0x{int(np.float32(w).view(np.uint32)):08x})")
