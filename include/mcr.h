@@ -389,6 +389,11 @@ int mcr_set_bodies(mcr_env* h, const float* bodies /*[B,N,5,6]*/);
  * takes another path) launches the pending scans first: the values returned here are always those of the last step. */
 int mcr_get_env_state(mcr_env* h, double* reward, int32_t* tile_visited_count, uint8_t* backward,
                       uint8_t* on_grass, double* t, uint16_t* tile_flags, int32_t* num_tiles);
+/* Run the backward / on-grass scans (csrc/k_flags.h) NOW, on the state as it stands, on `stream`: the pending scans of the last step first,
+ * then one scan per car of every env — after mcr_set_bodies / a state restore, which leave the flags of the last step in place (tests).
+ * An env that is not active, or that no step has followed since its reset(), keeps its flags.  No touch verdicts, no other state is
+ * written.  MCR_ERR_ARG for a NULL handle (checked before any HIP call).  Only enqueues: no synchronisation. */
+int mcr_flags_now(mcr_env* h, void* stream);
 /* hull.position per car [B,N,2] f32 */
 int mcr_get_positions(mcr_env* h, float* pos);
 /* mass KATs: hull invMass, invI, localCenter.x, .y, wheel invMass, invI (host computation) */

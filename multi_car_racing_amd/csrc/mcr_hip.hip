@@ -302,11 +302,25 @@ static void launch_view(mcr_env* h, int kid, int slots, hipStream_t st, const Mc
 // the scans read or write (CU_FLAGS, poses, env records, episode slots) launches them first, on the stream its own work goes to — every state
 // getter / setter, reset, render, and a step that takes another path than the last one.  The scans depend on nothing a later call changes:
 // the poses, env records and episode slots are the ones the step ended with until the next step's dynamics writes back.
+// k_flags' geometry: one wavefront per car of the batch, whatever the launch's role (a wavefront whose env is not the role's returns)
+static void launch_flags(hipStream_t st, const McrParams& P) { hipLaunchKernelGGL(k_flags, dim3(P.B * P.N), dim3(64), 0, st, P); }
 void flush_flags(mcr_env* h, hipStream_t st) {
   if (!h->flags_pending) return;
   h->flags_pending = false;
   if (h->P.debug & DEBUG_DROP_PENDING_FLAGS) return;     // (tests): the pending launch is DROPPED — stale flags show that the results came through it
-  hipLaunchKernelGGL(k_flags, dim3(h->flags_P.B * h->flags_P.N), dim3(64), 0, st, h->flags_P);
+  launch_flags(st, h->flags_P);
+}
+// The scan NOW, on the state as it stands (after mcr_set_bodies / a state restore, which launch nothing; tests): the pending launch first, then
+// every env's cars — ROLE_ALL, so that no partition mark skips an env —, no touch verdicts (they are the step's business).  Only enqueues.
+extern "C" int mcr_flags_now(mcr_env* h, void* stream) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  flush_flags(h, st);
+  McrParams P = h->P;
+  P.role = ROLE_ALL; P.part_next = nullptr; P.flags_deferred = 0;
+  launch_flags(st, P);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
 }
 // the synchronous calls (state getters / setters): the device's work is complete and so is the pending bookkeeping (null stream, waited for)
 hipError_t sync_state(mcr_env* h) {
@@ -396,7 +410,7 @@ static void step_single_stream(mcr_env* h, const McrParams& P, hipStream_t st, i
   }
   if (draw) launch_view(h, 2, B, st, with(P, ROLE_ALL, [](McrParams& q) { q.use_vorder = 1; }), 0);
   if (P.term_cnt) { launch_view(h, 7, B, st, with(P, ROLE_TERMINAL), 0); hipLaunchKernelGGL(k_term_finish, dim3(1), dim3(256), 0, st, P); }
-  if (view_flags) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, st, P);
+  if (view_flags) launch_flags(st, P);
 }
 
 // Grid sizes of the three-chain step, whichever way its streams are ordered (launch_step computes them once)
@@ -506,7 +520,7 @@ static void step_phase_words(mcr_env* h, const McrParams& Pin, const StepGrids& 
   if (view_flags && !fiv) hipLaunchKernelGGL(k_flags_list, dim3(g.lg_flags), dim3(64), 0, st, with(P, ROLE_DEFERRED));
   // Beyond three cars per env the third stream's chain (bookkeeping of B*N cars, then B*N views) is the longer one and the caller's
   // has slack: the main envs' bookkeeping — which the raster does not depend on — moves here, between the resume chain and its raster
-  if (flags_on_caller) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, st, with(P, ROLE_MAIN));
+  if (flags_on_caller) launch_flags(st, with(P, ROLE_MAIN));
   // ... and the step's join (+ the terminal entries' frames and count)
   if (draw) launch_view(h, 7, P.term_cnt ? 2 * B : B, st, with(P, P.auto_reset ? ROLE_DEFERRED_RESPAWN : ROLE_DEFERRED, [&](McrParams& q) { q.await_tail = 1; q.flags_blocks = fiv; }), 0);
   hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, h->s_defer, with(P, ROLE_MAIN), (int)W_DYN, -1);
@@ -516,7 +530,7 @@ static void step_phase_words(mcr_env* h, const McrParams& Pin, const StepGrids& 
     h->flags_P = with(P, ROLE_MAIN, [](McrParams& q) { q.part_next = nullptr; q.flags_deferred = 0; }); h->flags_pending = true;
   }
   else if (vif) hipLaunchKernelGGL(k_flags_viewprep, dim3(dyn_blocks + B * N), dim3(64), 0, h->s_defer, with(P, ROLE_MAIN), dyn_blocks);      // view records + bookkeeping: one launch
-  else if (view_flags && !flags_on_caller) hipLaunchKernelGGL(k_flags, dim3(B * N), dim3(64), 0, h->s_defer, with(P, ROLE_MAIN));
+  else if (view_flags && !flags_on_caller) launch_flags(h->s_defer, with(P, ROLE_MAIN));
   if (draw) launch_view(h, 2, B, h->s_defer, with(P, ROLE_MAIN, [](McrParams& q) { q.use_vorder = 1; }), 0);
   hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, h->s_defer, with(P, ROLE_MAIN), (int)W_MAIN);
   if (!draw) hipLaunchKernelGGL(k_await, dim3(1), dim3(64), 0, st, with(P, ROLE_MAIN), (int)W_SIDE, (int)W_MAIN);

@@ -760,6 +760,12 @@ class VecMultiCarRacing:
         _lib.check(self.L.mcr_contact_obs_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_contact_obs_now")
         return self.contact_mask, self.contact_impulse
 
+    def refresh_flags(self):
+        """Run the backward / on-grass scans on the CURRENT state on the current stream (include/mcr.h: mcr_flags_now) — after set_bodies() /
+        set_state_blob(), which do not; step() keeps the flags current by itself.  get_env_state() shows the result; does not synchronise."""
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_flags_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_flags_now")
+
     def _obs_ptr(self):
         """the observation buffer the raster writes: the frames, or the ring of a stacked format"""
         if not self.obs_enabled:

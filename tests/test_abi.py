@@ -107,3 +107,11 @@ def test_synth_actions_host_is_counter_based(lib):
     assert (big[..., 0] >= -1).all() and (big[..., 0] < 1).all() and (big[..., 1:] >= 0).all() and (big[..., 1:] < 1).all()
     assert abs(big[..., 0].mean()) < 0.03 and abs(big[..., 1].mean() - 0.5) < 0.02 and abs(big[..., 2].mean() - 0.5) < 0.02
     assert abs(np.corrcoef(big[:, 0, 1], big[:, 1, 1])[0, 1]) < 0.06
+
+
+def test_flags_now_checks_its_handle_before_any_hip_call(lib):
+    """mcr_flags_now (the backward / on-grass scans on the state as it stands): declared, bound, and a NULL handle is MCR_ERR_ARG on a machine
+    without a device"""
+    L = lib.load()
+    assert "mcr_flags_now" in _declared() and "mcr_flags_now" in lib.SYMBOLS
+    assert L.mcr_flags_now(None, None) == -1 and b"null handle" in L.mcr_last_error()
