@@ -394,6 +394,22 @@ int mcr_get_env_state(mcr_env* h, double* reward, int32_t* tile_visited_count, u
  * An env that is not active, or that no step has followed since its reset(), keeps its flags.  No touch verdicts, no other state is
  * written.  MCR_ERR_ARG for a NULL handle (checked before any HIP call).  Only enqueues: no synchronisation. */
 int mcr_flags_now(mcr_env* h, void* stream);
+/* Test / facade plumbing, the counterparts of mcr_get_state's `wheels` and of mcr_get_env_state; synchronous like mcr_set_bodies, the
+ * pending flag scans launched and waited for first.
+ * mcr_set_wheels: phase and omega (columns 3 and 4) of every wheel; columns 0..2, the controls, are ignored.
+ * mcr_set_env_state: self.reward, self.t and the tile flags — any pointer may be NULL; those three fields only: visit counts, the
+ * backward / on-grass flags and every other field of the env record stay as they are. */
+int mcr_set_wheels(mcr_env* h, const double* wheels /*[B,N,4,5]*/);
+int mcr_set_env_state(mcr_env* h, const double* reward /*[B,N]*/, const double* t /*[B]*/, const uint16_t* tile_flags /*[B,MCR_TILE_CAP]*/);
+/* Draw every env's observation NOW, from the state as it stands, into d_obs on `stream` (after the state setters, which draw nothing;
+ * tests): the pending flag scans, one pass that rewrites every active env's view records and car polygons from the state arrays — the
+ * score label's value is the current reward, the backwards flag the current driving_backward: the frame render("state_pixels") of the
+ * reference would return now — and ONE main raster launch (csrc/k_view.h) over all envs, in the handle's observation format (RGB, or
+ * GRAY with stack 1; d_obs [B,N] frames of mcr_obs_bytes_per_view).  An env that is not active keeps its frame.  Changes no state a step
+ * reads (the next step rewrites the records) and is not part of a step: outside the step's streams, lists and graphs.
+ * MCR_ERR_ARG for a NULL handle or buffer (checked before any HIP call).  MCR_ERR_STATE before the first mcr_reset, on a handle without
+ * obs_enabled, with a stacked format (the ring's slots are the step's), inside a caller's stream capture.  Only enqueues: no synchronisation. */
+int mcr_obs_now(mcr_env* h, uint8_t* d_obs, void* stream);
 /* hull.position per car [B,N,2] f32 */
 int mcr_get_positions(mcr_env* h, float* pos);
 /* mass KATs: hull invMass, invI, localCenter.x, .y, wheel invMass, invI (host computation) */

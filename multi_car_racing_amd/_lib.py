@@ -88,6 +88,9 @@ SYMBOLS = {
     "mcr_set_bodies": (_i, [_vp, _vp]),
     "mcr_get_env_state": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcr_flags_now": (_i, [_vp, _vp]),
+    "mcr_set_wheels": (_i, [_vp, _vp]),
+    "mcr_set_env_state": (_i, [_vp, _vp, _vp, _vp]),
+    "mcr_obs_now": (_i, [_vp, _vp, _vp]),
     "mcr_get_positions": (_i, [_vp, _vp]),
     "mcr_mass_props": (None, [_vp]),
     "mcr_sincos_host": (None, [ctypes.c_float, _vp, _vp]),

@@ -85,7 +85,7 @@ __device__ __forceinline__ bool centre_range(float lo, float hi, int c0, int c1,
 #define LABEL_CELL_W 4.0f
 #define LABEL_CELL_H 5.0f
 #define LABEL_Y0 32.5f
-#define LABEL_MAX_CHARS 6
+#define LABEL_MAX_CHARS 11                 // "-1999999999": mcr_label_value passes |reward| < 2e9
 static __device__ const uint8_t LABEL_GLYPHS[11][7] = {
     {0x0E, 0x11, 0x13, 0x15, 0x19, 0x11, 0x0E},   // 0
     {0x04, 0x0C, 0x04, 0x04, 0x04, 0x04, 0x0E},   // 1

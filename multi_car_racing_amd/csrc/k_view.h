@@ -107,7 +107,7 @@ __device__ __forceinline__ uint32_t hud_flag_mask(int cg, int r4) {
 // Two parts: hud_prep (no memory traffic) and hud_store (six streaming stores per lane); the caller consumes its own outstanding loads
 // between them.  On gfx9 stores count in vmcnt like loads: a wait for a load issued BEHIND them would wait for the stores' acknowledgements
 // from a memory system the raster keeps saturated.
-struct HudState { uint32_t xm[7], rm[7], rows_any, lvalid; unsigned long long lmask; int cg, rsel; };
+struct HudState { uint32_t xm[7], rm[7], rows_any, lvalid; unsigned long long lmask, lmask2; int cg, rsel; };
 __device__ __forceinline__ HudState hud_prep(const float* __restrict__ vr, const uint8_t* __restrict__ glyphs, const int lane, const bool flag_on) {
   HudState H;
   // ---- gauges (vertical_ind x 5, horiz_ind x 2, :643-663), lane i < 7: columns [a, b1) and rows [ra, rb1) whose pixel centres the rectangle
@@ -127,9 +127,9 @@ __device__ __forceinline__ HudState hud_prep(const float* __restrict__ vr, const
   unsigned long long bcd = 0ull; int nd = 0;
   for (unsigned t = (unsigned)(neg ? -(long long)value : value); ; ) { const unsigned q = t / 10u; bcd |= (unsigned long long)(t - q * 10u) << (4 * nd); ++nd; t = q; if (t == 0u) break; }
   nd = max(nd, 4 - neg);                                                     // zero padding of %04i (the sign counts)
-  bool lit = false;
-  {
-    const float fx = ((float)(1 + (lane & 15)) + 0.5f) * (1000.0f / 96.0f) - LABEL_X0, fy = (((float)(4 + (lane >> 4)) + 0.5f) * (800.0f / 96.0f) - LABEL_Y0) * (1.0f / LABEL_CELL_H);
+  auto label_lit = [&](const int x0) -> bool {                               // pixel column x0 + lane % 16, GL row 4 + lane / 16
+    bool lit = false;
+    const float fx = ((float)(x0 + (lane & 15)) + 0.5f) * (1000.0f / 96.0f) - LABEL_X0, fy = (((float)(4 + (lane >> 4)) + 0.5f) * (800.0f / 96.0f) - LABEL_Y0) * (1.0f / LABEL_CELL_H);
     const int j = (int)floorf(fx * (1.0f / LABEL_ADV));                      // character
     const int c = (int)floorf((fx - (float)j * LABEL_ADV) * (1.0f / LABEL_CELL_W));
     if (fx >= 0.0f && fy >= 0.0f && fy < 7.0f && j < nd + neg && c < 5) {
@@ -137,8 +137,13 @@ __device__ __forceinline__ HudState hud_prep(const float* __restrict__ vr, const
       const int g = (neg && j == 0) ? 10 : (int)((bcd >> (4 * max(d, 0))) & 15ull);
       lit = (((uint32_t)glyphs[g * 7 + 6 - (int)floorf(fy)] >> (4 - c)) & 1u) != 0u;
     }
-  }
-  H.lmask = __ballot(lit);
+    return lit;
+  };
+  H.lmask = __ballot(label_lit(1));
+  // a label of 7 .. LABEL_MAX_CHARS characters (|reward| of a million and more: no rollout, but mcr_label_value passes it) reaches
+  // beyond column 16: a second window, x 17..32 (the 11th character ends at window x 306, left of pixel centre 29) — a uniform branch
+  H.lmask2 = 0ull;
+  if (nd + neg > 6) H.lmask2 = __ballot(label_lit(17));
   const int cg = lane >= 24 ? (lane >= 48 ? 23 : lane - 24) : lane;
   H.cg = cg; H.rsel = lane >= 24 ? 1 : 0;
   // x part of the gauges: the bytes of my 4 pixels inside [a, b1).  M(k) = the low k bytes = the high word of 0xffffffff << 8k
@@ -153,8 +158,15 @@ __device__ __forceinline__ HudState hud_prep(const float* __restrict__ vr, const
   }
   if (H.lmask || flag_on) H.rows_any |= 0xf0u;
   // label bits of my group: bit (row - 4) * 16 + (x - 1) of lmask, x = 4 cg + j; x = 0 and x > 16 are outside the sampled window
+  // (a long label: hud_label2, bit (row - 4) * 16 + (x - 17) of lmask2)
   H.lvalid = cg == 0 ? 0xeu : cg < 4 ? 0xfu : cg == 4 ? 0x1u : 0u;
   return H;
+}
+// A long label's pixels of my group in GL row 4 + r4 (hud_prep: lmask2, columns 17..32), as a nibble like the first window's: group 4 holds
+// column 16 of the first window and 17..19 of the second, group 8 column 32
+__device__ __forceinline__ uint32_t hud_label2(const HudState& H, const int cg, const int r4) {
+  const uint32_t row = (uint32_t)(H.lmask2 >> (r4 * 16)) & 0xffffu;
+  return cg == 4 ? (row << 1) & 0xeu : (cg > 4 && cg <= 8) ? (row >> (4 * cg - 17)) & 0xfu : 0u;
 }
 // GRAY: the colour classes of my 4 pixels in GL row `row` (= 2k + rsel): black bar (:638-642), gauges, then label and flag in GL rows 4..7.
 // The same lines as the RGB trip of hud_store, which keeps its own copy: routed through this function the RGB instantiations' instructions
@@ -171,6 +183,7 @@ __device__ __forceinline__ uint32_t hud_classes(const HudState& H, const int k, 
     const int r4 = row - 4;
     uint32_t nib = cg == 0 ? ((uint32_t)(H.lmask >> (r4 * 16)) << 1) : (uint32_t)(H.lmask >> (r4 * 16 + 4 * min(cg, 4) - 1));
     nib &= H.lvalid;
+    if (H.lmask2) nib |= hud_label2(H, cg, r4);
     const uint32_t lm = ((nib * 0x00204081u) & 0x01010101u) * 0xffu;
     win = (win & ~lm) | (0x01010101u & lm);
     if (flag_on) {
@@ -217,6 +230,7 @@ __device__ __forceinline__ void hud_store(const HudState& H, uint32_t* __restric
         const int r4 = row - 4;
         uint32_t nib = cg == 0 ? ((uint32_t)(H.lmask >> (r4 * 16)) << 1) : (uint32_t)(H.lmask >> (r4 * 16 + 4 * min(cg, 4) - 1));
         nib &= H.lvalid;
+        if (H.lmask2) nib |= hud_label2(H, cg, r4);
         const uint32_t lm = ((nib * 0x00204081u) & 0x01010101u) * 0xffu;
         win = (win & ~lm) | (0x01010101u & lm);
         if (flag_on) {

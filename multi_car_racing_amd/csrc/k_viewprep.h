@@ -55,3 +55,14 @@ __device__ __forceinline__ void term_prepare(const McrParams& p, const int env) 
   if (lane < p.N) viewprep_car(*p.shapes, p.term_carf, p.term_card, p.term_cap * p.N, tidx * p.N + lane, p.term_viewp, p.term_carpoly, p.h_ratio, p.term_env[tidx].t);
 }
 __global__ __launch_bounds__(64) void k_viewprep(McrParams p) { viewprep_block(p, (int)blockIdx.x); }
+// mcr_obs_now: one lane per car of EVERY active env (ROLE_ALL semantics: no partition mark, and an env no step has followed since its reset
+// is not skipped) — the record and polygons of the state as it stands, the label's value and the flag word as they stand (what a
+// render("state_pixels") between two steps shows: the current reward, the current driving_backward)
+__global__ __launch_bounds__(64) void k_viewprep_now(McrParams p) {
+  const int ci = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  if (ci >= p.BN) return;
+  const McrEnvState es = p.env[ci / p.N];
+  if (!es.active) return;
+  viewprep_car(*p.shapes, p.carf, p.card, p.BN, ci, p.viewp, p.carpoly, p.h_ratio, es.t);
+  view_score(p.viewp + (size_t)ci * MCR_VIEWP_FLOATS, p.card[CD_REWARD * p.BN + ci], p.caru[CU_FLAGS * p.BN + ci]);
+}

@@ -322,6 +322,25 @@ extern "C" int mcr_flags_now(mcr_env* h, void* stream) {
   HIPCHK(hipGetLastError());
   return MCR_OK;
 }
+// The frame NOW, of the state as it stands (after the state setters, which launch nothing; tests): the pending scans first (the flag word is
+// drawn), one pass over every active env's cars for the view records, car polygons, label value and flag word (k_viewprep_now), then ONE main
+// raster launch over all B envs — ROLE_ALL, work slot = env index, no raster order list, the plain RGB / GRAY instantiation — into the
+// caller's buffer.  Outside the step's streams, lists and graphs; the records it writes are rewritten by the next step.  Only enqueues.
+extern "C" int mcr_obs_now(mcr_env* h, uint8_t* d_obs, void* stream) {
+  if (!h || !d_obs) { g_err = "mcr_obs_now: null argument"; return MCR_ERR_ARG; }
+  if (!h->cfg.obs_enabled) { g_err = "mcr_obs_now needs obs_enabled"; return MCR_ERR_STATE; }
+  if (!h->any_reset) { g_err = "mcr_obs_now before reset()"; return MCR_ERR_STATE; }
+  if (h->obs_gray && h->ring.k > 1) { g_err = "mcr_obs_now with a stacked observation format (the ring's slots belong to the step)"; return MCR_ERR_STATE; }
+  hipStream_t st = (hipStream_t)stream;
+  if (capturing(st)) { g_err = "mcr_obs_now inside a stream capture"; return MCR_ERR_STATE; }
+  flush_flags(h, st);
+  McrParams P = h->P;
+  P.role = ROLE_ALL; P.split = 0; P.use_vorder = 0; P.actions = nullptr; P.obs = d_obs;
+  hipLaunchKernelGGL(k_viewprep_now, dim3((P.BN + 63) / 64), dim3(64), 0, st, P);
+  mcr_view_launch(0, P.B, st, P, h->view_stamps, 0, nullptr, nullptr, h->obs_gray, h->ring);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
 // the synchronous calls (state getters / setters): the device's work is complete and so is the pending bookkeeping (null stream, waited for)
 hipError_t sync_state(mcr_env* h) {
   hipError_t e = hipDeviceSynchronize();

@@ -4,6 +4,7 @@
 #include "mcr_env.h"
 #include "k_envcopy.h"
 #include <cassert>
+#include <cstddef>
 #include <cstring>
 
 // ---------------------------------------------------------------------------- state access (synchronous)
@@ -48,6 +49,32 @@ extern "C" int mcr_set_bodies(mcr_env* h, const float* bodies) {
   }
   HIPCHK(hipMemcpy(h->P.carf, cf.data(), cf.size() * 4, hipMemcpyHostToDevice));
   h->bp_fresh = true; h->verdict_fresh = false;      // teleported cars: their broadphase proxies are re-created by the next contact pass
+  return MCR_OK;
+}
+
+// mcr_get_state's `wheels` back: phase and omega of every wheel (columns 3 and 4; the controls in columns 0..2 are not state of their own)
+extern "C" int mcr_set_wheels(mcr_env* h, const double* wheels) {
+  if (!h || !wheels) return MCR_ERR_ARG;
+  HIPCHK(sync_state(h));
+  const size_t BN = h->P.BN;
+  std::vector<double> cd(8 * BN);
+  static_assert(CD_PHASE == CD_OMEGA + 4 && CD_REWARD == CD_PHASE + 4, "omega and phase of the four wheels are eight consecutive rows");
+  for (size_t c = 0; c < BN; ++c) for (int k = 0; k < 4; ++k) {
+    const double* o = wheels + (c * 4 + k) * 5;
+    cd[(size_t)k * BN + c] = o[4]; cd[(size_t)(4 + k) * BN + c] = o[3];
+  }
+  HIPCHK(hipMemcpy(h->P.card + CD_OMEGA * BN, cd.data(), cd.size() * 8, hipMemcpyHostToDevice));
+  return MCR_OK;
+}
+
+// mcr_get_env_state's reward, t and tile_flags back — those three fields and nothing else (visit counts, flags and the rest of the env record stay)
+extern "C" int mcr_set_env_state(mcr_env* h, const double* reward, const double* t, const uint16_t* tile_flags) {
+  if (!h) return MCR_ERR_ARG;
+  HIPCHK(sync_state(h));
+  const size_t BN = h->P.BN; const int B = h->P.B;
+  if (reward) HIPCHK(hipMemcpy(h->P.card + CD_REWARD * BN, reward, BN * 8, hipMemcpyHostToDevice));
+  if (t) HIPCHK(hipMemcpy2D((uint8_t*)h->P.env + offsetof(McrEnvState, t), sizeof(McrEnvState), t, sizeof(double), sizeof(double), (size_t)B, hipMemcpyHostToDevice));
+  if (tile_flags) HIPCHK(hipMemcpy(h->P.tile_flags, tile_flags, sizeof(uint16_t) * MCR_TILE_CAP * (size_t)B, hipMemcpyHostToDevice));
   return MCR_OK;
 }
 

@@ -28,7 +28,8 @@ Observation format: `obs_format="rgb"` (default) hands out [B, N, 96, 96, 3] fra
 itself: [B, N, 96, 96].  With `frame_stack=k > 1` it is also gym's FrameStack(k): [B, N, k, 96, 96], oldest frame first, and after a reset or
 an auto-reset the env's first frame k times (gym's rule; SB3's VecFrameStack zero-fills instead).  The stack is a strided VIEW of a ring of
 2k frames per agent that the raster writes in place (include/mcr.h: mcr_set_obs_format): nothing is shifted or copied, and the view
-changes with every step — keep the tensor step() returns, not an older one.
+changes with every step — keep the tensor step() returns, not an older one.  reset() and step() draw; the state setters (set_bodies(),
+set_wheels(), set_env_state(), set_state_blob()) do not: refresh_obs() draws the state as it stands (frame_stack 1).
 
 State-vector observation: `state_obs=True` adds what a non-pixel policy trains on, with `obs=True` or `obs=False`: `self.state`, a persistent
 float32 device tensor [B, N, F] that a kernel of its own (csrc/k_stateobs.h: the feature table) rewrites after every reset() / reset_envs() /
@@ -766,6 +767,24 @@ class VecMultiCarRacing:
         st = torch.cuda.current_stream(self.device)
         _lib.check(self.L.mcr_flags_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_flags_now")
 
+    def refresh_obs(self, out=None):
+        """Draw every env's observation from the CURRENT state on the current stream (include/mcr.h: mcr_obs_now) — after set_bodies() /
+        set_wheels() / set_env_state() / set_state_blob(), which draw nothing; reset() and step() draw by themselves.  The score label shows
+        the current reward, the backwards flag the current driving_backward.  Writes into `out` (a contiguous uint8 tensor of `self.obs`'s
+        shape on the device) or, by default, into `self.obs`; returns that tensor; does not synchronise.  Not with frame_stack > 1."""
+        if not self.obs_enabled:
+            raise _lib.McrError("created with obs=False")
+        if self._ring is not None:
+            raise _lib.McrError("refresh_obs() with a stacked observation format: the ring's slots belong to step()")
+        if out is None:
+            out = self.obs
+        elif (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.device != self.device or tuple(out.shape) != tuple(self.obs.shape)
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 tensor {list(self.obs.shape)} on {self.device}")
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_obs_now(self.h, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(st.cuda_stream)), "mcr_obs_now")
+        return out
+
     def _obs_ptr(self):
         """the observation buffer the raster writes: the frames, or the ring of a stacked format"""
         if not self.obs_enabled:
@@ -854,6 +873,20 @@ class VecMultiCarRacing:
         b = np.ascontiguousarray(bodies, np.float32)
         assert b.shape == (self.B, self.N, 5, 6)
         _lib.check(self.L.mcr_set_bodies(self.h, _lib.ptr(b)), "mcr_set_bodies")
+
+    def set_wheels(self, wheels):
+        """get_state()["wheels"] back: phase and omega (columns 3, 4) of every wheel; the controls (columns 0..2) are ignored.  Synchronous."""
+        w = np.ascontiguousarray(wheels, np.float64)
+        assert w.shape == (self.B, self.N, 4, 5)
+        _lib.check(self.L.mcr_set_wheels(self.h, _lib.ptr(w)), "mcr_set_wheels")
+
+    def set_env_state(self, reward=None, t=None, tile_flags=None):
+        """get_env_state()'s reward [B, N] f64, t [B] f64 and tile_flags [B, TILE_CAP] u16 back (None: left alone) — those fields only.  Synchronous."""
+        r = None if reward is None else np.ascontiguousarray(reward, np.float64)
+        tt = None if t is None else np.ascontiguousarray(t, np.float64)
+        f = None if tile_flags is None else np.ascontiguousarray(tile_flags, np.uint16)
+        assert (r is None or r.shape == (self.B, self.N)) and (tt is None or tt.shape == (self.B,)) and (f is None or f.shape == (self.B, _lib.TILE_CAP))
+        _lib.check(self.L.mcr_set_env_state(self.h, _lib.ptr(r), _lib.ptr(tt), _lib.ptr(f)), "mcr_set_env_state")
 
     def get_env_state(self):
         B, N = self.B, self.N

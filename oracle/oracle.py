@@ -483,6 +483,26 @@ class OracleEnv:
         f.restype = None
         f(self.h, ctypes.c_double(t))
 
+    def set_reward(self, reward):
+        f = self.L.orc_set_reward
+        f.restype = None
+        f(self.h, _p(np.ascontiguousarray(reward, dtype=np.float64)))
+
+    def set_touched(self, touched):
+        """the tiles' touched bits [T] (what recolours a tile's road_poly entries, :102-104)"""
+        f = self.L.orc_set_touched
+        f.restype = None
+        tt = np.ascontiguousarray(touched, dtype=np.uint8)
+        assert tt.shape == (self.T,)
+        f(self.h, _p(tt))
+
+    def set_backward(self, backward):
+        f = self.L.orc_set_backward
+        f.restype = None
+        bw = np.ascontiguousarray(backward, dtype=np.uint8)
+        assert bw.shape == (self.N,)
+        f(self.h, _p(bw))
+
     def solve_only(self, steps=1):
         self.L.orc_set_trig_mode(self.trig_mode)
         self.L.orc_solve_only(self.h, ctypes.c_int(steps))

@@ -372,12 +372,13 @@ SENTINEL = np.float32(-7.25e11)
 
 
 class Rig:
-    """One handle on `tracks` (env e plays track e) with the observation under test on — observe: "state", "range", "driver" or None (no
+    """One handle on `tracks` (env e plays track e) with the observation under test on — observe: "state", "range", "driver", "pixels" (obs=True:
+    the raster is under test, tests/test_gpu_view_kernel.py; env_kw: further settings of the handle, e.g. obs_format) or None (no
     derived observation: the step's own bookkeeping is under test, tests/test_gpu_flags_kernel.py); the tests
     point it at buffers of their own through the C ABI.  The buffer of the last launch stays referenced here (`held`), and the driver's
     registered action buffer (`scratch`) lives as long as the rig: the handle never holds a pointer to freed memory."""
 
-    def __init__(self, lib, tracks, N, observe, steps=0, env_offset=0, every=None, spread=False):
+    def __init__(self, lib, tracks, N, observe, steps=0, env_offset=0, every=None, spread=False, **env_kw):
         import torch
         from multi_car_racing_amd import levels
         from tests.util import make_env
@@ -385,10 +386,10 @@ class Rig:
         every = tracks if every is None else every               # the pool: env e of a handle with env_offset o plays every[(o + e) % K]
         self.B = len(tracks)
         self.held = self.scratch = None
-        on = {"state": dict(state_obs=True), "range": dict(range_obs=True), "driver": dict(driver_params={}), None: {}}[observe]
+        on = {"state": dict(state_obs=True), "range": dict(range_obs=True), "driver": dict(driver_params={}), "pixels": env_kw, None: {}}[observe]
         self.tracks = tracks
         blobs = np.concatenate([levels.from_tracks([rows], N, "CW" if cw else "CCW") for _, rows, cw in every])
-        self.env = make_env(self.B, N, 0, levels=blobs, level_order="cycle", obs=False, streams=1, env_offset=env_offset, **on)
+        self.env = make_env(self.B, N, 0, levels=blobs, level_order="cycle", obs=observe == "pixels", streams=1, env_offset=env_offset, **on)
         self.env.reset()
         if spread:
             self.env.set_bodies(spread_bodies(tracks, N, self.env.get_state()["bodies"]))

@@ -115,3 +115,16 @@ def test_flags_now_checks_its_handle_before_any_hip_call(lib):
     L = lib.load()
     assert "mcr_flags_now" in _declared() and "mcr_flags_now" in lib.SYMBOLS
     assert L.mcr_flags_now(None, None) == -1 and b"null handle" in L.mcr_last_error()
+
+
+def test_obs_now_and_the_state_setters_check_their_arguments_before_any_hip_call(lib):
+    """mcr_obs_now (the main raster on the state as it stands), mcr_set_wheels, mcr_set_env_state: declared, bound, and a NULL handle — for
+    mcr_obs_now also a NULL buffer — is MCR_ERR_ARG on a machine without a device"""
+    L = lib.load()
+    for name in ("mcr_obs_now", "mcr_set_wheels", "mcr_set_env_state"):
+        assert name in _declared() and name in lib.SYMBOLS
+    frame = (ctypes.c_uint8 * 16)()
+    assert L.mcr_obs_now(None, frame, None) == -1 and b"null argument" in L.mcr_last_error()
+    assert L.mcr_obs_now(ctypes.c_void_p(16), None, None) == -1 and b"null argument" in L.mcr_last_error()      # (the handle is not looked at)
+    assert L.mcr_set_wheels(None, frame) == -1 and L.mcr_set_wheels(ctypes.c_void_p(16), None) == -1
+    assert L.mcr_set_env_state(None, None, None, None) == -1
