@@ -19,8 +19,10 @@
 // contributes nothing: its rows are zeroed by a launch that does not accumulate and left as they are by one that does.  So the sub-step in
 // which an episode ends is never reported: the env is parked behind it (frame_skip > 1) or already shows its new episode, whose reset pass
 // emptied the store (the last sub-step; frame_skip = 1).
-// ST_CC_OVERFLOW: more than MCR_CC_MAX fixture pairs touched and k_collide dropped the excess (the documented deviation of the store);
-// the outputs describe the MCR_CC_MAX stored records.
+// ST_CC_OVERFLOW: more than MCR_CC_MAX fixture pairs touched and k_collide dropped the excess — DESIGN.md §3.1, THE DROP RULE: the first
+// MCR_CC_MAX touching pairs are kept in the order k_collide finds them (pairs of cars ascending by (a, b), a < b; within a pair of cars
+// ascending by fixture of a * 8 + fixture of b), the others take no part in the step; a function of the entry poses alone, mirrored by the
+// oracle's orc_set_contact_cap.  The outputs describe the MCR_CC_MAX stored records.
 //
 // Shape: one wavefront per env, lane l = matrix cell (a, j) = (l >> 3, l & 7).  The env index is made wave-uniform (readfirstlane), so the
 // count and every record's key, point count and impulses are scalar loads shared by the 64 lanes; every lane walks the <= MCR_CC_MAX

@@ -783,7 +783,7 @@ __device__ __forceinline__ V2 spawn_centre(const double* sp, const Rot q, const 
 // N = 1) — none of the contact code is compiled in, and the contact-free loops keep the registers and the schedule they get alone
 // UNI (with CC): the launch holds ONE env per wavefront (the contact chain, ROLE_CONTACT): the contact sweeps run in the uniform form above
 template <bool CC, bool UNI = false, bool COOP = false>
-__device__ __forceinline__ void dynamics_block(const McrParams& p, const int mode, const int blk) {
+__device__ __forceinline__ void dynamics_block(const McrParams& p, const int mode, const int blk, const int sub = -1) {
   static_assert(CC || !UNI, "the uniform contact sweeps are part of the contact build");
   using namespace dyn;
   DYN_STAMP(0);
@@ -795,8 +795,11 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
   __shared__ float xms[64];
   __shared__ int xmap[64];                            // per lane: slot of wheel w's registers at bits 2w (island order of the joints)
   const int g = blk * 64 + threadIdx.x;
-  const int env = mcr_env_of_slot(p, mcr_dyn_slot(p, blk), true), agent = g % p.G;
   const int env_end = p.env0 + p.nenv;
+  // sub >= 0 (k_dynamics_passes below, a packed wavefront whose envs hold more manifolds than the LDS pool): this pass takes the wavefront's envs
+  // 2 sub and 2 sub + 1 only; the other lanes are nobody's, like the lanes beyond the batch
+  const int env = (sub >= 0 && (((int)threadIdx.x / p.G) >> 1) != sub) ? env_end : mcr_env_of_slot(p, mcr_dyn_slot(p, blk), true);
+  const int agent = g % p.G;
   bool lane_ok = env < env_end && agent < p.N;
   const int ci = lane_ok ? env * p.N + agent : 0;
   const int BN = p.BN;
@@ -936,7 +939,8 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
     int incl = need;
     for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
     pool_base = incl - need;
-    if (agent == 0 && pool_base + ccn > DYN_VC_POOL) { ccn = DYN_VC_POOL - pool_base; if (ccn < 0) ccn = 0; store[1] = 2u; mcr_raise(p, ST_CC_OVERFLOW); }
+    // (a guard: no launch reaches it — the list launches take MCR_SIDE_ENVS_PER_WAVE envs per wavefront, a packed wavefront beyond the pool goes to k_dynamics_passes, the reset pass steps cars on the spawn grid)
+    if (lane_ok && agent == 0 && pool_base + ccn > DYN_VC_POOL) { ccn = DYN_VC_POOL - pool_base; if (ccn < 0) ccn = 0; store[1] = 2u; mcr_raise(p, ST_CC_OVERFLOW); }
     ccn = __shfl(ccn, leader_lane); pool_base = __shfl(pool_base, leader_lane);
     // island order of this car's joints (3,2,1,0 unless a contact says otherwise); wq[t] = the wheel slot t holds.  (Everything that
     // knows about the permutation lives in the contact branches: the contact-free loops keep their registers.)
@@ -1718,6 +1722,31 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
 
 }
 
+// The wavefront's LDS pool holds DYN_VC_POOL = MCR_SIDE_ENVS_PER_WAVE * MCR_CC_MAX constraint records, and a packed launch (ROLE_ALL: the
+// single-stream step and the reset pass, behind k_collide) puts 64 / G envs into a wavefront.  Do the envs of wavefront `blk` hold more
+// manifolds than that together?  Wave-uniform.  From the stores' counts alone, whatever the envs' state: k_dynamics and k_dynamics_passes
+// ask one after the other and must get the same answer, and the first one changes env records (an env ends, thaws, re-spawns), never a count.
+// (The reset pass, mode 1, steps only cars that stand on the spawn grid, 6 apart across and 5 track points along: no manifold at all, and no
+// second launch for it — one launch is 3 us of a single-stream step's 343; the guard in dynamics_block stays behind it.)
+__device__ __forceinline__ bool dyn_pool_exceeded(const McrParams& p, const int mode, const int blk) {
+  const int epw = 64 / p.G;
+  if (mode != 0 || p.role != ROLE_ALL || !p.car_contacts || p.N < 2 || epw <= MCR_SIDE_ENVS_PER_WAVE) return false;
+  const int e = p.env0 + blk * epw + (int)threadIdx.x;
+  int need = 0;
+  if ((int)threadIdx.x < epw && e < p.env0 + p.nenv) { const uint32_t n = p.cc_store[(size_t)e * (MCR_CC_MAX * MCR_CC_WORDS + 4)]; need = n < (uint32_t)MCR_CC_MAX ? (int)n : MCR_CC_MAX; }
+  for (int o = 1; o < 64; o <<= 1) need += __shfl_xor(need, o);
+  return __builtin_amdgcn_readfirstlane(need) > DYN_VC_POOL;
+}
+// ... then k_dynamics leaves the wavefront alone and this kernel, launched behind it with the same grid, steps its envs
+// MCR_SIDE_ENVS_PER_WAVE at a time, one pass of dynamics_block after the other: what an env computes does not depend on who shares its
+// wavefront, and no manifold is left out for want of room.  A kernel of its own, so that k_dynamics<true> keeps the registers it has without
+// the loop (230 VGPRs, two wavefronts per SIMD; with the loop 256 + 76 AGPRs, one); every other wavefront leaves after one load.
+__global__ __launch_bounds__(64) void k_dynamics_passes(McrParams p, int mode) {
+  if (!dyn_pool_exceeded(p, mode, (int)blockIdx.x)) return;
+  const int passes = (64 / p.G + MCR_SIDE_ENVS_PER_WAVE - 1) / MCR_SIDE_ENVS_PER_WAVE;
+  for (int s = 0; s < passes; ++s) { dynamics_block<true>(p, mode, (int)blockIdx.x, s); __syncthreads(); }
+}
+
 // main launches (ROLE_ALL / ROLE_MAIN): 64 / G envs per wavefront (the list launches call dynamics_block from k_list_chain.h)
 template <bool CC>
 __global__ __launch_bounds__(64) void k_dynamics(McrParams p, int mode) {
@@ -1732,6 +1761,7 @@ __global__ __launch_bounds__(64) void k_dynamics(McrParams p, int mode) {
     for (int i = 0; i < 4; ++i) if (p.next_counts[i]) *p.next_counts[i] = 0;
     if (p.term_cnt_next) { p.term_cnt_next[0] = 0; p.term_cnt_next[1] = 0; p.term_cnt_next[2] = 0; }
   }
+  if constexpr (CC) { if (dyn_pool_exceeded(p, mode, (int)blockIdx.x)) return; }     // k_dynamics_passes, launched behind this kernel, steps this wavefront's envs
   dynamics_block<CC>(p, mode, (int)blockIdx.x);
   if (mode == 0 && p.soft_sync && p.role == ROLE_MAIN) {
     // W_DYN from inside the kernel (the phase-word step's main dynamics): every workgroup (= wavefront) releases what it stored (agent scope:

@@ -275,7 +275,12 @@ static hipEvent_t get_event(mcr_env* h) {
 #define LAUNCH_LDS(kid_, kernel, grid, block, lds_, st, ...) TIMED(kid_, st, hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_, st, __VA_ARGS__))
 
 // a launch of the dynamics over all envs: with or without the contact code (k_dynamics.h)
-#define LAUNCH_DYN(kid_, cc_, grid, st, ...) do { if (cc_) LAUNCH(kid_, k_dynamics<true>, grid, 64, st, __VA_ARGS__); else LAUNCH(kid_, k_dynamics<false>, grid, 64, st, __VA_ARGS__); } while (0)
+// (with the contact code: k_dynamics_passes behind it, for the wavefronts whose envs hold more manifolds than their LDS pool — k_dynamics.h)
+static void launch_dyn_cc(int grid, hipStream_t st, const McrParams& P, int mode) {
+  hipLaunchKernelGGL(k_dynamics<true>, dim3(grid), dim3(64), 0, st, P, mode);
+  if (mode == 0) hipLaunchKernelGGL(k_dynamics_passes, dim3(grid), dim3(64), 0, st, P, mode);
+}
+#define LAUNCH_DYN(kid_, cc_, grid, st, ...) do { if (cc_) TIMED(kid_, st, launch_dyn_cc(grid, st, __VA_ARGS__)); else LAUNCH(kid_, k_dynamics<false>, grid, 64, st, __VA_ARGS__); } while (0)
 
 void mcr_view_launch(int variant, int grid, hipStream_t st, const McrParams& P, unsigned long long* stamps, int only_just_reset, hipEvent_t stop, hipEvent_t start,
                      bool gray, const McrObsRing& ring);   // mcr_view.hip

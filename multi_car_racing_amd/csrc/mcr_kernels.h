@@ -229,7 +229,7 @@ struct McrContactObs {
 // capacity-bound list (documented deviation): the step goes on, mcr_status shows the count
 enum { ST_SPIN_GIVEUP = 0,     // a kernel gave up waiting for another stream's kernels (three-chain step: the contact pass of an env, a phase word)
        ST_VERDICT = 1,         // the contact pass disagreed with the one-step-ahead touch verdict
-       ST_CC_OVERFLOW = 2,     // more touching car<->car fixture pairs than the manifold store / the LDS pool holds: the excess was dropped
+       ST_CC_OVERFLOW = 2,     // more touching car<->car fixture pairs than the manifold store holds: the excess was dropped (the drop rule)
        ST_EVENT_OVERFLOW = 3,  // more tile begin events in one env-step than the replay buffer holds
        ST_FROZEN = 4,          // an env ended its episode before the host had staged the next one: it froze (zero outputs) until the episode arrived
        MCR_STATUS_WORDS = 8,

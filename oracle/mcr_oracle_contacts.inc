@@ -9,24 +9,42 @@
 //   * fixture pair (A,B): A = lower (car, fixture) where fixture 0..3 = hull polys, 4..7 = wheels
 //   * contact order: ascending (carA, fixA, carB, fixB)
 //   * joint order inside a car: 3,2,1,0 (island DFS order from the newest body — see DESIGN.md)
+//
+// The product's manifold store holds MCR_CC_MAX records per env.  orc_set_contact_cap(h, cap) mirrors that (DESIGN.md §3.1, THE DROP RULE):
+// of the touching fixture pairs of a step, found at the poses entering it, the first `cap` are kept in the order k_collide finds them —
+// pairs of cars ascending by (a, b), a < b; within a pair of cars ascending by fixture-of-a * 8 + fixture-of-b — whichever of the two
+// fixtures is fixtureA.  The others are dropped for that step: no constraint, no island link, no warm start from them next step.
+// The kept set is a function of the entry poses alone.  cap 0 (the default): no cap, Box2D's behaviour.
 namespace {
+
+// what the contact code reached, per env (orc_contact_coverage; Env::cov).  MAX rows hold a maximum, the others count.
+enum { COV_MAX_MANIFOLDS = 0, COV_BLOCK_BOTH, COV_BLOCK_X1, COV_BLOCK_X2, COV_BLOCK_NEITHER, COV_BLOCK_NONE, COV_ILL_CONDITIONED, COV_FACE_A, COV_FACE_B,
+       COV_FLIPPED, COV_POS_SWEEPS_ALL, COV_ID_MATCH, COV_ID_MISS, COV_TRANSLATION_CLAMP, COV_ROTATION_CLAMP, COV_MAX_ISLAND_CARS, COV_MAX_CANDIDATES,
+       COV_DROPPED, COV_ILL_THEN_WELL, COV_ROWS };
+static_assert((int)COV_ROWS <= (int)ORC_COV_ROWS, "Env::cov is too small");
+inline void cov_max(Env& E, int row, long long v) { if (v > E.cov[row]) E.cov[row] = v; }
 
 struct CPoint { V2 local; f32 nImp, tImp; uint32_t id; };
 struct CManifold { int type; V2 localNormal, localPoint; int n; CPoint p[2]; };
 struct CarContact {
   int carA, fixA, carB, fixB;
   CManifold m;
+  bool ill = false, prev_ill = false;   // this step / the pair's last step solved a two-point manifold as one point (ill-conditioned K)
+  int found;                     // where k_collide finds the pair: (a * 8 + b) * 64 + fixture of a * 8 + fixture of b, a < b
 };
 struct ContactStore {
   std::vector<CarContact> cur;   // touching contacts of the current step, defined order
   std::vector<CarContact> prev;  // previous step (warm-start matching by feature id)
+  std::vector<int> cord;         // the order the last step solved `cur` in
+  int jord[8][4];                // ... and each car's joints
+  int candidates = 0;            // touching pairs of the last step before the cap
 };
 ContactStore& store_of(Env& E) {
   if (!E.contact_store) E.contact_store = new ContactStore();
   return *(ContactStore*)E.contact_store;
 }
 void contacts_free(Env& E) { delete (ContactStore*)E.contact_store; E.contact_store = nullptr; }
-void contacts_reset(Env& E) { ContactStore& S = store_of(E); S.cur.clear(); S.prev.clear(); }
+void contacts_reset(Env& E) { ContactStore& S = store_of(E); S.cur.clear(); S.prev.clear(); S.cord.clear(); S.candidates = 0; }
 
 inline const Poly& fixture_poly(const Env& E, int fix) { return fix < 4 ? E.S.hull[fix] : E.S.wheel; }
 inline int fixture_body(int fix) { return fix < 4 ? 0 : fix - 3; }
@@ -120,7 +138,7 @@ bool car_fixture_id_lower(const Env& E, int pf, int pg);   // mcr_oracle.cpp: pr
 // b2ContactManager::Collide for the dynamic (car<->car) pairs at the poses entering the step.
 void collide_cars(Env& E) {
   ContactStore& S = store_of(E);
-  S.prev.swap(S.cur); S.cur.clear();
+  S.prev.swap(S.cur); S.cur.clear(); S.cord.clear(); S.candidates = 0;
   if (!E.enable_car_contacts) return;
   const int N = E.N;
   {   // b2ContactManager::Collide destroys the contacts whose fat AABBs ceased to overlap
@@ -149,16 +167,38 @@ void collide_cars(Env& E) {
     // fixtureA of a contact = the fixture with the LOWER proxy id (b2BroadPhase::UpdatePairs hands AddPair (min, max), b2Contact::Create keeps
     // the order for polygon pairs): car a's in a fresh world; whichever the tree's free list gave the lower id in a world that lives on
     const bool flip = car_fixture_id_lower(E, ib, ia);
-    CarContact C;
+    CarContact C; C.found = (a * 8 + b) * 64 + fa * 8 + fb;
     if (!flip) { C.carA = a; C.fixA = fa; C.carB = b; C.fixB = fb; } else { C.carA = b; C.fixA = fb; C.carB = a; C.fixB = fa; }
     collide_polygons(C.m, fixture_poly(E, C.fixA), E.cars[C.carA].b[fixture_body(C.fixA)].xf, fixture_poly(E, C.fixB), E.cars[C.carB].b[fixture_body(C.fixB)].xf);
     if (C.m.n == 0) continue;
-    for (const CarContact& O : S.prev)               // b2Contact::Update id matching
-      if (O.carA == C.carA && O.fixA == C.fixA && O.carB == C.carB && O.fixB == C.fixB)
-        for (int i = 0; i < C.m.n; ++i) for (int j = 0; j < O.m.n; ++j)
-          if (O.m.p[j].id == C.m.p[i].id) { C.m.p[i].nImp = O.m.p[j].nImp; C.m.p[i].tImp = O.m.p[j].tImp; break; }
     S.cur.push_back(C);
   }
+  S.candidates = (int)S.cur.size();
+  cov_max(E, COV_MAX_CANDIDATES, S.candidates);
+  if (E.contact_cap > 0 && (int)S.cur.size() > E.contact_cap) {     // THE DROP RULE (header): the first `cap` in the order k_collide finds them
+    std::vector<int> key; for (const CarContact& C : S.cur) key.push_back(C.found);
+    std::sort(key.begin(), key.end());
+    const int last = key[E.contact_cap - 1];
+    size_t w = 0;
+    for (size_t i = 0; i < S.cur.size(); ++i) if (S.cur[i].found <= last) S.cur[w++] = S.cur[i];
+    E.cov[COV_DROPPED] += (long long)(S.cur.size() - w);
+    S.cur.resize(w);
+  }
+  for (CarContact& C : S.cur) {
+    E.cov[C.m.type == 1 ? COV_FACE_A : COV_FACE_B] += 1;
+    if (C.carA > C.carB) E.cov[COV_FLIPPED] += 1;
+    for (const CarContact& O : S.prev)               // b2Contact::Update id matching
+      if (O.carA == C.carA && O.fixA == C.fixA && O.carB == C.carB && O.fixB == C.fixB) {
+        C.prev_ill = O.ill;
+        for (int i = 0; i < C.m.n; ++i) {
+          bool hit = false;
+          for (int j = 0; j < O.m.n; ++j)
+            if (O.m.p[j].id == C.m.p[i].id) { C.m.p[i].nImp = O.m.p[j].nImp; C.m.p[i].tImp = O.m.p[j].tImp; hit = true; break; }
+          E.cov[hit ? COV_ID_MATCH : COV_ID_MISS] += 1;
+        }
+      }
+  }
+  cov_max(E, COV_MAX_MANIFOLDS, (long long)S.cur.size());
 }
 
 struct VCPoint { V2 rA, rB; f32 nImp, tImp, normalMass, tangentMass, velocityBias; };
@@ -191,7 +231,7 @@ void world_manifold(const CManifold& M, const Xf& xfA, const Xf& xfB, V2* normal
   }
 }
 
-void contact_solve_velocity(VC& c) {
+void contact_solve_velocity(VC& c, long long* cov) {
   Body& A = *c.A; Body& B = *c.B;
   f32 mA = A.invMass, iA = A.invI, mB = B.invMass, iB = B.invI;
   V2 vA = A.v, vB = B.v; f32 wA = A.w, wB = B.w;
@@ -229,13 +269,14 @@ void contact_solve_velocity(VC& c) {
     V2 x; bool ok = false;
     for (;;) {
       x = -v2(c.nm11 * b.x + c.nm12 * b.y, c.nm21 * b.x + c.nm22 * b.y);
-      if (x.x >= 0.0f && x.y >= 0.0f) { ok = true; break; }
+      if (x.x >= 0.0f && x.y >= 0.0f) { ok = true; cov[COV_BLOCK_BOTH] += 1; break; }
       x.x = -cp1.normalMass * b.x; x.y = 0.0f; vn1 = 0.0f; vn2 = c.k21 * x.x + b.y;
-      if (x.x >= 0.0f && vn2 >= 0.0f) { ok = true; break; }
+      if (x.x >= 0.0f && vn2 >= 0.0f) { ok = true; cov[COV_BLOCK_X1] += 1; break; }
       x.x = 0.0f; x.y = -cp2.normalMass * b.y; vn1 = c.k12 * x.y + b.x; vn2 = 0.0f;
-      if (x.y >= 0.0f && vn1 >= 0.0f) { ok = true; break; }
+      if (x.y >= 0.0f && vn1 >= 0.0f) { ok = true; cov[COV_BLOCK_X2] += 1; break; }
       x.x = 0.0f; x.y = 0.0f; vn1 = b.x; vn2 = b.y;
-      if (vn1 >= 0.0f && vn2 >= 0.0f) { ok = true; break; }
+      if (vn1 >= 0.0f && vn2 >= 0.0f) { ok = true; cov[COV_BLOCK_NEITHER] += 1; break; }
+      cov[COV_BLOCK_NONE] += 1;
       break;
     }
     if (ok) {
@@ -343,8 +384,10 @@ void world_solve(Env& E, f32 h, int velIters, int posIters) {
   auto find = [&](int x) { while (isl[x] != x) x = isl[x]; return x; };
   for (const CarContact& C : S.cur) { int a = find(C.carA), b = find(C.carB); if (a != b) isl[std::max(a, b)] = std::min(a, b); }
   for (int c = 0; c < N; ++c) isl[c] = find(c);
+  for (int r = 0; r < N; ++r) { int n = 0; for (int c = 0; c < N; ++c) n += isl[c] == r; if (n > 1) cov_max(E, COV_MAX_ISLAND_CARS, n); }
   // the order of joints (per car) and contacts: DEFINED (island order 0, what the kernels implement) or Box2D's island DFS (1)
-  int jord[8][4]; std::vector<int> cord(S.cur.size());
+  int (&jord)[8][4] = S.jord; std::vector<int>& cord = S.cord; cord.resize(S.cur.size());
+  for (int c = 0; c < 8; ++c) for (int q = 0; q < 4; ++q) jord[c][q] = 0;
   for (int c = 0; c < N; ++c) for (int q = 0; q < 4; ++q) jord[c][q] = JOINT_ORDER[q];
   for (size_t i = 0; i < S.cur.size(); ++i) cord[i] = (int)i;
   if (E.island_order >= 1) island_dfs(E, S, jord, cord);
@@ -392,7 +435,8 @@ void world_solve(Env& E, f32 h, int velIters, int posIters) {
         vc.k11 = k11; vc.k12 = k12; vc.k21 = k12; vc.k22 = k22;
         f32 det = k11 * k22 - k12 * k12; if (det != 0.0f) det = 1.0f / det;
         vc.nm11 = det * k22; vc.nm12 = -det * k12; vc.nm21 = -det * k12; vc.nm22 = det * k11;
-      } else vc.n = 1;
+        if (C.prev_ill) E.cov[COV_ILL_THEN_WELL] += 1;      // (the second point's stored impulse is the one the fallback left alone)
+      } else { vc.n = 1; S.cur[i].ill = true; E.cov[COV_ILL_CONDITIONED] += 1; }
     }
   }
   for (int oi : cord) {   // WarmStart
@@ -427,7 +471,7 @@ void world_solve(Env& E, f32 h, int velIters, int posIters) {
       for (int q = 0; q < 4; ++q) joint_solve_velocity(E.cars[c], jord[c][q], h);
       if (track_fix && fix_at[c] == velIters) { const Snap after = snap_of(E.cars[c]); if (memcmp(&before, &after, sizeof(Snap)) == 0) fix_at[c] = it; }
     }
-    for (int oi : cord) contact_solve_velocity(vcs[oi]);
+    for (int oi : cord) contact_solve_velocity(vcs[oi], E.cov);
     if (track_cyc && cyc_at == velIters) {
       const std::vector<f32> cur = env_snap();
       for (int pp = 1; pp <= 8 && pp <= (int)ring.size(); ++pp) {
@@ -444,16 +488,18 @@ void world_solve(Env& E, f32 h, int velIters, int posIters) {
   for (int c = 0; c < N; ++c) for (int k = 0; k < 5; ++k) {
     Body& b = E.cars[c].b[k];
     V2 tr = h * b.v;
-    if (dot(tr, tr) > b2_maxTranslationSquared) { f32 ratio = b2_maxTranslation / length(tr); b.v = ratio * b.v; }
+    if (dot(tr, tr) > b2_maxTranslationSquared) { f32 ratio = b2_maxTranslation / length(tr); b.v = ratio * b.v; E.cov[COV_TRANSLATION_CLAMP] += 1; }
     f32 rot = h * b.w;
-    if (rot * rot > b2_maxRotationSquared) { f32 ratio = b2_maxRotation / fabsf(rot); b.w *= ratio; }
+    if (rot * rot > b2_maxRotationSquared) { f32 ratio = b2_maxRotation / fabsf(rot); b.w *= ratio; E.cov[COV_ROTATION_CLAMP] += 1; }
     b.c = b.c + h * b.v; b.a += h * b.w;
   }
   // position iterations + sleep, per island
   for (int root = 0; root < N; ++root) {
     if (isl[root] != root) continue;
-    bool positionSolved = false;
+    bool positionSolved = false; int sweeps = 0; bool has_contact = false;
+    for (const CarContact& C : S.cur) has_contact = has_contact || isl[C.carA] == root;
     for (int it = 0; it < posIters; ++it) {
+      sweeps = it + 1;
       E.dbg_pos_iters = std::max(E.dbg_pos_iters, it + 1);
       f32 minSep = 0.0f;
       for (int oi : cord) { const CarContact& C = S.cur[oi]; if (isl[C.carA] != root) continue;
@@ -464,6 +510,7 @@ void world_solve(Env& E, f32 h, int velIters, int posIters) {
         for (int q = 0; q < 4; ++q) { bool ok = joint_solve_position(E.cars[c], jord[c][q]); jointsOkay = jointsOkay && ok; }
       if (contactsOkay && jointsOkay) { positionSolved = true; break; }
     }
+    if (has_contact && sweeps == posIters) E.cov[COV_POS_SWEEPS_ALL] += 1;
     f32 minSleepTime = 3.402823466e+38f;
     const f32 linTolSqr = b2_linearSleepTolerance * b2_linearSleepTolerance;
     const f32 angTolSqr = b2_angularSleepTolerance * b2_angularSleepTolerance;
@@ -490,3 +537,37 @@ extern "C" void orc_debug_fixed_point(void* h, long long* hist) { ((Env*)h)->dbg
 // count only the steps with touching car<->car contacts
 extern "C" void orc_debug_cycle(void* h, long long* hist, int contacts_only) { ((Env*)h)->dbg_cycle = hist; ((Env*)h)->dbg_cycle_contacts_only = contacts_only; }
 extern "C" int orc_num_car_contacts(void* h) { return (int)store_of(*(Env*)h).cur.size(); }
+// The env's touching contacts after the last step, in the order they were solved, as the product's manifold store holds them
+// (multi_car_racing_amd/csrc/k_carcontacts.h: the record layout): out[0] = count, out[1] = 1 if the cap dropped pairs in that step,
+// out[2..3] = each car's joint order (2 bits per position, 8 bits per car), then 16 words per contact: key = carA | fixA << 4 | carB << 8 |
+// fixB << 12, type | n << 8, localNormal, localPoint, two points of (local x, local y, nImp, tImp, id); the words of a point the manifold
+// does not have are 0.  Writes at most `cap` words; returns the count.
+extern "C" int orc_get_car_contacts(void* h, uint32_t* out, int cap) {
+  Env& E = *(Env*)h; const ContactStore& S = store_of(E);
+  const int n = (int)S.cur.size();
+  std::vector<uint32_t> w(4 + (size_t)n * 16, 0u);
+  auto bits = [](f32 v) { uint32_t u; memcpy(&u, &v, 4); return u; };
+  w[0] = (uint32_t)n; w[1] = (E.contact_cap > 0 && S.candidates > E.contact_cap) ? 1u : 0u;
+  if ((int)S.cord.size() == n) {
+    unsigned long long jo = 0ull;
+    for (int c = 0; c < E.N; ++c) for (int q = 0; q < 4; ++q) jo |= (unsigned long long)(S.jord[c][q] & 3) << (c * 8 + 2 * q);
+    w[2] = (uint32_t)jo; w[3] = (uint32_t)(jo >> 32);
+    for (int i = 0; i < n; ++i) {
+      const CarContact& C = S.cur[S.cord[i]]; uint32_t* d = &w[4 + (size_t)i * 16];
+      d[0] = (uint32_t)C.carA | ((uint32_t)C.fixA << 4) | ((uint32_t)C.carB << 8) | ((uint32_t)C.fixB << 12);
+      d[1] = (uint32_t)C.m.type | ((uint32_t)C.m.n << 8);
+      d[2] = bits(C.m.localNormal.x); d[3] = bits(C.m.localNormal.y); d[4] = bits(C.m.localPoint.x); d[5] = bits(C.m.localPoint.y);
+      for (int j = 0; j < C.m.n; ++j) { uint32_t* q = d + 6 + j * 5; q[0] = bits(C.m.p[j].local.x); q[1] = bits(C.m.p[j].local.y); q[2] = bits(C.m.p[j].nImp); q[3] = bits(C.m.p[j].tImp); q[4] = C.m.p[j].id; }
+    }
+  }
+  for (size_t i = 0; i < w.size() && (int)i < cap; ++i) out[i] = w[i];
+  return n;
+}
+// Coverage of the contact code by this env since the last reset of the counters: out[ORC_COV_ROWS] (oracle.py: COVERAGE_ROWS names them)
+extern "C" int orc_contact_coverage(void* h, long long* out, int reset) {
+  Env& E = *(Env*)h;
+  for (int i = 0; i < ORC_COV_ROWS; ++i) { out[i] = E.cov[i]; if (reset) E.cov[i] = 0; }
+  return COV_ROWS;
+}
+// 0 (default): no cap.  cap > 0: THE DROP RULE of the header, the product's MCR_CC_MAX
+extern "C" void orc_set_contact_cap(void* h, int cap) { ((Env*)h)->contact_cap = cap < 0 ? 0 : cap; }

@@ -202,6 +202,10 @@ def new_episode(N, track_rng, global_rng, direction="CCW", use_random_direction=
 
 
 # ----------------------------------------------------------------------------- C++ oracle binding
+# orc_contact_coverage's rows (mcr_oracle_contacts.inc: COV_*); the max_* rows hold a maximum, the others count events
+COVERAGE_ROWS = ("max_manifolds", "block_both", "block_x1", "block_x2", "block_neither", "block_none", "ill_conditioned", "face_a", "face_b",
+                 "flipped", "pos_sweeps_all", "id_match", "id_miss", "translation_clamp", "rotation_clamp", "max_island_cars", "max_candidates",
+                 "dropped", "ill_then_well")
 _lib = None
 
 
@@ -228,6 +232,12 @@ def lib():
         L.orc_set_world_mode.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.orc_debug_proxy_ids.restype = ctypes.c_int
         L.orc_debug_proxy_ids.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.orc_get_car_contacts.restype = ctypes.c_int
+        L.orc_get_car_contacts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.orc_contact_coverage.restype = ctypes.c_int
+        L.orc_contact_coverage.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.orc_set_contact_cap.restype = None
+        L.orc_set_contact_cap.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _lib = L
     return _lib
 
@@ -509,3 +519,23 @@ class OracleEnv:
 
     def num_car_contacts(self):
         return self.L.orc_num_car_contacts(self.h)
+
+    def car_contacts(self):
+        """The touching car<->car contacts after the last step as the product's manifold store holds them (k_carcontacts.h): uint32
+        [4 + 16 n] — count, "the cap dropped pairs", the joint-order words, then one 16-word record per contact in the order they were solved."""
+        n = self.num_car_contacts()
+        out = np.zeros(4 + 16 * n, np.uint32)
+        assert self.L.orc_get_car_contacts(self.h, _p(out), len(out)) == n
+        return out
+
+    def contact_coverage(self, reset=False):
+        """dict row name -> what this env's contact code reached since the counters were last reset (COVERAGE_ROWS)"""
+        out = np.zeros(24, np.int64)
+        n = self.L.orc_contact_coverage(self.h, _p(out), int(bool(reset)))
+        assert n == len(COVERAGE_ROWS), (n, len(COVERAGE_ROWS))
+        return {k: int(out[i]) for i, k in enumerate(COVERAGE_ROWS)}
+
+    def set_contact_cap(self, cap):
+        """0 (default): no cap on the touching car<->car pairs of a step.  cap > 0: the product's manifold store (MCR_CC_MAX) — the first
+        `cap` pairs in the order k_collide finds them are kept, the others dropped for the step (mcr_oracle_contacts.inc: THE DROP RULE)."""
+        self.L.orc_set_contact_cap(self.h, int(cap))
