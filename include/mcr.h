@@ -317,8 +317,8 @@ int mcr_hull_polygons(float* out, int32_t* counts);
  * track point L1 tiles ahead of the nearest one for the steering, a target speed that falls with the curvature towards the point L2 tiles
  * ahead for gas and brake.  An action is a pure function of the env's current state, its episode and the car's parameter row, defined in
  * IEEE f64 operations in a fixed order and rounded to f32 once: a host reproduces it bit for bit (tests/driver_ref.py), and snapshots,
- * clones, level pools and sharding need nothing new.  It follows the track on a free road; it does NOT avoid collisions, overtake, or recover
- * from a spin or from the grass.
+ * clones, level pools and sharding need nothing new.  On its own it follows the track on a free road; it does NOT avoid collisions, overtake,
+ * or recover from a spin or from the grass — mcr_set_racecraft (below) adds a side-step, a follow rule and a speed cap on the grass.
  * A parameter row is MCR_DRV_PARAMS floats: L1, L2 (integers 1..64), v_max (> 0, the speed on a straight), K_s, K_c, K_g, K_b (gains >= 0),
  * offset (lateral offset of the line, positive = to the right of the episode's driving direction), gas_max, brake_max (in [0, 1]). */
 #define MCR_DRV_PARAMS 10
@@ -338,6 +338,24 @@ int mcr_set_drivers(mcr_env* h, const float* params, uint32_t agent_mask, float*
  * buffer to fill, NULL = the registered one.  So "merge the scripted cars into the step's buffer" is (actions, 0, NULL) and "every car's
  * expert action into a buffer of the caller's" is (NULL, 0xffffffff, buf).  MCR_ERR_STATE without mcr_set_drivers.  Only enqueues. */
 int mcr_driver_actions(mcr_env* h, const float* d_actions_in, uint32_t agent_mask_override, float* d_out, void* stream);
+/* Racecraft: an optional second parameter row per scripted car (csrc/k_driver.h holds the definition, tests/racecraft_ref.py restates it).
+ * A car with its bit in the racecraft mask looks at EVERY car of its env (scripted or not): the nearest car ahead within `look` track points
+ * is its leader; if the leader sits within w_block of the car's line, the line is moved w_pass to the leader's free side (never beyond
+ * +-off_max); while the leader is within w_block laterally in the car's own frame the target speed is capped at the leader's speed plus
+ * K_f (gap - d_safe); and a car more than w_off from the centre line drives at v_off at most.  Still stateless, still reproducible bit for
+ * bit.  Every other scripted car keeps the plain controller, bit for bit, and a handle without racecraft launches the plain kernel.
+ * A row is MCR_RC_PARAMS floats: look (an integer 1..64), w_block, w_pass, off_max, d_safe, K_f, w_off, v_off (finite, >= 0). */
+#define MCR_RC_PARAMS 8
+#define MCR_RC_DEFAULTS { 24.0f, 3.5f, 4.25f, 4.5f, 16.0f, 2.0f, 7.5f, 15.0f }
+/* the default row (host [MCR_RC_PARAMS]); no handle, no GPU needed */
+int mcr_racecraft_defaults(float* out);
+/* mcr_set_racecraft's validation of rows and mask without a handle (no GPU needed): MCR_OK or MCR_ERR_ARG */
+int mcr_check_racecraft(int num_agents, const float* params, uint32_t agent_mask);
+/* params: host [num_agents][MCR_RC_PARAMS], copied; agent_mask: bit a = car a races.  NULL params or mask 0 turn racecraft off.
+ * mcr_driver_actions then uses the extended controller for the cars that are both in the mask it drives (the registered one, or every car
+ * under its override) and in this one, and the plain controller for the rest.  MCR_ERR_STATE before mcr_set_drivers; MCR_ERR_ARG as
+ * mcr_set_drivers.  May be called again; no HIP call, no synchronisation. */
+int mcr_set_racecraft(mcr_env* h, const float* params, uint32_t agent_mask);
 /* Rollout statistics accumulated on the device since creation / the last reset of the counters (synchronises):
  * out2[0] = episodes finished, out2[1] = sum of their returns over all agents.  These are the per-rank inputs of the
  * job-wide metric all-reduce. */

@@ -15,6 +15,9 @@ RANGE_RAYS_MAX = 32             # include/mcr.h: MCR_RANGE_RAYS_MAX, rays per ca
 DRV_PARAMS = 10                 # include/mcr.h: MCR_DRV_PARAMS, floats per parameter row of a scripted driver
 DRIVER_PARAM_NAMES = ("L1", "L2", "v_max", "K_s", "K_c", "K_g", "K_b", "offset", "gas_max", "brake_max")
 DRIVER_DEFAULTS = dict(zip(DRIVER_PARAM_NAMES, (4.0, 12.0, 70.0, 8.0, 20.0, 0.2, 0.1, 0.0, 1.0, 0.8)))    # include/mcr.h: MCR_DRV_DEFAULTS
+RC_PARAMS = 8                   # include/mcr.h: MCR_RC_PARAMS, floats per racecraft row of a scripted driver
+RACECRAFT_PARAM_NAMES = ("look", "w_block", "w_pass", "off_max", "d_safe", "K_f", "w_off", "v_off")
+RACECRAFT_DEFAULTS = dict(zip(RACECRAFT_PARAM_NAMES, (24.0, 3.5, 4.25, 4.5, 16.0, 2.0, 7.5, 15.0)))        # include/mcr.h: MCR_RC_DEFAULTS
 LEVEL_ORDER = {"random": 0, "cycle": 1}      # include/mcr.h: mcr_set_episode_pool's mode ("weighted" is no mode: vec_env.py puts a sampler on a mode-0 pool)
 
 # mcr_debug_set bits: the mirror of enum McrDebugBit (csrc/mcr_kernels.h, which says what each one does; tests/test_abi.py compares the two)
@@ -117,6 +120,9 @@ SYMBOLS = {
     "mcr_check_drivers": (_i, [_i, _vp, ctypes.c_uint32]),
     "mcr_set_drivers": (_i, [_vp, _vp, ctypes.c_uint32, _vp]),
     "mcr_driver_actions": (_i, [_vp, _vp, ctypes.c_uint32, _vp, _vp]),
+    "mcr_racecraft_defaults": (_i, [_vp]),
+    "mcr_check_racecraft": (_i, [_i, _vp, ctypes.c_uint32]),
+    "mcr_set_racecraft": (_i, [_vp, _vp, ctypes.c_uint32]),
     "mcr_read_rollout_stats": (_i, [_vp, _vp, _i]),
     "mcr_render": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mcr_debug_read_contact_counts": (_i, [_vp, _vp]),

@@ -17,6 +17,7 @@
 
 #define MCR_MAX_AGENTS 8
 #define MCR_DRV_PARAMS 10     // include/mcr.h: floats per parameter row of the scripted driver (k_driver.h)
+#define MCR_RC_PARAMS 8       // include/mcr.h: floats per racecraft row of the scripted driver (k_driver.h)
 #define MCR_RANGE_RAYS_MAX 32 // include/mcr.h: rays per car of the range-finder observation (k_rangeobs.h)
 #define MCR_TILE_CAP 512
 #define MCR_QUAD_CAP 768

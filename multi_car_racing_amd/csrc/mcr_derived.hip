@@ -194,11 +194,44 @@ extern "C" int mcr_set_drivers(mcr_env* h, const float* params, uint32_t agent_m
   h->drv_out = d_actions; h->drv_mask = agent_mask;
   return MCR_OK;
 }
+// Racecraft (k_driver.h): rows and mask beside the driver's, validated and stored alike
+static const float MCR_RC_DEFAULT_ROW[MCR_RC_PARAMS] = MCR_RC_DEFAULTS;
+static const char* rc_check_row(const float* w) {
+  for (int j = 0; j < MCR_RC_PARAMS; ++j) if (!std::isfinite(w[j])) return "a parameter is not finite";
+  if (w[0] < 1.0f || w[0] > (float)MCR_DRV_LOOKAHEAD_MAX || w[0] != (float)(int)w[0]) return "look must be an integer 1..64";
+  for (int j = 1; j < MCR_RC_PARAMS; ++j) if (w[j] < 0.0f) return "w_block, w_pass, off_max, d_safe, K_f, w_off, v_off must be >= 0";
+  return nullptr;
+}
+extern "C" int mcr_racecraft_defaults(float* out) {
+  if (!out) { g_err = "null argument"; return MCR_ERR_ARG; }
+  for (int j = 0; j < MCR_RC_PARAMS; ++j) out[j] = MCR_RC_DEFAULT_ROW[j];
+  return MCR_OK;
+}
+extern "C" int mcr_check_racecraft(int num_agents, const float* params, uint32_t agent_mask) {
+  if (num_agents < 1 || num_agents > MCR_MAX_AGENTS) { g_err = "racecraft: num_agents 1..8"; return MCR_ERR_ARG; }
+  if (!params) { g_err = "racecraft: null parameter rows"; return MCR_ERR_ARG; }
+  if (agent_mask >> num_agents) { g_err = "racecraft: agent_mask has bits of cars >= num_agents"; return MCR_ERR_ARG; }
+  for (int a = 0; a < num_agents; ++a)
+    if (const char* why = rc_check_row(params + (size_t)a * MCR_RC_PARAMS)) { g_err = "racecraft: car " + std::to_string(a) + ": " + why; return MCR_ERR_ARG; }
+  return MCR_OK;
+}
+extern "C" int mcr_set_racecraft(mcr_env* h, const float* params, uint32_t agent_mask) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!h->drv_out) { g_err = "mcr_set_racecraft: no drivers set (mcr_set_drivers)"; return MCR_ERR_STATE; }
+  if (!params || !agent_mask) { h->drv.rc_mask = 0; return MCR_OK; }
+  if (int rc = mcr_check_racecraft(h->P.N, params, agent_mask)) return rc;
+  for (int a = 0; a < MCR_MAX_AGENTS; ++a)
+    for (int j = 0; j < MCR_RC_PARAMS; ++j) h->drv.rc[a][j] = a < h->P.N ? params[a * MCR_RC_PARAMS + j] : MCR_RC_DEFAULT_ROW[j];
+  h->drv.rc_mask = agent_mask;
+  return MCR_OK;
+}
 extern "C" int mcr_driver_actions(mcr_env* h, const float* d_actions_in, uint32_t agent_mask_override, float* d_out, void* stream) {
   if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
   if (!h->drv_out) { g_err = "mcr_driver_actions: no drivers set (mcr_set_drivers)"; return MCR_ERR_STATE; }
   const uint32_t mask = agent_mask_override == 0xffffffffu ? (1u << h->P.N) - 1u : h->drv_mask;
-  hipLaunchKernelGGL(k_driver, dim3(h->P.B), dim3(64), 0, (hipStream_t)stream, h->P, h->drv, d_actions_in, mask, d_out ? d_out : h->drv_out);
+  // (the extended kernel only where a car it drives races: a handle without racecraft launches the plain instantiation)
+  if (mask & h->drv.rc_mask) hipLaunchKernelGGL(k_driver<true>, dim3(h->P.B), dim3(64), 0, (hipStream_t)stream, h->P, h->drv, d_actions_in, mask, d_out ? d_out : h->drv_out);
+  else hipLaunchKernelGGL(k_driver<false>, dim3(h->P.B), dim3(64), 0, (hipStream_t)stream, h->P, h->drv, d_actions_in, mask, d_out ? d_out : h->drv_out);
   HIPCHK(hipGetLastError());
   return MCR_OK;
 }

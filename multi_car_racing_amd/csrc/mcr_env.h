@@ -72,7 +72,7 @@ struct mcr_env {
   McrParams flags_P{};          // ... the launch's parameters: ROLE_MAIN with that step's partition marks (its parity's part / dpart buffers), no touch verdicts
   McrStateObs so{nullptr, 0, 0, 0};   // mcr_set_state_obs: the low-dimensional observation (k_stateobs.h); out == nullptr: off
   McrRangeObs ro{};           // mcr_set_range_obs: the range-finder observation (k_rangeobs.h); out == nullptr: off
-  McrDriver drv{};            // mcr_set_drivers: the scripted driver's parameter rows (k_driver.h) ...
+  McrDriver drv{};            // mcr_set_drivers / mcr_set_racecraft: the scripted driver's parameter rows, racecraft rows and mask (k_driver.h) ...
   float* drv_out = nullptr;   // ... the registered [B][N][3] buffer (nullptr: no drivers, nothing is launched) ...
   uint32_t drv_mask = 0;      // ... and the cars it drives
   McrPool pool{nullptr, 0, 0, 0, 0, nullptr, nullptr, nullptr};   // mcr_set_episode_pool: the device stages the episodes itself (k_pool.h); blobs == nullptr: the host does

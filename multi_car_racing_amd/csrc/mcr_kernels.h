@@ -193,9 +193,12 @@ struct McrRangeObs {
 };
 
 // The scripted driver (k_driver.h): launch argument of k_driver beside McrParams, kept in the handle.  The parameter rows travel BY VALUE with
-// every launch (320 bytes of kernel arguments): a later mcr_set_drivers changes the launches enqueued after it and nothing in flight
+// every launch (320 + 260 bytes of kernel arguments): a later mcr_set_drivers / mcr_set_racecraft changes the launches enqueued after it and
+// nothing in flight.  k_driver<false> reads `prm` alone.
 struct McrDriver {
   float prm[MCR_MAX_AGENTS][MCR_DRV_PARAMS];   // per car: L1, L2, v_max, K_s, K_c, K_g, K_b, offset, gas_max, brake_max
+  float rc[MCR_MAX_AGENTS][MCR_RC_PARAMS];     // per car: look, w_block, w_pass, off_max, d_safe, K_f, w_off, v_off (mcr_set_racecraft)
+  uint32_t rc_mask;                            // bit a: car a races (0: k_driver<false> is launched)
 };
 
 // A level pool (include/mcr.h: mcr_set_episode_pool; k_pool.h): launch argument of k_pool_restage, kept in the handle (null `blobs`: no pool —

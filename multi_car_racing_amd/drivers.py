@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import DRIVER_DEFAULTS, DRIVER_PARAM_NAMES, DRV_PARAMS  # noqa: F401
+from ._lib import DRIVER_DEFAULTS, DRIVER_PARAM_NAMES, DRV_PARAMS, RACECRAFT_DEFAULTS, RACECRAFT_PARAM_NAMES, RC_PARAMS  # noqa: F401
 
 
 def default_params(num_agents):
@@ -61,3 +61,52 @@ def driver_params_array(num_agents, driver_params=None):
     if L.mcr_check_drivers(N, _lib.ptr(rows), ctypes.c_uint32(0)) != 0:
         raise ValueError(L.mcr_last_error().decode())
     return rows
+
+
+def default_racecraft_params(num_agents):
+    """[N, 8] float32: the default racecraft row for every car"""
+    return np.tile(np.asarray([RACECRAFT_DEFAULTS[k] for k in RACECRAFT_PARAM_NAMES], np.float32), (int(num_agents), 1))
+
+
+def racecraft_params_array(num_agents, racecraft=True, scripted_mask=0):
+    """VecMultiCarRacing's `racecraft` keyword -> (rows [N, 8] float32, car mask), or (None, 0) for None / False.  True: the defaults; a dict
+    {name: scalar or per-car sequence} of overrides, optionally with "agents": the cars that race; a float array [N, 8].  Without "agents"
+    the cars of `scripted_mask` race, or every car when that is 0 (expert labels only).  ValueError for an unknown name, a wrong shape, a
+    car outside 0 .. N-1 or a value mcr_set_racecraft would refuse."""
+    N = int(num_agents)
+    if racecraft is None or racecraft is False:
+        return None, 0
+    rows = default_racecraft_params(N)
+    mask = int(scripted_mask) if scripted_mask else (1 << N) - 1
+    if racecraft is True:
+        pass
+    elif isinstance(racecraft, dict):
+        for name, v in racecraft.items():
+            if name == "agents":
+                try:
+                    mask = driver_mask(N, v)
+                except ValueError as e:
+                    raise ValueError(str(e).replace("scripted_agents", "racecraft['agents']")) from None
+                continue
+            if name not in RACECRAFT_PARAM_NAMES:
+                raise ValueError(f"racecraft: unknown parameter {name!r} (one of {', '.join(RACECRAFT_PARAM_NAMES)}, agents)")
+            try:
+                col = np.asarray(v, np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"racecraft[{name!r}] must be a number or a sequence of {N} numbers, got {v!r}") from None
+            if col.ndim > 1 or (col.ndim == 1 and col.shape[0] != N):
+                raise ValueError(f"racecraft[{name!r}] must be a number or a sequence of {N} numbers, got shape {col.shape}")
+            rows[:, RACECRAFT_PARAM_NAMES.index(name)] = col.astype(np.float32)
+    else:
+        try:
+            arr = np.asarray(racecraft, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("racecraft must be None, a bool, a dict of overrides or a float array [num_agents, 8]") from None
+        if arr.shape != (N, RC_PARAMS):
+            raise ValueError(f"racecraft must be None, a bool, a dict of overrides or a float array of shape ({N}, {RC_PARAMS}), got {arr.shape}")
+        rows = arr.astype(np.float32)
+    rows = np.ascontiguousarray(rows, np.float32)
+    L = _lib.load()
+    if L.mcr_check_racecraft(N, _lib.ptr(rows), ctypes.c_uint32(0)) != 0:
+        raise ValueError(L.mcr_last_error().decode())
+    return rows, mask

@@ -129,7 +129,12 @@ reference's action-less step for every car, with no driver.  `expert_actions()` 
 current state ([B, N, 3], no step, no synchronisation: labels for imitation learning / DAgger); it needs `scripted_agents` or
 `driver_params` (`driver_params={}` = the defaults, no car scripted).  An action is a pure function of the env's state, its episode and
 `self.driver_params` ([N, 10]): snapshots, clones, level pools, sharding and every step path need nothing new.  The controller follows
-the track on a free road; it does not avoid collisions, overtake, or recover from a spin or from the grass.
+the track on a free road; on its own it does not avoid collisions, overtake, or recover from a spin or from the grass.
+`racecraft=True` (or a dict of overrides {name: scalar or per-car sequence}, optionally with "agents": the cars it applies to, or a float
+array [N, 8]; `drivers.RACECRAFT_DEFAULTS`) gives the scripted cars racecraft, still stateless (csrc/k_driver.h): a car looks at every other
+car of its env, moves its line to the free side of the car ahead when that car sits on it, holds the leader's speed while it is still
+behind it, and slows down when it is off the road.  It needs `scripted_agents` or `driver_params`; `self.racecraft_params` ([N, 8]) and
+`self.racecraft_agents` report what is set (None and () when off), and `expert_actions()` uses it for the same cars.
 """
 import atexit
 import collections
@@ -200,11 +205,14 @@ class VecMultiCarRacing:
                  skid_particles=False, terminal_obs=False, terminal_cap=None, fresh_world=False, obs_format="rgb", frame_stack=1,
                  state_obs=False, state_waypoints=6, state_stride=5, frame_skip=1, levels=None, level_seed=None, level_order="random",
                  level_stats=False,
-                 scripted_agents=None, driver_params=None, range_obs=False, range_rays=19, range_fov=math.pi, range_angles=None,
+                 scripted_agents=None, driver_params=None, racecraft=None, range_obs=False, range_rays=19, range_fov=math.pi, range_angles=None,
                  range_max=100.0, contact_obs=False):
         # scripted drivers (module docstring): validated on the host before anything is created
         drv_mask = _drivers.driver_mask(num_agents, scripted_agents)
         drv_rows = _drivers.driver_params_array(num_agents, driver_params) if (drv_mask or driver_params is not None) else None
+        rc_rows, rc_mask = _drivers.racecraft_params_array(num_agents, racecraft, drv_mask)
+        if rc_rows is not None and drv_rows is None:
+            raise ValueError("racecraft needs scripted_agents or driver_params (there is no scripted driver to apply it to)")
         range_table = range_obs_table(range_rays, range_fov, range_angles, range_max) if range_obs else None
         if contact_obs and (int(num_agents) < 2 or not car_contacts):
             raise ValueError("contact_obs=True needs num_agents >= 2 and car_contacts=True (there is no car<->car manifold store otherwise)")
@@ -353,6 +361,9 @@ class VecMultiCarRacing:
             if drv_mask:
                 self.actions = self._drv_buf
             _lib.check(self.L.mcr_set_drivers(self.h, _lib.ptr(drv_rows), ctypes.c_uint32(drv_mask), ctypes.c_void_p(self._drv_buf.data_ptr())), "mcr_set_drivers")
+        self.racecraft_params, self.racecraft_agents = rc_rows, tuple(a for a in range(self.N) if rc_mask >> a & 1)
+        if rc_rows is not None:
+            _lib.check(self.L.mcr_set_racecraft(self.h, _lib.ptr(rc_rows), ctypes.c_uint32(rc_mask)), "mcr_set_racecraft")
         # RNG streams
         self.mt_track = np.zeros((self.B, _lib.MT_WORDS), np.uint32)
         self.mt_draw = np.zeros((self.B, _lib.MT_WORDS), np.uint32)
