@@ -545,6 +545,9 @@ int mcr_debug_read_contact_counts(mcr_env* h, int32_t* out /*[num_envs]*/);
 /* the raw manifold stores of all envs after the last step (mcr_contact_store_words: the sizes; csrc/k_carcontacts.h: the record layout);
  * synchronises.  The input of the car-contact observation's host reference. */
 int mcr_debug_read_contacts(mcr_env* h, uint32_t* out /*[num_envs][words per env]*/);
+/* the wheel<->tile sensor pass's per-tile state after the last step (csrc/k_collide.h): out[env][tile] bit car * 4 + wheel = that wheel rests on
+ * the tile (the reference's `tile in wheel.tiles`); tiles at and beyond the episode's count are not meaningful.  Read-only; synchronises. */
+int mcr_debug_read_tile_touch(mcr_env* h, uint32_t* out /*[num_envs][MCR_TILE_CAP]*/);
 /* fresh_world = 0: the broadphase proxy ids of env `env`'s live episode on its one world (csrc/k_world.h) — out[0 .. T) tiles in track order,
  * then num_agents * 8 car fixtures (car * 8 + fixture; 0..3 hull polygons, 4..7 wheels); returns the count written; synchronises.  Tests
  * hold it against the oracle's literal b2DynamicTree (what mcr_world_proxy_ids is for the host-side twin). */

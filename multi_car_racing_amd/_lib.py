@@ -128,6 +128,7 @@ SYMBOLS = {
     "mcr_debug_read_contact_counts": (_i, [_vp, _vp]),
     "mcr_debug_read_contacts": (_i, [_vp, _vp]),
     "mcr_debug_contact_obs": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "mcr_debug_read_tile_touch": (_i, [_vp, _vp]),
     "mcr_debug_read_proxy_ids": (_i, [_vp, _i, _vp, _i]),
     "mcr_debug_read_env_records": (_i, [_vp, _vp, _i]),
     "mcr_debug_read_partition": (_i, [_vp, _vp, _vp]),

@@ -939,7 +939,7 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
     int incl = need;
     for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
     pool_base = incl - need;
-    // (a guard: no launch reaches it — the list launches take MCR_SIDE_ENVS_PER_WAVE envs per wavefront, a packed wavefront beyond the pool goes to k_dynamics_passes, the reset pass steps cars on the spawn grid)
+    // (a guard: no launch reaches it — the list launches take MCR_SIDE_ENVS_PER_WAVE envs per wavefront, a packed wavefront beyond the pool goes to k_dynamics_passes, in the step and in the reset pass)
     if (lane_ok && agent == 0 && pool_base + ccn > DYN_VC_POOL) { ccn = DYN_VC_POOL - pool_base; if (ccn < 0) ccn = 0; store[1] = 2u; mcr_raise(p, ST_CC_OVERFLOW); }
     ccn = __shfl(ccn, leader_lane); pool_base = __shfl(pool_base, leader_lane);
     // island order of this car's joints (3,2,1,0 unless a contact says otherwise); wq[t] = the wheel slot t holds.  (Everything that
@@ -1726,11 +1726,13 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
 // single-stream step and the reset pass, behind k_collide) puts 64 / G envs into a wavefront.  Do the envs of wavefront `blk` hold more
 // manifolds than that together?  Wave-uniform.  From the stores' counts alone, whatever the envs' state: k_dynamics and k_dynamics_passes
 // ask one after the other and must get the same answer, and the first one changes env records (an env ends, thaws, re-spawns), never a count.
-// (The reset pass, mode 1, steps only cars that stand on the spawn grid, 6 apart across and 5 track points along: no manifold at all, and no
-// second launch for it — one launch is 3 us of a single-stream step's 343; the guard in dynamics_block stays behind it.)
+// (The reset pass, mode 1, asks too: on a generated track it steps only cars that stand on the spawn grid, 6 apart across and 5 track points along
+// — no manifold at all —, but on a caller's track (mcr_episode_from_track) whose points lie closer than a car is long the grid's cars overlap
+// at spawn, 24 manifolds an env and more: three such envs in a packed wavefront are beyond the pool.  The counts of the wavefront's other envs
+// are the last step's: they can only send a wavefront here that did not need it.)
 __device__ __forceinline__ bool dyn_pool_exceeded(const McrParams& p, const int mode, const int blk) {
   const int epw = 64 / p.G;
-  if (mode != 0 || p.role != ROLE_ALL || !p.car_contacts || p.N < 2 || epw <= MCR_SIDE_ENVS_PER_WAVE) return false;
+  if (p.role != ROLE_ALL || !p.car_contacts || p.N < 2 || epw <= MCR_SIDE_ENVS_PER_WAVE) return false;
   const int e = p.env0 + blk * epw + (int)threadIdx.x;
   int need = 0;
   if ((int)threadIdx.x < epw && e < p.env0 + p.nenv) { const uint32_t n = p.cc_store[(size_t)e * (MCR_CC_MAX * MCR_CC_WORDS + 4)]; need = n < (uint32_t)MCR_CC_MAX ? (int)n : MCR_CC_MAX; }

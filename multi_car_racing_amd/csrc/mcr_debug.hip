@@ -108,6 +108,13 @@ extern "C" int mcr_debug_read_contacts(mcr_env* h, uint32_t* out) {
   if (!h || !out) return MCR_ERR_ARG;
   return read_back(out, h->P.cc_store, sizeof(uint32_t) * MCR_CC_STORE_WORDS * (size_t)h->cfg.num_envs);
 }
+// the per-tile wheel bits the sensor pass keeps between steps (k_collide.h: touch[]); read-only
+extern "C" int mcr_debug_read_tile_touch(mcr_env* h, uint32_t* out) {
+  if (!h || !out) { g_err = "mcr_debug_read_tile_touch: null argument"; return MCR_ERR_ARG; }
+  HIPCHK(sync_state(h));
+  HIPCHK(hipMemcpy(out, h->P.tile_touch, sizeof(uint32_t) * MCR_TILE_CAP * (size_t)h->cfg.num_envs, hipMemcpyDeviceToHost));
+  return MCR_OK;
+}
 extern "C" int mcr_debug_read_proxy_ids(mcr_env* h, int env, int32_t* out, int cap) {
   if (!h || !out || env < 0 || env >= h->cfg.num_envs) return MCR_ERR_ARG;
   if (!h->P.pid_tab) { g_err = "mcr_debug_read_proxy_ids: the handle was created with fresh_world = 1 (ids ascend in creation order)"; return MCR_ERR_STATE; }

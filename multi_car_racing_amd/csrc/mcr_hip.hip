@@ -278,7 +278,7 @@ static hipEvent_t get_event(mcr_env* h) {
 // (with the contact code: k_dynamics_passes behind it, for the wavefronts whose envs hold more manifolds than their LDS pool — k_dynamics.h)
 static void launch_dyn_cc(int grid, hipStream_t st, const McrParams& P, int mode) {
   hipLaunchKernelGGL(k_dynamics<true>, dim3(grid), dim3(64), 0, st, P, mode);
-  if (mode == 0) hipLaunchKernelGGL(k_dynamics_passes, dim3(grid), dim3(64), 0, st, P, mode);
+  hipLaunchKernelGGL(k_dynamics_passes, dim3(grid), dim3(64), 0, st, P, mode);
 }
 #define LAUNCH_DYN(kid_, cc_, grid, st, ...) do { if (cc_) TIMED(kid_, st, launch_dyn_cc(grid, st, __VA_ARGS__)); else LAUNCH(kid_, k_dynamics<false>, grid, 64, st, __VA_ARGS__); } while (0)
 

@@ -218,7 +218,7 @@ def lib():
         L.orc_create.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         for name in ("orc_destroy", "orc_set_track", "orc_reset", "orc_step", "orc_render", "orc_get_state",
                      "orc_set_body", "orc_get_env", "orc_positions", "orc_contact_event", "orc_set_hull_pose",
-                     "orc_bookkeeping", "orc_wheel_tile_counts", "orc_reset_nostep", "orc_step_masked", "orc_reset_masked", "orc_solve_only"):
+                     "orc_bookkeeping", "orc_wheel_tile_counts", "orc_begin_events", "orc_wheel_touch", "orc_set_event_order", "orc_reset_nostep", "orc_step_masked", "orc_reset_masked", "orc_solve_only"):
             getattr(L, name).restype = None
         L.orc_render_size.restype = None
         L.orc_render_size.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -458,6 +458,26 @@ class OracleEnv:
         out = np.zeros((self.N, 4), np.int32)
         self.L.orc_wheel_tile_counts(self.h, _p(out))
         return out
+
+    def begin_events(self):
+        """(wheel<->tile begin events of the last Collide — the last step's, or reset()'s —, the largest `past` (:117) among those that were a
+        car's first visit of their tile, -1 where there was none): what the product's replay queue has to hold (csrc/k_collide.h: EVQ_CAP)"""
+        out = np.zeros(2, np.int32)
+        self.L.orc_begin_events(self.h, _p(out))
+        return int(out[0]), int(out[1])
+
+    def wheel_touch(self):
+        """per tile [T] u32: bit car * 4 + wheel — the wheel rests on the tile (tile in w.tiles)"""
+        out = np.zeros(self.T, np.uint32)
+        self.L.orc_wheel_touch(self.h, _p(out))
+        return out
+
+    def set_event_order(self, mode):
+        """0 (default, what the kernels implement): Box2D's order of the sensor callbacks inside one Collide (mcr_oracle.cpp: the broadphase
+        model); 1: the events sorted by (tile, car, wheel); 2: Box2D's order as it would be if every contact were of one batch — descending
+        (lower proxy id, higher proxy id).  1 and 2 are for measurement only: where 0 and 1 give different rewards the order matters, where 0
+        and 2 do, the batch a contact was made in decides"""
+        self.L.orc_set_event_order(self.h, ctypes.c_int(int(mode)))
 
     def draw_list(self, agent=0, width=96, height=96, cap=2048):
         """Polygons of the frame render_view() would draw now, in draw order: list of (xy [n,2] f64 pixel space, rgb)."""

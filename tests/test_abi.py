@@ -117,6 +117,15 @@ def test_flags_now_checks_its_handle_before_any_hip_call(lib):
     assert L.mcr_flags_now(None, None) == -1 and b"null handle" in L.mcr_last_error()
 
 
+def test_tile_touch_reader_checks_its_arguments_before_any_hip_call(lib):
+    """mcr_debug_read_tile_touch (the sensor pass's per-tile wheel bits, tests/test_gpu_tile_kernel.py): declared, bound, NULL is MCR_ERR_ARG"""
+    L = lib.load()
+    assert "mcr_debug_read_tile_touch" in _declared() and "mcr_debug_read_tile_touch" in lib.SYMBOLS
+    out = (ctypes.c_uint32 * 16)()
+    assert L.mcr_debug_read_tile_touch(None, out) == -1 and b"null argument" in L.mcr_last_error()
+    assert L.mcr_debug_read_tile_touch(ctypes.c_void_p(16), None) == -1
+
+
 def test_obs_now_and_the_state_setters_check_their_arguments_before_any_hip_call(lib):
     """mcr_obs_now (the main raster on the state as it stands), mcr_set_wheels, mcr_set_env_state: declared, bound, and a NULL handle — for
     mcr_obs_now also a NULL buffer — is MCR_ERR_ARG on a machine without a device"""
