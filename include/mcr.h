@@ -287,6 +287,34 @@ int mcr_set_range_obs(mcr_env* h, float* d_ranges, const float* dirs /* [rays][2
 /* Recompute the tensor from the CURRENT state on `stream` (after mcr_set_bodies / mcr_set_state_blob, which do not; tests).  MCR_ERR_STATE
  * when no buffer is set.  Only enqueues: the ranges read no backward / on-grass flags. */
 int mcr_range_obs_now(mcr_env* h, void* stream);
+/* Grid observations: the ego-centred bird's-eye-view tensor driving policies are usually trained on — per car rows x cols bytes fixed to the
+ * hull, row 0 farthest ahead, column 0 leftmost, [B, N, rows, cols] u8.  A cell's byte says what lies under its CENTRE: MCR_GRID_ROAD (a
+ * road or kerb quad: a car standing there would not be driving_on_grass), MCR_GRID_FRESH (a tile this car has not visited: it still gets
+ * paid there), MCR_GRID_TAKEN (a tile another car has visited: the pay is dampened), MCR_GRID_CAR (a hull polygon of another car); bits 4..7
+ * are 0.  `cell` is the cell size in world units; (origin_row, origin_col) is where the hull's body origin sits, in cell units from the
+ * grid's top left corner — fractional or outside the grid if the caller wishes.  csrc/k_gridobs.h holds the definition and the arithmetic
+ * contract: "under" is the reference's own strict-interior predicate in IEEE f64 (a centre exactly on an edge is in nothing), and a host
+ * reproduces every bit (tests/grid_obs_ref.py).  Written on the device by a kernel of its own wherever the range finder is: after every
+ * mcr_reset, mcr_step (once per macro-step) and state restore / copy, on the caller's stream behind the step, with obs_enabled 0 or 1.  Rows
+ * of envs that are not active (never reset, frozen) are zeros; an env that re-spawned in the step shows the first state of its new episode
+ * (the tiles the cars spawned on are visited, as the reference's reset leaves them; every other tile cell is FRESH).  With one car MCR_GRID_TAKEN and MCR_GRID_CAR are never set. */
+#define MCR_GRID_MAX 64
+#define MCR_GRID_ROAD 1
+#define MCR_GRID_FRESH 2
+#define MCR_GRID_TAKEN 4
+#define MCR_GRID_CAR 8
+/* mcr_set_grid_obs' validation of the geometry without a handle (no GPU needed): MCR_OK, or MCR_ERR_ARG for rows or cols outside
+ * 1..MCR_GRID_MAX, a cell that is not finite or <= 0, or an origin that is not finite */
+int mcr_check_grid_obs(int rows, int cols, float cell, float origin_row, float origin_col);
+/* d_grid: the caller's device buffer [B, N, rows, cols] u8 at ANY byte alignment (a view is rows * cols bytes; odd products happen); NULL
+ * turns the feature off (the step path then does nothing new; the other arguments are ignored).  MCR_ERR_ARG for a NULL handle or what
+ * mcr_check_grid_obs refuses.  Allowed at any time; takes effect with the next mcr_reset / mcr_step / mcr_grid_obs_now.  No HIP call, no
+ * synchronisation. */
+int mcr_set_grid_obs(mcr_env* h, uint8_t* d_grid, int rows, int cols, float cell, float origin_row, float origin_col);
+/* Recompute the tensor from the CURRENT state on `stream` (after mcr_set_bodies / mcr_set_state_blob / mcr_set_env_state, which do not;
+ * tests).  MCR_ERR_STATE when no buffer is set.  Only enqueues: the grid reads the tiles' visit bits, which the step itself writes, and no
+ * backward / on-grass flags. */
+int mcr_grid_obs_now(mcr_env* h, void* stream);
 /* Car-contact observations: who touched whom in the step, and how hard — what Box2D's PostSolve would report, reduced on the device from the
  * car<->car manifold store every env keeps for warm starting (csrc/k_contactobs.h holds the definition and the arithmetic contract;
  * csrc/k_carcontacts.h the record layout).  Two tensors, written by a kernel of its own on the caller's stream behind every mcr_reset, every env

@@ -12,6 +12,8 @@ MT_WORDS = 625
 OBS_RGB, OBS_GRAY, OBS_STACK_MAX = 0, 1, 8
 REPEAT_MAX = 16                 # include/mcr.h: MCR_REPEAT_MAX
 RANGE_RAYS_MAX = 32             # include/mcr.h: MCR_RANGE_RAYS_MAX, rays per car of the range-finder observation
+GRID_MAX = 64                   # include/mcr.h: MCR_GRID_MAX, rows and columns per car of the grid observation
+GRID_ROAD, GRID_FRESH, GRID_TAKEN, GRID_CAR = 1, 2, 4, 8        # include/mcr.h: MCR_GRID_*, the bits of a grid cell
 DRV_PARAMS = 10                 # include/mcr.h: MCR_DRV_PARAMS, floats per parameter row of a scripted driver
 DRIVER_PARAM_NAMES = ("L1", "L2", "v_max", "K_s", "K_c", "K_g", "K_b", "offset", "gas_max", "brake_max")
 DRIVER_DEFAULTS = dict(zip(DRIVER_PARAM_NAMES, (4.0, 12.0, 70.0, 8.0, 20.0, 0.2, 0.1, 0.0, 1.0, 0.8)))    # include/mcr.h: MCR_DRV_DEFAULTS
@@ -112,6 +114,9 @@ SYMBOLS = {
     "mcr_check_range_obs": (_i, [_vp, _i, ctypes.c_float]),
     "mcr_set_range_obs": (_i, [_vp, _vp, _vp, _i, ctypes.c_float]),
     "mcr_range_obs_now": (_i, [_vp, _vp]),
+    "mcr_check_grid_obs": (_i, [_i, _i, ctypes.c_float, ctypes.c_float, ctypes.c_float]),
+    "mcr_set_grid_obs": (_i, [_vp, _vp, _i, _i, ctypes.c_float, ctypes.c_float, ctypes.c_float]),
+    "mcr_grid_obs_now": (_i, [_vp, _vp]),
     "mcr_set_contact_obs": (_i, [_vp, _vp, _vp]),
     "mcr_contact_obs_now": (_i, [_vp, _vp]),
     "mcr_contact_store_words": (_i, [_vp, _vp]),

@@ -170,3 +170,21 @@ __device__ inline bool point_in_road_poly_f64(const uint8_t* __restrict__ slot, 
   }
   return pos || neg;
 }
+// the same four f64 vertices, for a caller that tests many points against one polygon (k_gridobs.h): the expressions above, letter for letter
+__device__ inline void road_poly_vertices_f64(const uint8_t* __restrict__ slot, int t, int T, bool kerb, double (&X)[4], double (&Y)[4]) {
+  const double* TX = (const double*)(slot + MCR_OFF_TRACK_X); const double* TY = (const double*)(slot + MCR_OFF_TRACK_Y); const double* TB = (const double*)(slot + MCR_OFF_TRACK_B);
+  const double* TC = (const double*)(slot + MCR_OFF_TRACK_C); const double* TS = (const double*)(slot + MCR_OFF_TRACK_S);
+  const double TW = 40 / MCR_SCALE, TBW = 8 / MCR_SCALE;
+  const int u = t == 0 ? T - 1 : t - 1;
+  const double x1 = TX[t], y1 = TY[t], c1 = TC[t], s1 = TS[t], x2 = TX[u], y2 = TY[u], c2 = TC[u], s2 = TS[u];
+  if (!kerb) {
+    X[0] = x1 - TW * c1; Y[0] = y1 - TW * s1; X[1] = x1 + TW * c1; Y[1] = y1 + TW * s1;
+    X[2] = x2 + TW * c2; Y[2] = y2 + TW * s2; X[3] = x2 - TW * c2; Y[3] = y2 - TW * s2;
+  } else {
+    const double db = TB[u] - TB[t];
+    const double side = db > 0.0 ? 1.0 : (db < 0.0 ? -1.0 : 0.0);          // np.sign
+    const double w0 = side * TW, w1 = side * (TW + TBW);
+    X[0] = x1 + w0 * c1; Y[0] = y1 + w0 * s1; X[1] = x1 + w1 * c1; Y[1] = y1 + w1 * s1;
+    X[2] = x2 + w1 * c2; Y[2] = y2 + w1 * s2; X[3] = x2 + w0 * c2; Y[3] = y2 + w0 * s2;
+  }
+}

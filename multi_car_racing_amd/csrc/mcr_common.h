@@ -19,6 +19,11 @@
 #define MCR_DRV_PARAMS 10     // include/mcr.h: floats per parameter row of the scripted driver (k_driver.h)
 #define MCR_RC_PARAMS 8       // include/mcr.h: floats per racecraft row of the scripted driver (k_driver.h)
 #define MCR_RANGE_RAYS_MAX 32 // include/mcr.h: rays per car of the range-finder observation (k_rangeobs.h)
+#define MCR_GRID_MAX 64       // include/mcr.h: rows and columns per car of the grid observation (k_gridobs.h)
+#define MCR_GRID_ROAD 1       // ... and its bits (include/mcr.h)
+#define MCR_GRID_FRESH 2
+#define MCR_GRID_TAKEN 4
+#define MCR_GRID_CAR 8
 #define MCR_TILE_CAP 512
 #define MCR_QUAD_CAP 768
 

@@ -1,8 +1,9 @@
 // mcr_derived.hip — what the C ABI (include/mcr.h) DERIVES from the state a reset / a restore / a step ended with: the state vector (k_stateobs.h),
-// the range finder (k_rangeobs.h), scripted drivers (k_driver.h), level pools (k_pool.h).  Launched from mcr_hip.hip / mcr_state.hip: mcr_env.h.
+// the range finder (k_rangeobs.h), the grid (k_gridobs.h), scripted drivers (k_driver.h), level pools (k_pool.h).  Launched from mcr_hip.hip / mcr_state.hip: mcr_env.h.
 #include "mcr_env.h"
 #include "k_stateobs.h"
 #include "k_rangeobs.h"
+#include "k_gridobs.h"
 #include "k_driver.h"
 #include "k_pool.h"
 #include "k_levelstats.h"
@@ -36,8 +37,15 @@ void launch_contact_obs(mcr_env* h, hipStream_t st, bool accumulate) {
   if (!h->co.mask) return;
   run_contact_obs(st, h->P.cc_store, h->P.env, h->P.B, h->P.N, accumulate, h->co.mask, h->co.impulse);
 }
-// (the step's tail takes the first two only: step_one has launched the contact observation behind every sub-step, mcr_env.h)
-static void launch_state_range(mcr_env* h, hipStream_t st) { launch_state_obs(h, st); launch_range_obs(h, st); }
+// The grid observation (k_gridobs.h) goes wherever the range finder goes, behind it: a wavefront per view on the caller's stream.  It reads
+// tile_flags, which k_collide alone writes — inside the step, behind whose tail `st` waits; the k_flags launch a phase-word step leaves
+// pending writes CU_FLAGS only: no flush_flags.  Off (no buffer): one test.
+static void launch_grid_obs(mcr_env* h, hipStream_t st) {
+  if (!h->go.out) return;
+  hipLaunchKernelGGL(k_gridobs, dim3(h->P.B * h->P.N), dim3(64), 0, st, h->P, h->go);
+}
+// (the step's tail takes the first three only: step_one has launched the contact observation behind every sub-step, mcr_env.h)
+static void launch_state_range(mcr_env* h, hipStream_t st) { launch_state_obs(h, st); launch_range_obs(h, st); launch_grid_obs(h, st); }
 void launch_derived(mcr_env* h, hipStream_t st) { launch_state_range(h, st); launch_contact_obs(h, st, false); }
 
 // Level pools (k_pool.h): every env that installed its staged episode gets its next one from the pool.  Launched where launch_state_obs goes — on
@@ -116,6 +124,27 @@ extern "C" int mcr_range_obs_now(mcr_env* h, void* stream) {
   if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
   if (!h->ro.out) { g_err = "mcr_range_obs_now: no buffer set (mcr_set_range_obs)"; return MCR_ERR_STATE; }
   launch_range_obs(h, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+// The grid observation (k_gridobs.h).  mcr_set_grid_obs only validates and stores: no HIP call, no device needed for its argument checks.
+extern "C" int mcr_check_grid_obs(int rows, int cols, float cell, float origin_row, float origin_col) {
+  if (rows < 1 || rows > MCR_GRID_MAX || cols < 1 || cols > MCR_GRID_MAX) { g_err = "grid_obs: rows, cols 1..64"; return MCR_ERR_ARG; }
+  if (!std::isfinite(cell) || !(cell > 0.0f)) { g_err = "grid_obs: cell must be finite and > 0"; return MCR_ERR_ARG; }
+  if (!std::isfinite(origin_row) || !std::isfinite(origin_col)) { g_err = "grid_obs: the origin is not finite"; return MCR_ERR_ARG; }
+  return MCR_OK;
+}
+extern "C" int mcr_set_grid_obs(mcr_env* h, uint8_t* d_grid, int rows, int cols, float cell, float origin_row, float origin_col) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!d_grid) { h->go.out = nullptr; return MCR_OK; }
+  if (int rc = mcr_check_grid_obs(rows, cols, cell, origin_row, origin_col)) return rc;
+  h->go = McrGridObs{d_grid, rows, cols, cell, origin_row, origin_col};
+  return MCR_OK;
+}
+extern "C" int mcr_grid_obs_now(mcr_env* h, void* stream) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!h->go.out) { g_err = "mcr_grid_obs_now: no buffer set (mcr_set_grid_obs)"; return MCR_ERR_STATE; }
+  launch_grid_obs(h, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MCR_OK;
 }

@@ -72,6 +72,7 @@ struct mcr_env {
   McrParams flags_P{};          // ... the launch's parameters: ROLE_MAIN with that step's partition marks (its parity's part / dpart buffers), no touch verdicts
   McrStateObs so{nullptr, 0, 0, 0};   // mcr_set_state_obs: the low-dimensional observation (k_stateobs.h); out == nullptr: off
   McrRangeObs ro{};           // mcr_set_range_obs: the range-finder observation (k_rangeobs.h); out == nullptr: off
+  McrGridObs go{};            // mcr_set_grid_obs: the grid observation (k_gridobs.h); out == nullptr: off
   McrDriver drv{};            // mcr_set_drivers / mcr_set_racecraft: the scripted driver's parameter rows, racecraft rows and mask (k_driver.h) ...
   float* drv_out = nullptr;   // ... the registered [B][N][3] buffer (nullptr: no drivers, nothing is launched) ...
   uint32_t drv_mask = 0;      // ... and the cars it drives
@@ -90,13 +91,13 @@ bool stream_bound(const mcr_env* h, hipStream_t st);   // may a step launched on
 // ... and the one staging path (mcr_stage_episodes, the refill service): n rows of `src` into the free slots of envs ids[0..n) (null: 0..n-1)
 hipError_t stage_rows(mcr_env* h, const int32_t* ids, int n, const uint8_t* src, bool row_by_id, hipStream_t st, const char** what);
 // mcr_derived.hip: the launches behind a reset, a restore and a step, on the caller's stream; each returns at once where its feature is off
-void launch_derived(mcr_env* h, hipStream_t st);       // the outputs derived from the current state: state vector (k_stateobs.h), range finder (k_rangeobs.h), car contacts (k_contactobs.h, not accumulating)
+void launch_derived(mcr_env* h, hipStream_t st);       // the outputs derived from the current state: state vector (k_stateobs.h), range finder (k_rangeobs.h), grid (k_gridobs.h), car contacts (k_contactobs.h, not accumulating)
 // the car-contact observation (k_contactobs.h) from the store as it stands.  ONE place launches it for a step: step_one (mcr_hip.hip), behind
 // launch_step of EVERY sub-step with accumulate = sub > 0 — launch_step_tail, which runs behind the last sub-step only, leaves it alone
 // (a second, non-accumulating pass there would wipe the earlier sub-steps' sums).  Reset, restore and clone get it through launch_derived
 void launch_contact_obs(mcr_env* h, hipStream_t st, bool accumulate);
 void launch_pool_restage(mcr_env* h, hipStream_t st, int envs_per_group);   // level pools (k_pool.h): the next episode of every env that installed its staged one
-// behind the last sub-step of a macro-step: the state vector and the range finder (launch_derived's, less the car contacts), the per-level statistics (k_levelstats.h) from the step's done / truncated rows while
+// behind the last sub-step of a macro-step: the state vector, the range finder and the grid (launch_derived's, less the car contacts), the per-level statistics (k_levelstats.h) from the step's done / truncated rows while
 // `level` still names the episodes that ended, then the pool re-stage with MCR_POOL_GROUP
 void launch_step_tail(mcr_env* h, hipStream_t st, const uint8_t* d_done, const uint8_t* d_trunc);
 // mcr_refill.hip, mcr_debug.hip: ABI entry points only (mcr_destroy calls mcr_refill_stop first).

@@ -192,6 +192,15 @@ struct McrRangeObs {
   float dir[MCR_RANGE_RAYS_MAX][2];   // (ck, sk): ray k points along ck forward + sk right
 };
 
+// The grid observation (k_gridobs.h): launch argument of k_gridobs beside McrParams, kept in the handle (null `out`: the feature is off and
+// nothing is launched).  The geometry travels BY VALUE with every launch
+struct McrGridObs {
+  uint8_t* out;                 // [B][N][rows][cols] the caller's device buffer, any byte alignment
+  int32_t rows, cols;           // 1 .. MCR_GRID_MAX each
+  float cell;                   // cell size in world units, finite and > 0
+  float orow, ocol;             // the hull origin's position in cell units (row, column); fractional, possibly outside the grid
+};
+
 // The scripted driver (k_driver.h): launch argument of k_driver beside McrParams, kept in the handle.  The parameter rows travel BY VALUE with
 // every launch (320 + 260 bytes of kernel arguments): a later mcr_set_drivers / mcr_set_racecraft changes the launches enqueued after it and
 // nothing in flight.  k_driver<false> reads `prm` alone.

@@ -50,6 +50,17 @@ holds them (f64), `self.range_dirs` the float32 (cos, sin) table the kernel is g
 1 is `range_max`.  At a folded inner hairpin the inner border can lie inside the road: channel 0 is the first border segment a ray meets.
 After set_bodies() / set_state_blob() call refresh_ranges().
 
+Grid observation: `grid_obs=True` adds the ego-centred bird's-eye-view tensor driving policies are usually trained on, with `obs=True` or
+`obs=False` and beside every other observation: `self.grid`, a persistent uint8 device tensor [B, N, H, W], also info["grid"], that a kernel
+of its own (csrc/k_gridobs.h: the definition) rewrites wherever `self.state` is rewritten.  `grid_shape=(H, W)` (1..64 each) cells of
+`grid_cell` world units are fixed to the hull: row 0 is farthest ahead, column 0 leftmost, and the hull's body origin sits at
+`grid_origin=(row, col)` in cell units (None: (0.75 H, 0.5 W), a quarter from the bottom; fractional or outside the grid if you wish).  A
+byte says what lies under the cell's CENTRE: GRID_ROAD (1: road or kerb — a car there would not be driving_on_grass), GRID_FRESH (2: a tile
+this car has not visited yet, so it still pays), GRID_TAKEN (4: a tile another car has visited, so the pay is dampened), GRID_CAR (8: another
+car's hull).  "Under" is the reference's own strict-interior test in float64: a centre exactly on a tile's edge is in nothing.
+`self.grid_shape` = (N, H, W); grid_planes() gives the four bits as [B, N, 4, H, W] planes of 0/1.  With one car GRID_TAKEN and GRID_CAR are
+never set.  After set_bodies() / set_env_state() / set_state_blob() call refresh_grid().
+
 Car-contact observation: `contact_obs=True` (needs `num_agents >= 2` and `car_contacts=True`) reports the one thing that makes the simulator
 multi-car — who touched whom in the step, and how hard — with `obs=True` or `obs=False`: `self.contact_mask`, a persistent int32 device
 tensor [B, N], also info["contact_mask"], and `self.contact_impulse`, float64 [B, N, N], also info["contact_impulse"], that a kernel of its
@@ -197,6 +208,38 @@ def range_obs_table(range_rays=19, range_fov=math.pi, range_angles=None, range_m
     return angles, dirs, rmax
 
 
+def grid_obs_geometry(grid_shape=(32, 32), grid_cell=1.5, grid_origin=None):
+    """The geometry of the grid observation (module docstring), validated on the host: (H, W, cell, origin_row, origin_col), the last three as
+    the float32 values the kernel is given.  ValueError for a shape that is not two ints 1..64, a cell that is not finite or <= 0 (as
+    float32), or an origin that is not two finite numbers."""
+    try:
+        H, W = grid_shape
+    except (TypeError, ValueError):
+        raise ValueError(f"grid_shape must be (rows, cols), got {grid_shape!r}") from None
+    for v in (H, W):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= _lib.GRID_MAX:
+            raise ValueError(f"grid_shape must be two ints 1..{_lib.GRID_MAX}, got {grid_shape!r}")
+    H, W = int(H), int(W)
+    try:
+        with np.errstate(all="ignore"):
+            cell = np.float32(grid_cell)
+    except (TypeError, ValueError):
+        raise ValueError(f"grid_cell must be a number, got {grid_cell!r}") from None
+    if not np.isfinite(cell) or not cell > 0:
+        raise ValueError(f"grid_cell must be finite and > 0 as float32, got {grid_cell!r}")
+    if grid_origin is None:
+        grid_origin = (0.75 * H, 0.5 * W)
+    try:
+        orow, ocol = grid_origin
+        with np.errstate(all="ignore"):
+            orow, ocol = np.float32(orow), np.float32(ocol)
+    except (TypeError, ValueError):
+        raise ValueError(f"grid_origin must be (row, col) or None, got {grid_origin!r}") from None
+    if not (np.isfinite(orow) and np.isfinite(ocol)):
+        raise ValueError(f"grid_origin must be finite as float32, got {grid_origin!r}")
+    return H, W, float(cell), float(orow), float(ocol)
+
+
 class VecMultiCarRacing:
     def __init__(self, num_envs, num_agents=2, device=None, seed=0, env_offset=0, direction="CCW",
                  use_random_direction=True, backwards_flag=True, h_ratio=0.25, use_ego_color=False,
@@ -206,7 +249,7 @@ class VecMultiCarRacing:
                  state_obs=False, state_waypoints=6, state_stride=5, frame_skip=1, levels=None, level_seed=None, level_order="random",
                  level_stats=False,
                  scripted_agents=None, driver_params=None, racecraft=None, range_obs=False, range_rays=19, range_fov=math.pi, range_angles=None,
-                 range_max=100.0, contact_obs=False):
+                 range_max=100.0, contact_obs=False, grid_obs=False, grid_shape=(32, 32), grid_cell=1.5, grid_origin=None):
         # scripted drivers (module docstring): validated on the host before anything is created
         drv_mask = _drivers.driver_mask(num_agents, scripted_agents)
         drv_rows = _drivers.driver_params_array(num_agents, driver_params) if (drv_mask or driver_params is not None) else None
@@ -214,6 +257,7 @@ class VecMultiCarRacing:
         if rc_rows is not None and drv_rows is None:
             raise ValueError("racecraft needs scripted_agents or driver_params (there is no scripted driver to apply it to)")
         range_table = range_obs_table(range_rays, range_fov, range_angles, range_max) if range_obs else None
+        grid_geom = grid_obs_geometry(grid_shape, grid_cell, grid_origin) if grid_obs else None
         if contact_obs and (int(num_agents) < 2 or not car_contacts):
             raise ValueError("contact_obs=True needs num_agents >= 2 and car_contacts=True (there is no car<->car manifold store otherwise)")
         frame_skip = int(frame_skip)
@@ -344,6 +388,15 @@ class VecMultiCarRacing:
             self.range_shape = (self.N, 2, R)
             _lib.check(self.L.mcr_set_range_obs(self.h, ctypes.c_void_p(self.ranges.data_ptr()), _lib.ptr(self.range_dirs), R,
                                                 ctypes.c_float(self.range_max)), "mcr_set_range_obs")
+        # grid observation (include/mcr.h: mcr_set_grid_obs): [B, N, H, W] u8, rewritten where self.state is
+        self.grid = self.grid_shape = self.grid_cell = self.grid_origin = None
+        if grid_geom is not None:
+            gh, gw, self.grid_cell, orow, ocol = grid_geom
+            self.grid_origin = (orow, ocol)
+            self.grid = torch.zeros((self.B, self.N, gh, gw), dtype=torch.uint8, device=self.device)
+            self.grid_shape = (self.N, gh, gw)
+            _lib.check(self.L.mcr_set_grid_obs(self.h, ctypes.c_void_p(self.grid.data_ptr()), gh, gw, ctypes.c_float(self.grid_cell),
+                                               ctypes.c_float(orow), ctypes.c_float(ocol)), "mcr_set_grid_obs")
         # car-contact observation (include/mcr.h: mcr_set_contact_obs): [B, N] int32 and [B, N, N] f64, rewritten where self.state is and behind
         # every env step of a macro-step
         self.contact_mask = self.contact_impulse = None
@@ -718,6 +771,8 @@ class VecMultiCarRacing:
             info["state"] = self.state
         if self.ranges is not None:
             info["ranges"] = self.ranges
+        if self.grid is not None:
+            info["grid"] = self.grid
         if self.contact_mask is not None:
             info["contact_mask"] = self.contact_mask
             info["contact_impulse"] = self.contact_impulse
@@ -752,6 +807,23 @@ class VecMultiCarRacing:
         st = torch.cuda.current_stream(self.device)
         _lib.check(self.L.mcr_state_obs_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_state_obs_now")
         return self.state
+
+    def refresh_grid(self):
+        """Recompute `self.grid` from the CURRENT state on the current stream (include/mcr.h: mcr_grid_obs_now) — after set_bodies() /
+        set_env_state() / set_state_blob(), which leave it alone.  Returns the tensor."""
+        if self.grid is None:
+            raise _lib.McrError("created without grid_obs=True")
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_grid_obs_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_grid_obs_now")
+        return self.grid
+
+    def grid_planes(self, dtype=torch.float32):
+        """`self.grid` as four planes of 0 / 1 — GRID_ROAD, GRID_FRESH, GRID_TAKEN, GRID_CAR — [B, N, 4, H, W] of `dtype`: a torch expression on
+        the current stream, a new tensor every call."""
+        if self.grid is None:
+            raise _lib.McrError("created without grid_obs=True")
+        shifts = torch.arange(4, dtype=torch.uint8, device=self.grid.device).view(1, 1, 4, 1, 1)
+        return ((self.grid.unsqueeze(2) >> shifts) & 1).to(dtype)
 
     def refresh_ranges(self):
         """Recompute `self.ranges` from the CURRENT state on the current stream (include/mcr.h: mcr_range_obs_now) — after set_bodies() /
@@ -1014,7 +1086,7 @@ class VecMultiCarRacing:
     def clone_envs(self, src_ids, dst_ids, check=True):
         """Env dst_ids[i] becomes a copy of env src_ids[i] (a source may be listed many times): the state by one kernel (mcr_copy_states),
         then the rows of obs (the ring of a stacked format), reward, done and truncated, so that the clone is observationally equal at once;
-        `self.state` and `self.ranges` are rewritten, and with a level pool the `level` rows are copied.  Destinations must be distinct and disjoint from the sources — validated (ValueError) with check=True when
+        `self.state`, `self.ranges` and `self.grid` are rewritten, and with a level pool the `level` rows are copied.  Destinations must be distinct and disjoint from the sources — validated (ValueError) with check=True when
         the ids are sequences, the caller's obligation otherwise.  On the current stream; does not synchronise."""
         src, n, src_h = self._env_ids(src_ids, "src_ids")
         dst, m, dst_h = self._env_ids(dst_ids, "dst_ids", distinct=check)
