@@ -334,6 +334,36 @@ int mcr_grid_obs_now(mcr_env* h, void* stream);
 int mcr_set_contact_obs(mcr_env* h, int32_t* d_mask /* [B][N] */, double* d_impulse /* [B][N][N] */);
 /* Recompute both tensors, without accumulation, from the stores as they stand, on `stream`.  MCR_ERR_STATE when no buffers are set.  Only enqueues. */
 int mcr_contact_obs_now(mcr_env* h, void* stream);
+/* Early episode ending on the device: "no new tile for `patience` env steps" and "off the road for `offroad_patience` env steps" (csrc/k_endrules.h
+ * holds the definition; tests/end_rules_ref.py restates it as a wrapper round the oracle).  Three buffers the CALLER owns:
+ *   d_counters [B, 4] int32, 16-byte aligned: idle (env steps since the counted cars' sum of tile_visited_count last changed), offroad (env
+ *              steps in a row in which every — offroad_mode 0 — or some — offroad_mode 1 — counted car had no wheel on a tile), tvc_sum
+ *              (that sum), a reserved 0; both counts saturate at INT32_MAX and start at 0 with every episode
+ *   d_armed    [B] u8: bit 0 idle >= patience > 0, bit 1 offroad >= offroad_patience > 0, as of the last env step
+ *   d_reason   [B] u8: the armed word the env entered its last env step with — non-zero: that step ended the episode by these rules;
+ *              mcr_step_repeat ORs the sub-steps' words, like `done`.  An action-less mcr_step runs no pass and leaves the word of the last
+ *              env step taken with actions in place (VecMultiCarRacing.step(None) zeroes its tensor itself)
+ * A kernel of its own counts behind every env step taken WITH actions (the action-less step counts nothing and ends nothing), for the cars
+ * of agent_mask (bit a: car a), on the caller's stream.  An env that is armed ends its episode in the NEXT env step taken with actions, one
+ * step after its rule was first met, exactly as under the TimeLimit: truncated = !done, then done = 1 — so truncated = 0 says that the
+ * reference's own rules (or the TimeLimit) ended the episode in that very step —, end_reward added to every car's step reward (one f64 add
+ * behind the reference's arithmetic: reward and episode return stay reproducible bit for bit), and everything behind `done` as ever:
+ * auto-reset and re-spawn, parking inside a macro-step, episode statistics, terminal entries, level statistics.  With auto_reset 0 an env
+ * stepped past such an ending stays armed while its rule holds and reports done in every step until it is reset.  Envs that are not live
+ * (never reset, frozen, parked) keep their counters and are not armed.  mcr_reset / mcr_load_states / mcr_copy_states run the kernel's
+ * SETTLE pass: rows of envs in the first state of an episode start over, every other row keeps its counters and has its armed byte
+ * recomputed from them — restore the counter rows you saved with the states, in front of mcr_load_states, and the continuation is bit-identical.
+ * All three pointers NULL turn the feature off (nothing is launched, the step's kernels test one null pointer).  MCR_ERR_ARG: some but not
+ * all pointers NULL, a patience < 0, both patiences 0 with buffers given, offroad_mode outside {0, 1}, an end_reward that is not finite,
+ * counters not 16-byte aligned — all checked in front of the handle —, a NULL handle, an agent_mask without a car below num_agents.
+ * Allowed at any time; takes effect with the next mcr_reset / mcr_step.  No HIP call. */
+int mcr_set_end_rules(mcr_env* h, int patience, int offroad_patience, int offroad_mode, uint32_t agent_mask, double end_reward,
+                      int32_t* d_counters /* [B][4] */, uint8_t* d_armed /* [B] */, uint8_t* d_reason /* [B] */);
+/* the value checks of mcr_set_end_rules for a given num_agents; no handle, no GPU needed */
+int mcr_check_end_rules(int num_agents, int patience, int offroad_patience, int offroad_mode, uint32_t agent_mask, double end_reward);
+/* The SETTLE pass on `stream`: after writing d_counters yourself (a restore), or after mcr_set_state_blob / mcr_set_env_state, which leave
+ * the buffers alone.  MCR_ERR_STATE when no buffers are set.  Only enqueues. */
+int mcr_end_rules_now(mcr_env* h, void* stream);
 /* the manifold store's sizes in u32 words, per env and per record (either pointer may be NULL); returns the records kept per env (MCR_CC_MAX).
  * An env's store: word 0 the record count, 1 the overflow mark, 2-3 the joint order, then the records.  No handle, no GPU needed. */
 int mcr_contact_store_words(int32_t* words_per_env, int32_t* words_per_record);

@@ -119,6 +119,9 @@ SYMBOLS = {
     "mcr_grid_obs_now": (_i, [_vp, _vp]),
     "mcr_set_contact_obs": (_i, [_vp, _vp, _vp]),
     "mcr_contact_obs_now": (_i, [_vp, _vp]),
+    "mcr_set_end_rules": (_i, [_vp, _i, _i, _i, ctypes.c_uint32, _d, _vp, _vp, _vp]),
+    "mcr_check_end_rules": (_i, [_i, _i, _i, _i, ctypes.c_uint32, _d]),
+    "mcr_end_rules_now": (_i, [_vp, _vp]),
     "mcr_contact_store_words": (_i, [_vp, _vp]),
     "mcr_hull_polygons": (_i, [_vp, _vp]),
     "mcr_driver_defaults": (_i, [_vp]),

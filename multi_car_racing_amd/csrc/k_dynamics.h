@@ -1562,6 +1562,9 @@ __device__ __forceinline__ void dynamics_block(const McrParams& p, const int mod
     if (run && has_action) {
       int steps = es.steps + 1;
       if (p.max_steps > 0 && steps >= p.max_steps) { trunc = !done; done = true; }
+      // early ending (k_endrules.h): the env was armed behind the last env step — the episode ends here, like the TimeLimit's, and every car
+      // takes end_reward: one f64 add behind the reference's own arithmetic.  (Every lane of the env loads the same byte.)  Null: off
+      if (p.end_armed != nullptr && p.end_armed[env] != 0) { trunc = !done; done = true; step_reward = step_reward + p.end_reward; }
     }
     if (run && has_action) {   // episode statistics: what a RecordEpisodeStatistics wrapper would report at `done`
       epret = p.card[CD_EPRET * BN + ci] + step_reward;

@@ -1,5 +1,6 @@
 // mcr_derived.hip — what the C ABI (include/mcr.h) DERIVES from the state a reset / a restore / a step ended with: the state vector (k_stateobs.h),
-// the range finder (k_rangeobs.h), the grid (k_gridobs.h), scripted drivers (k_driver.h), level pools (k_pool.h).  Launched from mcr_hip.hip / mcr_state.hip: mcr_env.h.
+// the range finder (k_rangeobs.h), the grid (k_gridobs.h), scripted drivers (k_driver.h), level pools (k_pool.h), car contacts (k_contactobs.h),
+// early episode ending (k_endrules.h).  Launched from mcr_hip.hip / mcr_state.hip: mcr_env.h.
 #include "mcr_env.h"
 #include "k_stateobs.h"
 #include "k_rangeobs.h"
@@ -8,6 +9,7 @@
 #include "k_pool.h"
 #include "k_levelstats.h"
 #include "k_contactobs.h"
+#include "k_endrules.h"
 #include <cmath>
 
 // The low-dimensional observation of the state a reset / a step ended with (k_stateobs.h), a wavefront per env on the caller's stream: behind
@@ -46,7 +48,16 @@ static void launch_grid_obs(mcr_env* h, hipStream_t st) {
 }
 // (the step's tail takes the first three only: step_one has launched the contact observation behind every sub-step, mcr_env.h)
 static void launch_state_range(mcr_env* h, hipStream_t st) { launch_state_obs(h, st); launch_range_obs(h, st); launch_grid_obs(h, st); }
-void launch_derived(mcr_env* h, hipStream_t st) { launch_state_range(h, st); launch_contact_obs(h, st, false); }
+// Early episode ending (k_endrules.h): a lane per env on the caller's stream, where launch_contact_obs goes and for its reasons — behind
+// launch_step, outside the step's streams and outside a replayed step graph; it reads the env record, CU_TVC and CU_ONROAD, none of which
+// k_flags writes: no flush.  The next step's dynamics, whichever chain, loads armed[] behind this kernel (k_endrules.h: Ordering).  Off: one test.
+static void run_end_rules(mcr_env* h, hipStream_t st, int pass) {
+  if (!h->er.counters) return;
+  hipLaunchKernelGGL(k_endrules, dim3((h->P.B + MCR_ER_LANES - 1) / MCR_ER_LANES), dim3(MCR_ER_LANES), 0, st, (const McrEnvState*)h->P.env, (const uint32_t*)h->P.caru,
+                     h->P.B, h->P.N, pass, h->er);
+}
+void launch_end_rules(mcr_env* h, hipStream_t st, bool accumulate) { run_end_rules(h, st, accumulate ? MCR_ER_ADVANCE_ACCUMULATE : MCR_ER_ADVANCE); }
+void launch_derived(mcr_env* h, hipStream_t st) { launch_state_range(h, st); launch_contact_obs(h, st, false); run_end_rules(h, st, MCR_ER_SETTLE); }
 
 // Level pools (k_pool.h): every env that installed its staged episode gets its next one from the pool.  Launched where launch_state_obs goes — on
 // the caller's stream in front of and behind launch_reset and behind the LAST sub-step of a macro-step (a parked env re-spawns only there), whose
@@ -174,6 +185,43 @@ extern "C" int mcr_contact_obs_now(mcr_env* h, void* stream) {
   if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
   if (!h->co.mask) { g_err = "mcr_contact_obs_now: no buffers set (mcr_set_contact_obs)"; return MCR_ERR_STATE; }
   launch_contact_obs(h, (hipStream_t)stream, false);
+  HIPCHK(hipGetLastError());
+  return MCR_OK;
+}
+// Early episode ending (k_endrules.h).  mcr_set_end_rules only validates and stores: no HIP call; everything that does not need the handle's
+// num_agents is checked in front of the handle, so that it can be tested without a device (mcr_check_end_rules: all of it, for a given N).
+static int end_rules_values(int patience, int offroad_patience, int offroad_mode, double end_reward) {
+  if (patience < 0 || offroad_patience < 0) { g_err = "end_rules: patience and offroad_patience must be >= 0 (0: the rule is off)"; return MCR_ERR_ARG; }
+  if (patience == 0 && offroad_patience == 0) { g_err = "end_rules: both patiences are 0 (no rule to count for; pass null buffers to turn the feature off)"; return MCR_ERR_ARG; }
+  if (offroad_mode != 0 && offroad_mode != 1) { g_err = "end_rules: offroad_mode 0 (all counted cars off the road) or 1 (any)"; return MCR_ERR_ARG; }
+  if (!std::isfinite(end_reward)) { g_err = "end_rules: end_reward is not finite"; return MCR_ERR_ARG; }
+  return MCR_OK;
+}
+extern "C" int mcr_check_end_rules(int num_agents, int patience, int offroad_patience, int offroad_mode, uint32_t agent_mask, double end_reward) {
+  if (num_agents < 1 || num_agents > MCR_MAX_AGENTS) { g_err = "end_rules: num_agents 1..8"; return MCR_ERR_ARG; }
+  if (int rc = end_rules_values(patience, offroad_patience, offroad_mode, end_reward)) return rc;
+  if (!(agent_mask & ((1u << num_agents) - 1u))) { g_err = "end_rules: agent_mask names no car below num_agents"; return MCR_ERR_ARG; }
+  return MCR_OK;
+}
+extern "C" int mcr_set_end_rules(mcr_env* h, int patience, int offroad_patience, int offroad_mode, uint32_t agent_mask, double end_reward,
+                                 int32_t* d_counters, uint8_t* d_armed, uint8_t* d_reason) {
+  const int given = (d_counters != nullptr) + (d_armed != nullptr) + (d_reason != nullptr);
+  if (given != 0 && given != 3) { g_err = "mcr_set_end_rules: the counters, the armed and the reason buffer are set together or not at all"; return MCR_ERR_ARG; }
+  if (given) {
+    if (int rc = end_rules_values(patience, offroad_patience, offroad_mode, end_reward)) return rc;
+    if ((uintptr_t)d_counters & 15u) { g_err = "mcr_set_end_rules: the counters buffer must be 16-byte aligned (one row is one 16-byte access)"; return MCR_ERR_ARG; }
+  }
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!given) { h->er = McrEndRules{}; h->P.end_armed = nullptr; h->P.end_reward = 0.0; return MCR_OK; }
+  if (int rc = mcr_check_end_rules(h->P.N, patience, offroad_patience, offroad_mode, agent_mask, end_reward)) return rc;
+  h->er = McrEndRules{d_counters, d_armed, d_reason, patience, offroad_patience, offroad_mode, agent_mask & ((1u << h->P.N) - 1u)};
+  h->P.end_armed = d_armed; h->P.end_reward = end_reward;
+  return MCR_OK;
+}
+extern "C" int mcr_end_rules_now(mcr_env* h, void* stream) {
+  if (!h) { g_err = "null handle"; return MCR_ERR_ARG; }
+  if (!h->er.counters) { g_err = "mcr_end_rules_now: no buffers set (mcr_set_end_rules)"; return MCR_ERR_STATE; }
+  run_end_rules(h, (hipStream_t)stream, MCR_ER_SETTLE);
   HIPCHK(hipGetLastError());
   return MCR_OK;
 }

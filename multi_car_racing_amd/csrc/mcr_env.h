@@ -79,6 +79,7 @@ struct mcr_env {
   McrPool pool{nullptr, 0, 0, 0, 0, nullptr, nullptr, nullptr};   // mcr_set_episode_pool: the device stages the episodes itself (k_pool.h); blobs == nullptr: the host does
   McrLevelStats ls{nullptr, nullptr};   // mcr_set_level_stats: per-level episode statistics (k_levelstats.h); stats == nullptr: off
   McrContactObs co{nullptr, nullptr};   // mcr_set_contact_obs: the car-contact observation (k_contactobs.h); mask == nullptr: off
+  McrEndRules er{};           // mcr_set_end_rules: early episode ending (k_endrules.h); counters == nullptr: off (P.end_armed is null then, too)
 };
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -91,11 +92,14 @@ bool stream_bound(const mcr_env* h, hipStream_t st);   // may a step launched on
 // ... and the one staging path (mcr_stage_episodes, the refill service): n rows of `src` into the free slots of envs ids[0..n) (null: 0..n-1)
 hipError_t stage_rows(mcr_env* h, const int32_t* ids, int n, const uint8_t* src, bool row_by_id, hipStream_t st, const char** what);
 // mcr_derived.hip: the launches behind a reset, a restore and a step, on the caller's stream; each returns at once where its feature is off
-void launch_derived(mcr_env* h, hipStream_t st);       // the outputs derived from the current state: state vector (k_stateobs.h), range finder (k_rangeobs.h), grid (k_gridobs.h), car contacts (k_contactobs.h, not accumulating)
+void launch_derived(mcr_env* h, hipStream_t st);       // the outputs derived from the current state: state vector (k_stateobs.h), range finder (k_rangeobs.h), grid (k_gridobs.h), car contacts (k_contactobs.h, not accumulating), the end rules' settle pass (k_endrules.h)
 // the car-contact observation (k_contactobs.h) from the store as it stands.  ONE place launches it for a step: step_one (mcr_hip.hip), behind
 // launch_step of EVERY sub-step with accumulate = sub > 0 — launch_step_tail, which runs behind the last sub-step only, leaves it alone
 // (a second, non-accumulating pass there would wipe the earlier sub-steps' sums).  Reset, restore and clone get it through launch_derived
 void launch_contact_obs(mcr_env* h, hipStream_t st, bool accumulate);
+// early episode ending (k_endrules.h), the ADVANCE pass: the same ONE place, step_one, behind launch_step of every sub-step that has actions
+// (an action-less step counts nothing), accumulate = sub > 0 for the reason word.  The SETTLE pass goes with launch_derived.  Off: one test
+void launch_end_rules(mcr_env* h, hipStream_t st, bool accumulate);
 void launch_pool_restage(mcr_env* h, hipStream_t st, int envs_per_group);   // level pools (k_pool.h): the next episode of every env that installed its staged one
 // behind the last sub-step of a macro-step: the state vector, the range finder and the grid (launch_derived's, less the car contacts), the per-level statistics (k_levelstats.h) from the step's done / truncated rows while
 // `level` still names the episodes that ended, then the pool re-stage with MCR_POOL_GROUP

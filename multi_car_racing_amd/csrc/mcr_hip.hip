@@ -776,6 +776,7 @@ static int step_one(mcr_env* h, const float* d_actions, uint8_t* d_obs, double* 
   }
   if (!replay) launch_step(h, P, st, vf);
   launch_contact_obs(h, st, sub > 0);                                    // behind EVERY sub-step, the only place a step launches it (mcr_env.h); off: one test
+  if (d_actions) launch_end_rules(h, st, sub > 0);                       // early ending (k_endrules.h): counted behind every sub-step that has actions; off: one test
   if (last) launch_step_tail(h, st, d_done, d_trunc);                    // (a replayed step is a whole call: repeat == 1)
   HIPCHK(hipGetLastError());
   return MCR_OK;

@@ -164,6 +164,9 @@ struct McrParams {
   int32_t debug;                // McrDebugBit switches (0 in production)
   unsigned long long* dbg_stamps; // [2][dyn_blocks][8] phase clocks of k_dynamics (DEBUG_DYN_CLOCKS)
   double h_ratio;
+  // early episode ending (include/mcr.h: mcr_set_end_rules; k_endrules.h).  Null: off — the two hooks in k_dynamics.h's bookkeeping block are dead
+  const uint8_t* end_armed;     // [B] non-zero: k_endrules armed the env behind the last env step — this step ends its episode like the TimeLimit
+  double end_reward;            // ... and adds this to every car's step reward, one f64 add behind the reference's own arithmetic
 };
 
 // The observation format of the raster (include/mcr.h: mcr_set_obs_format): a launch argument of k_view beside McrParams, read by its GRAY
@@ -235,6 +238,17 @@ struct McrLevelStats {
 struct McrContactObs {
   int32_t* mask;                // [B][N] the caller's: bit j car j was touched, bit 8 with the own hull, bit 9 with an own wheel
   double* impulse;              // [B][N][N] the caller's: sum of the normal impulses between two cars
+};
+
+// Early episode ending (include/mcr.h: mcr_set_end_rules; k_endrules.h): launch argument of k_endrules, kept in the handle (null `counters`:
+// off, nothing is launched).  The three pointers are set together or not at all; McrParams::end_armed is the same `armed`
+struct McrEndRules {
+  int32_t* counters;            // [B][4] the caller's, 16-byte aligned: idle, offroad, tvc_sum, reserved 0
+  uint8_t* armed;               // [B] the caller's: bit 0 the idle rule is met, bit 1 the off-road rule — the next env step with actions ends the episode
+  uint8_t* reason;              // [B] the caller's: the armed word the env entered its last env step with (OR-ed over the sub-steps of a macro-step)
+  int32_t patience, offroad_patience;   // P, G; 0: that rule is off
+  int32_t any_mode;             // 0 "all": every counted car is off the road; 1 "any": some counted car is
+  uint32_t agent_mask;          // bit a: car a is counted
 };
 
 // status words (mapped host memory).  FATAL ones (give-up, verdict) make the next mcr_step return MCR_ERR_STATE; an OVERFLOW truncated a

@@ -33,12 +33,12 @@ def reduce_metrics(env_steps, elapsed_s, episodes=0.0, return_sum=0.0, group=Non
 class ShardedVecEnv:
     """This rank's slice of a job-wide batch of `total_envs` environments.  Env g (global index) behaves
     identically whatever the world size because its RNG streams are keyed by g (vec_env.py).  Every keyword of
-    VecMultiCarRacing passes through (`state_obs`, `state_waypoints`, `state_stride`, `range_obs`, `range_rays`, `range_fov`, `range_angles`, `range_max`, `contact_obs`, `grid_obs`, `grid_shape`, `grid_cell`, `grid_origin`, `frame_skip`, `levels`, `level_seed`, `level_order`
+    VecMultiCarRacing passes through (`state_obs`, `state_waypoints`, `state_stride`, `range_obs`, `range_rays`, `range_fov`, `range_angles`, `range_max`, `contact_obs`, `grid_obs`, `grid_shape`, `grid_cell`, `grid_origin`, `end_patience`, `end_offroad`, `end_offroad_mode`, `end_agents`, `end_reward`, `frame_skip`, `levels`, `level_seed`, `level_order`
     included: every rank makes the same pool, and an env's levels follow its GLOBAL index — under `level_order="weighted"` too, provided every
     rank calls `set_level_weights` with the same weights at the same steps; `level_stats`: each rank accumulates ITS slice's episodes in its own
     `level_stats` — a caller may all_reduce the tensor, after which the sums are no longer bit-identical across world sizes; `scripted_agents`, `driver_params`: the scripted
     driver is a pure function of an env's state, so a car drives the same whatever rank holds its env) and every attribute
-    and method of the slice is reachable here (`state`, `state_shape`, `ranges`, `range_shape`, `range_angles`, `range_dirs`, `refresh_ranges()`, `grid`, `grid_shape`, `grid_cell`, `grid_origin`, `refresh_grid()`, `grid_planes()`, `contact_mask`, `contact_impulse`, `refresh_contacts()`, `frame_skip`, `refresh_state()`, `actions`, `driver_params`,
+    and method of the slice is reachable here (`state`, `state_shape`, `ranges`, `range_shape`, `range_angles`, `range_dirs`, `refresh_ranges()`, `grid`, `grid_shape`, `grid_cell`, `grid_origin`, `refresh_grid()`, `grid_planes()`, `contact_mask`, `contact_impulse`, `refresh_contacts()`, `end_counters`, `end_reason`, `refresh_end_rules()`, `frame_skip`, `refresh_state()`, `actions`, `driver_params`,
     `expert_actions()`: this rank's rows)."""
 
     def __init__(self, total_envs, num_agents=2, seed=0, rank=0, world_size=1, device=None, **kw):

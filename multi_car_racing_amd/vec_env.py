@@ -75,6 +75,19 @@ one summed.  After reset() / reset_envs() / load_states() / clone_envs() a row s
 source's).  Where an env's store overflowed (status word 2: more than 24 touching fixture pairs) the outputs describe the 24 kept records.
 refresh_contacts() recomputes both tensors from the stores as they stand.
 
+Early episode ending: `end_patience=P` ends an episode when the counted cars (`end_agents`, default all; for a learner racing scripted cars
+pass the learners) have visited no new tile for P env steps, `end_offroad=G` when every counted car (`end_offroad_mode="all"`) or some counted
+car ("any") has had no wheel on a tile for G env steps in a row; 0 turns a rule off, both 0 (the default) the feature.  A kernel of its own
+(csrc/k_endrules.h: the definition; tests/end_rules_ref.py: the same as a wrapper round the oracle) counts behind every env step taken with
+actions — step(None) counts nothing and ends nothing — in `self.end_counters`, int32 [B, 4] = idle, offroad, tvc_sum, 0, which the CALLER owns
+(load_states() leaves them alone: save and restore the rows beside the states).  The episode ends in the env step AFTER the one in which a rule
+was first met — one step of lag, the price of leaving the step's kernels as they are — exactly as under the TimeLimit: `truncated = !done`,
+`done = 1`, then auto-reset, episode statistics, terminal observations, level statistics as ever; `end_reward` (default 0.0) is added to every
+car's reward of that step, one f64 add.  `self.end_reason` = info["end_reason"], uint8 [B]: 0, or why the step ended the episode by these
+rules (bit 0 idle, bit 1 off-road; OR-ed over a macro-step's env steps); `truncated = 0` beside it says that the reference's own rules or the
+TimeLimit ended the episode in the same env step; after step(None) it is 0.  With `auto_reset=False` an env stepped past such an ending reports `done` in every step
+while its rule holds, until reset_envs().  refresh_end_rules() after writing the counters yourself.
+
 Action repeat: `frame_skip=k` (1..16) makes step() one MACRO-step, gym's FrameSkip_k(TimeLimit(env)) per env with the auto-reset outside it
 (include/mcr.h: mcr_step_repeat): the same actions drive up to k env steps of every env, an env stops at the step that ends its episode,
 `reward` is the f64 sum of the env steps' rewards in order, `done` their OR, `truncated` the ending step's; `max_episode_steps`,
@@ -240,6 +253,39 @@ def grid_obs_geometry(grid_shape=(32, 32), grid_cell=1.5, grid_origin=None):
     return H, W, float(cell), float(orow), float(ocol)
 
 
+END_OFFROAD_MODE = {"all": 0, "any": 1}
+
+
+def end_rules_config(num_agents, end_patience, end_offroad, end_offroad_mode, end_agents, end_reward):
+    """The end-rule keywords of VecMultiCarRacing, validated on the host: None when both patiences are 0 (the feature is off, whatever the
+    other keywords say), else (patience, offroad patience, mode, counted cars as a sorted tuple, end_reward)."""
+    N = int(num_agents)
+    for name, v in (("end_patience", end_patience), ("end_offroad", end_offroad)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 2 ** 31 - 1:
+            raise ValueError(f"{name} must be an int in 0 .. 2^31 - 1 (0: off), got {v!r}")
+    if end_offroad_mode not in END_OFFROAD_MODE:
+        raise ValueError(f"end_offroad_mode must be one of {sorted(END_OFFROAD_MODE)}, got {end_offroad_mode!r}")
+    try:
+        reward = float(end_reward)
+    except (TypeError, ValueError):
+        raise ValueError(f"end_reward must be a finite float, got {end_reward!r}") from None
+    if not np.isfinite(reward):
+        raise ValueError(f"end_reward must be a finite float, got {end_reward!r}")
+    if end_agents is None:
+        cars = tuple(range(N))
+    else:
+        try:
+            cars = tuple(sorted(set(int(a) for a in end_agents)))
+            ok = all(isinstance(a, (int, np.integer)) and not isinstance(a, bool) for a in end_agents)
+        except (TypeError, ValueError):
+            raise ValueError(f"end_agents must be None or a sequence of car indices, got {end_agents!r}") from None
+        if not ok or not cars or cars[0] < 0 or cars[-1] >= N:
+            raise ValueError(f"end_agents must name at least one car in 0 .. {N - 1}, got {end_agents!r}")
+    if int(end_patience) == 0 and int(end_offroad) == 0:
+        return None
+    return int(end_patience), int(end_offroad), end_offroad_mode, cars, reward
+
+
 class VecMultiCarRacing:
     def __init__(self, num_envs, num_agents=2, device=None, seed=0, env_offset=0, direction="CCW",
                  use_random_direction=True, backwards_flag=True, h_ratio=0.25, use_ego_color=False,
@@ -249,7 +295,8 @@ class VecMultiCarRacing:
                  state_obs=False, state_waypoints=6, state_stride=5, frame_skip=1, levels=None, level_seed=None, level_order="random",
                  level_stats=False,
                  scripted_agents=None, driver_params=None, racecraft=None, range_obs=False, range_rays=19, range_fov=math.pi, range_angles=None,
-                 range_max=100.0, contact_obs=False, grid_obs=False, grid_shape=(32, 32), grid_cell=1.5, grid_origin=None):
+                 range_max=100.0, contact_obs=False, grid_obs=False, grid_shape=(32, 32), grid_cell=1.5, grid_origin=None,
+                 end_patience=0, end_offroad=0, end_offroad_mode="all", end_agents=None, end_reward=0.0):
         # scripted drivers (module docstring): validated on the host before anything is created
         drv_mask = _drivers.driver_mask(num_agents, scripted_agents)
         drv_rows = _drivers.driver_params_array(num_agents, driver_params) if (drv_mask or driver_params is not None) else None
@@ -260,6 +307,7 @@ class VecMultiCarRacing:
         grid_geom = grid_obs_geometry(grid_shape, grid_cell, grid_origin) if grid_obs else None
         if contact_obs and (int(num_agents) < 2 or not car_contacts):
             raise ValueError("contact_obs=True needs num_agents >= 2 and car_contacts=True (there is no car<->car manifold store otherwise)")
+        end_rules = end_rules_config(num_agents, end_patience, end_offroad, end_offroad_mode, end_agents, end_reward)
         frame_skip = int(frame_skip)
         if not 1 <= frame_skip <= _lib.REPEAT_MAX:
             raise ValueError(f"frame_skip must be 1..{_lib.REPEAT_MAX}, got {frame_skip}")
@@ -405,6 +453,16 @@ class VecMultiCarRacing:
             self.contact_impulse = torch.zeros((self.B, self.N, self.N), dtype=torch.float64, device=self.device)
             _lib.check(self.L.mcr_set_contact_obs(self.h, ctypes.c_void_p(self.contact_mask.data_ptr()),
                                                   ctypes.c_void_p(self.contact_impulse.data_ptr())), "mcr_set_contact_obs")
+        # early episode ending (include/mcr.h: mcr_set_end_rules): [B, 4] int32 counters the caller owns (idle, offroad, tvc_sum, 0), the armed
+        # bytes beside them and [B] u8 end_reason, all advanced by a kernel of its own behind every env step taken with actions
+        self.end_counters = self.end_armed = self.end_reason = None
+        self.end_patience, self.end_offroad, self.end_offroad_mode, self.end_agents, self.end_reward = end_rules[:5] if end_rules else (0, 0, "all", (), 0.0)
+        if end_rules:
+            self.end_counters = torch.zeros((self.B, 4), dtype=torch.int32, device=self.device)
+            self.end_armed = torch.zeros((self.B,), dtype=torch.uint8, device=self.device)
+            self.end_reason = torch.zeros((self.B,), dtype=torch.uint8, device=self.device)
+            self._set_end_rules()
+            torch.cuda.synchronize(self.device)                    # the zeros are in place whichever stream the first reset() runs on
         # scripted drivers (include/mcr.h: mcr_set_drivers): self.actions [B, N, 3] f32 is what step() is driven by when cars are scripted
         self.driver_params, self.scripted_agents = drv_rows, tuple(a for a in range(self.N) if drv_mask >> a & 1)
         self._drv_mask = drv_mask
@@ -453,6 +511,13 @@ class VecMultiCarRacing:
             if level_stats:
                 self._init_level_stats()
         _LIVE.add(self)
+
+    def _set_end_rules(self):
+        """hand the (possibly re-pointed: tests use row views) end-rule tensors to the handle"""
+        mask = sum(1 << a for a in self.end_agents)
+        _lib.check(self.L.mcr_set_end_rules(self.h, self.end_patience, self.end_offroad, END_OFFROAD_MODE[self.end_offroad_mode], ctypes.c_uint32(mask),
+                                            ctypes.c_double(self.end_reward), ctypes.c_void_p(self.end_counters.data_ptr()),
+                                            ctypes.c_void_p(self.end_armed.data_ptr()), ctypes.c_void_p(self.end_reason.data_ptr())), "mcr_set_end_rules")
 
     def _init_levels(self, levels, level_seed, level_order, seed):
         if isinstance(levels, np.ndarray):
@@ -695,6 +760,8 @@ class VecMultiCarRacing:
             # (k_install skips those): drain, poll and refill first, then every env installs a fresh episode
             self._settle_staging(st)
         _lib.check(self.L.mcr_reset(self.h, None, self._obs_ptr(), ctypes.c_void_p(st.cuda_stream)), "mcr_reset")
+        if self.end_reason is not None:
+            self.end_reason.zero_()   # (no step has ended anything yet; the counters and armed bytes are mcr_reset's settle pass)
         st.synchronize()
         self._has_reset = True
         self._poll_and_refill()
@@ -756,6 +823,8 @@ class VecMultiCarRacing:
         _lib.check(self.L.mcr_step_repeat(self.h, a_ptr, self.frame_skip, self._obs_ptr(),
                                           ctypes.c_void_p(self.reward.data_ptr()), ctypes.c_void_p(self.done.data_ptr()),
                                           ctypes.c_void_p(self.truncated.data_ptr()), ctypes.c_void_p(st.cuda_stream)), "mcr_step_repeat")
+        if actions is None and self.end_reason is not None:
+            self.end_reason.zero_()   # the action-less step ends nothing (and no k_endrules pass runs behind it: the word would be the last step's)
         self._step_idx += self.frame_skip     # env steps (only a step that was launched counts: a reported McrError leaves the accounting alone)
         if self._ring is not None:
             self.obs = self._window()
@@ -776,6 +845,8 @@ class VecMultiCarRacing:
         if self.contact_mask is not None:
             info["contact_mask"] = self.contact_mask
             info["contact_impulse"] = self.contact_impulse
+        if self.end_reason is not None:
+            info["end_reason"] = self.end_reason
         if self.level is not None:
             info["level"] = self.level
         if self.level_stats is not None:
@@ -843,6 +914,17 @@ class VecMultiCarRacing:
         st = torch.cuda.current_stream(self.device)
         _lib.check(self.L.mcr_contact_obs_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_contact_obs_now")
         return self.contact_mask, self.contact_impulse
+
+    def refresh_end_rules(self):
+        """Settle the end rules on the current stream (include/mcr.h: mcr_end_rules_now) after writing `self.end_counters` yourself — a restore
+        beside load_states() — or after set_state_blob() / set_env_state(): rows of envs in the first state of an episode start over, every other
+        row keeps its counters and has its armed byte recomputed from them.  reset(), reset_envs(), load_states() and clone_envs() do this by
+        themselves.  Returns (end_counters, end_reason); does not synchronise."""
+        if self.end_counters is None:
+            raise _lib.McrError("created without end_patience / end_offroad")
+        st = torch.cuda.current_stream(self.device)
+        _lib.check(self.L.mcr_end_rules_now(self.h, ctypes.c_void_p(st.cuda_stream)), "mcr_end_rules_now")
+        return self.end_counters, self.end_reason
 
     def refresh_flags(self):
         """Run the backward / on-grass scans on the CURRENT state on the current stream (include/mcr.h: mcr_flags_now) — after set_bodies() /
@@ -1042,7 +1124,10 @@ class VecMultiCarRacing:
         observation buffers are not redrawn (the next step draws them).  check=True validates on the host first — shape, ids given as a
         sequence, the header words of every row: ValueError, nothing changed — which synchronises, and raises McrError if the kernel
         refused a row.  check=False never synchronises and returns the int32 device counter [1] of refused rows (rows whose header is not
-        this handle's, ids out of range: those envs stay untouched)."""
+        this handle's, ids out of range: those envs stay untouched).
+        End rules (end_patience / end_offroad): the blob does not hold `self.end_counters` — they are the caller's.  Save the rows with the
+        states and write them back IN FRONT of this call, whose settle pass recomputes the armed bytes from them (or afterwards, followed by
+        refresh_end_rules()): the continuation is then bit-identical.  Left alone, a restored env goes on from whatever its row held."""
         if self.frame_stack > 1:
             raise ValueError("load_states with frame_stack > 1: a restored env has no frame history to fill its stack with")
         pitch = self.state_blob_pitch
@@ -1086,7 +1171,7 @@ class VecMultiCarRacing:
     def clone_envs(self, src_ids, dst_ids, check=True):
         """Env dst_ids[i] becomes a copy of env src_ids[i] (a source may be listed many times): the state by one kernel (mcr_copy_states),
         then the rows of obs (the ring of a stacked format), reward, done and truncated, so that the clone is observationally equal at once;
-        `self.state`, `self.ranges` and `self.grid` are rewritten, and with a level pool the `level` rows are copied.  Destinations must be distinct and disjoint from the sources — validated (ValueError) with check=True when
+        `self.state`, `self.ranges` and `self.grid` are rewritten, with a level pool the `level` rows are copied, and with end rules the `end_counters` / `end_reason` rows (the clone arms when its source does).  Destinations must be distinct and disjoint from the sources — validated (ValueError) with check=True when
         the ids are sequences, the caller's obligation otherwise.  On the current stream; does not synchronise."""
         src, n, src_h = self._env_ids(src_ids, "src_ids")
         dst, m, dst_h = self._env_ids(dst_ids, "dst_ids", distinct=check)
@@ -1097,9 +1182,12 @@ class VecMultiCarRacing:
         if check and src_h is not None and dst_h is not None and len(np.intersect1d(src_h, dst_h)):
             raise ValueError("dst_ids must be disjoint from src_ids")
         st = torch.cuda.current_stream(self.device)
+        s64, d64 = src.long(), dst.long()
+        if self.end_counters is not None and n:      # in front of mcr_copy_states, whose settle pass makes the clones' armed bytes from the copied rows
+            for t in (self.end_counters, self.end_reason):
+                t.index_copy_(0, d64, t.index_select(0, s64))
         _lib.check(self.L.mcr_copy_states(self.h, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()), n,
                                           ctypes.c_void_p(st.cuda_stream)), "mcr_copy_states")
-        s64, d64 = src.long(), dst.long()
         frames = self._ring if self._ring is not None else self.obs
         for t in (frames, self.reward, self.done, self.truncated, self.level):
             if t is not None and n:
