@@ -20,87 +20,42 @@ off median lies outside the parent's range the tool prints a FAIL line per confi
 A child that fails ends the whole measurement: nothing more is started on the device."""
 import argparse
 import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import costlib
+
 CONFIGS = {"obs0": (0, "random"), "obs1": (1, "random")}
 
 
 def worker(args):
-    tree = os.path.abspath(args.parent_tree) if args.worker == "parent" else ROOT
-    sys.path.insert(0, tree)
-    import torch
-    from multi_car_racing_amd.vec_env import VecMultiCarRacing
-    import multi_car_racing_amd
-    assert os.path.abspath(os.path.dirname(os.path.dirname(multi_car_racing_amd.__file__))) == tree, "the package did not come from the tree asked for"
-    assert torch.cuda.is_available(), "needs the MI355X: there is no CPU path to time"
-    B, N, K, W = args.envs, args.agents, args.steps, args.warmup
+    torch, VecMultiCarRacing = costlib.import_tree(args.parent_tree if args.worker == "parent" else costlib.ROOT)
+    B, N, K = args.envs, args.agents, args.steps
     obs, actions = CONFIGS[args.config]
-    kw = {"end_patience": args.patience} if args.worker == "on" else {}
+    on = {"end_patience": args.patience} if args.worker == "on" else {}
+    kw = dict(on)
     if args.siblings:                                   # (kernel traces) the other per-step derived-output kernels in the same trace: k_contactobs, k_stateobs
         kw.update(state_obs=True, contact_obs=True)
     env = VecMultiCarRacing(B, N, seed=0, obs=bool(obs), auto_reset=True, use_random_direction=True, streams=2, async_refill=True, **kw)
     env.reset()
-    dev = env.device
-    g = torch.Generator(device=dev); g.manual_seed(1234)
-    ACT_BLOCK = 16
-
-    def action_stream(e):
-        """the counter-based action stream from step 0, generated by handle `e` itself into buffers of its own, ACT_BLOCK steps at a time"""
-        act = [torch.empty((ACT_BLOCK, B, N, 3), dtype=torch.float32, device=dev) for _ in range(2)]
-        tstep = [0]
-
-        def nxt():
-            t = tstep[0]; tstep[0] += 1
-            blk, j = divmod(t, ACT_BLOCK)
-            if j == 0:
-                e.synth_actions(t, seed=1234, out=act[blk & 1], steps=ACT_BLOCK)
-            return act[blk & 1][j]
-        return nxt
-    next_actions = action_stream(env)
-    L = 1000                                            # bench.py's stagger: every env reset once, at a step of its own, before anything is timed
-    ids = torch.randperm(B, device=dev, generator=g)
-    for j in range(L):
-        env.step(next_actions())
-        msk = ((ids * L) // B == j).to(torch.uint8)
-        if bool(msk.any()):
-            env.reset_envs(msk)
-    for k in range(W):
-        env.step(next_actions())
-    env.wait_refills()
-    torch.cuda.synchronize()
-    LOOKAHEAD = 16; FENCE = LOOKAHEAD // 4
-    evs = [torch.cuda.Event(blocking=True) for _ in range(4)]
-    t0 = time.perf_counter()
-    for k in range(K):
-        env.step(next_actions())
-        if k % FENCE == FENCE - 1:
-            j = (k // FENCE) % 4
-            if k >= LOOKAHEAD:
-                while not evs[j].query():
-                    time.sleep(1e-4)
-            evs[j].record()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
+    next_actions = costlib.action_stream(env)
+    step = lambda: env.step(next_actions())
+    costlib.preroll(env, step, warmup=args.warmup)
+    elapsed = costlib.timed_steps(step, K)
     env.wait_refills()
     frozen = int(env.debug_counters()[3]); status = env.status_words()[:5].tolist()
     forced = None
     if getattr(env, "end_reason", None) is not None:    # (outside the timed region) forced ends per step over 64 more steps
         n = 0
         for k in range(64):
-            env.step(next_actions())
+            step()
             n += int((env.end_reason != 0).sum().item())
         forced = n / 64.0
     env.close()
     # (outside the timed region) the share of env-steps with a counted car on the road: a state_obs twin of the same setting, physics only,
     # from reset() through one TimeLimit and 256 sampled steps (the parent has the state vector too: its share is the "without" figure)
-    twin = VecMultiCarRacing(B, N, seed=0, obs=False, auto_reset=True, use_random_direction=True, streams=2, async_refill=True, state_obs=True,
-                             **({"end_patience": args.patience} if args.worker == "on" else {}))
+    twin = VecMultiCarRacing(B, N, seed=0, obs=False, auto_reset=True, use_random_direction=True, streams=2, async_refill=True, state_obs=True, **on)
     twin.reset()
-    twin_actions = action_stream(twin)                   # (the twin's own stream: `env` is closed)
+    twin_actions = costlib.action_stream(twin)          # (the twin's own stream, from step 0: `env` is closed)
     on_road = total = 0
     for k in range(1000 + 256):
         twin.step(twin_actions())
@@ -112,64 +67,67 @@ def worker(args):
                                       frozen_env_steps=frozen, status=status, forced_ends_per_step=forced, on_road_share=on_road / total)), flush=True)
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worker", choices=["parent", "off", "on"], default=None, help="run ONE measurement in this process")
-    ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit (omit: the `parent` runs are left out)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="obs0", help="the worker's configuration")
     ap.add_argument("--siblings", type=int, default=0, help="worker: 1 = also state_obs=True and contact_obs=True (k_stateobs and k_contactobs in the same kernel trace)")
     ap.add_argument("--patience", type=int, default=100, help="end_patience of the `on` runs")
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--agents", type=int, default=2)
-    ap.add_argument("--steps", type=int, default=1000)
-    ap.add_argument("--warmup", type=int, default=64)
-    ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--configs", default="obs0,obs1", help="configurations to measure")
-    ap.add_argument("--child-timeout", type=int, default=240)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    if args.worker:
-        return worker(args)
-    which = (["parent"] if args.parent_tree else []) + ["off", "on"]
-    runs = []
-    for cfg in args.configs.split(","):
-        for rep in range(args.repeats):
-            for w in which:                              # alternating: a drift of the machine hits all three alike
-                cmd = [sys.executable, os.path.abspath(__file__), "--worker", w, "--config", cfg, "--envs", str(args.envs), "--agents", str(args.agents),
-                       "--steps", str(args.steps), "--warmup", str(args.warmup), "--patience", str(args.patience)] + (["--parent-tree", args.parent_tree] if args.parent_tree else [])
-                pr = subprocess.run(["timeout", "-k", "10", str(args.child_timeout)] + cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-                line = [l for l in pr.stdout.splitlines() if l.startswith("RESULT ")]
-                if pr.returncode != 0 or not line:
-                    print(pr.stdout[-4000:])
-                    print(f"child {w} config={cfg} ended with {pr.returncode}: nothing more is started", flush=True)
-                    return 1
-                r = json.loads(line[-1][7:]); r["repeat"] = rep
-                runs.append(r); print(json.dumps(r), flush=True)
+    costlib.add_common_args(ap, child_timeout=240)
+    return ap
+
+
+def summarise(runs, which, configs):
     summary = {}
-    for cfg in args.configs.split(","):
+    for cfg in configs:
         for w in which:
-            v = sorted(r["env_steps_per_s"] for r in runs if r["config"] == cfg and r["which"] == w)
-            summary[f"{cfg} {w}"] = dict(runs=[round(x) for x in v], median=round(v[len(v) // 2]), spread_pct=round(100.0 * (v[-1] - v[0]) / v[len(v) // 2], 2))
+            summary[f"{cfg} {w}"] = costlib.median_triple(r["env_steps_per_s"] for r in runs if r["config"] == cfg and r["which"] == w)
         off = summary[f"{cfg} off"]["median"]
         summary[f"{cfg} on vs off pct"] = round(100.0 * (summary[f"{cfg} on"]["median"] - off) / off, 2)
-        if args.parent_tree:
+        if "parent" in which:
             par = summary[f"{cfg} parent"]
             summary[f"{cfg} off vs parent pct"] = round(100.0 * (off - par["median"]) / par["median"], 2)
-            summary[f"{cfg} off inside parent range"] = bool(par["runs"][0] <= off <= par["runs"][-1])      # THE off-path condition: the parent's own run-to-run range
+            # THE off-path condition, TWO-sided: the parent's own run-to-run range, slowest <= median <= fastest (range_obs_cost.py's and
+            # grid_obs_cost.py's `within_parent_spread` is one-sided: no slower than the parent's slowest run)
+            summary[f"{cfg} off inside parent range"] = bool(par["runs"][0] <= off <= par["runs"][-1])
         for w in which:
             v = sorted(r["on_road_share"] for r in runs if r["config"] == cfg and r["which"] == w)
             summary[f"{cfg} {w} on-road share"] = round(v[len(v) // 2], 4)
-    out = dict(steps=args.steps, envs=args.envs, agents=args.agents, runs=runs, summary=summary)
-    print("SUMMARY " + json.dumps(summary, indent=1), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
-    outside = [cfg for cfg in args.configs.split(",") if summary.get(f"{cfg} off inside parent range") is False]
-    for cfg in outside:
-        par = summary[f"{cfg} parent"]["runs"]
-        off = summary[f"{cfg} off"]["median"]
-        print(f"FAIL {cfg}: the off median {off} lies {'below' if off < par[0] else 'above'} the parent's own range {par[0]} .. {par[-1]}", flush=True)
-    return 2 if outside else 0
+    return summary
+
+
+def verdict(summary, configs):
+    """(exit code, FAIL lines): 2 and a line per configuration whose off median lies outside the parent's range, else 0 and none"""
+    lines = []
+    for cfg in configs:
+        if summary.get(f"{cfg} off inside parent range") is False:
+            par = summary[f"{cfg} parent"]["runs"]
+            off = summary[f"{cfg} off"]["median"]
+            lines.append(f"FAIL {cfg}: the off median {off} lies {'below' if off < par[0] else 'above'} the parent's own range {par[0]} .. {par[-1]}")
+    return (2 if lines else 0), lines
+
+
+def main():
+    args = parser().parse_args()
+    if args.worker:
+        return worker(args)
+    which = (["parent"] if args.parent_tree else []) + ["off", "on"]
+    configs = args.configs.split(",")
+    tail = ["--envs", str(args.envs), "--agents", str(args.agents), "--steps", str(args.steps), "--warmup", str(args.warmup)] \
+        + (["--parent-tree", args.parent_tree] if args.parent_tree else [])
+    # alternating: a drift of the machine hits all three alike
+    jobs = [(f"{w} config={cfg}", ["--worker", w, "--config", cfg, "--patience", str(args.patience)] + tail, rep)
+            for cfg in configs for rep in range(args.repeats) for w in which]
+    runs = costlib.run_children(__file__, jobs, args.child_timeout)
+    if runs is None:
+        return 1
+    summary = summarise(runs, which, configs)
+    costlib.finish(dict(steps=args.steps, envs=args.envs, agents=args.agents, runs=runs, summary=summary), summary, args.out)
+    code, lines = verdict(summary, configs)
+    for line in lines:
+        print(line, flush=True)
+    return code
 
 
 if __name__ == "__main__":

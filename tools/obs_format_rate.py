@@ -11,12 +11,9 @@ env_steps_per_s over the timed steps, raster_us: the main raster launch's dispat
 """
 import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import costlib
 
 
 def luma(torch, rgb):
@@ -25,26 +22,18 @@ def luma(torch, rgb):
 
 
 def run_leg(leg, B, N, K, W, stagger):
-    import torch
-    from multi_car_racing_amd.vec_env import VecMultiCarRacing
+    torch, VecMultiCarRacing = costlib.import_tree(costlib.ROOT)
     fmt, k = {"a": ("rgb", 1), "b": ("rgb", 1), "c": ("gray", 1), "d": ("gray", 4)}[leg]
     env = VecMultiCarRacing(B, N, seed=0, use_random_direction=True, obs_format=fmt, frame_stack=k)
     env.reset()
-    dev = env.device
-    ACT_BLOCK = 16
-    act = [torch.empty((ACT_BLOCK, B, N, 3), dtype=torch.float32, device=dev) for _ in range(2)]
-    tstep = [0]
-
-    def next_actions():
-        t = tstep[0]; tstep[0] += 1
-        blk, j = divmod(t, ACT_BLOCK)
-        if j == 0:
-            env.synth_actions(t, seed=0, out=act[blk & 1], steps=ACT_BLOCK)
-        return act[blk & 1][j]
-
+    next_actions = costlib.action_stream(env, seed=0)
     stack = [None]
+    TIME_EVERY = 8
+    timed = [None]                                       # the timed region's step counter (None in front of it: no launch is timed)
 
     def step():
+        if timed[0] is not None:
+            env.timing(4 if timed[0] % TIME_EVERY == 0 else 0); timed[0] += 1
         obs, rew, done, info = env.step(next_actions())
         if leg == "b":                                   # what a user does with the RGB frames to get gym's gray FrameStack(4)
             y = luma(torch, obs).unsqueeze(2)
@@ -52,35 +41,15 @@ def run_leg(leg, B, N, K, W, stagger):
                 stack[0] = y.repeat(1, 1, 4, 1, 1)
             s = torch.cat([stack[0][:, :, 1:], y], 2)
             stack[0] = torch.where(done.bool()[:, None, None, None, None], y.expand_as(s), s)
-        return obs
 
-    g = torch.Generator(device=dev); g.manual_seed(1234)
-    if stagger:                                          # spread the TimeLimit phases (bench.py --stagger 1)
-        L = 1000
-        ids = torch.randperm(B, device=dev, generator=g)
-        for j in range(L):
-            step()
-            msk = ((ids * L) // B == j).to(torch.uint8)
-            if bool(msk.any()):
-                env.reset_envs(msk)
-                stack[0] = None
-    for _ in range(W):
-        step()
-    env.wait_refills()
+    def drop_stack():
+        stack[0] = None
+    # spread the TimeLimit phases (bench.py --stagger 1)
+    costlib.preroll(env, step, stagger_steps=1000 if stagger else 0, warmup=W, after_reset=drop_stack)
     env.timing(0)
-    torch.cuda.synchronize()
-    LOOKAHEAD, FENCE, TIME_EVERY = 16, 4, 8
-    evs = [torch.cuda.Event(blocking=True) for _ in range(4)]
-    t0 = time.perf_counter()
-    for i in range(K):
-        env.timing(4 if i % TIME_EVERY == 0 else 0)
-        step()
-        if i % FENCE == FENCE - 1:
-            j = (i // FENCE) % 4
-            if i >= LOOKAHEAD:
-                while not evs[j].query():
-                    time.sleep(1e-4)
-            evs[j].record()
+    timed[0] = 0
+    t0 = time.perf_counter()                             # the tool's own clock: its time includes the wait_refills() behind the loop
+    costlib.fenced_steps(step, K)
     torch.cuda.synchronize()
     env.wait_refills()
     elapsed = time.perf_counter() - t0
@@ -94,15 +63,16 @@ def run_leg(leg, B, N, K, W, stagger):
             "obs_bytes_per_view": 96 * 96 * 3 if leg in "ab" else 96 * 96 * (2 * 4 if leg == "d" else 1)}
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--agents", type=int, default=2)
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--warmup", type=int, default=200)
+    costlib.add_common_args(ap, steps=2000, warmup=200, child_timeout=None)
     ap.add_argument("--stagger", type=int, default=1)
     ap.add_argument("--legs", default="abcd")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = parser().parse_args()
     for leg in args.legs:
         print(json.dumps(run_leg(leg, args.envs, args.agents, args.steps, args.warmup, args.stagger)), flush=True)
 
