@@ -450,6 +450,10 @@ void world_solve(Env& E, f32 h, int velIters, int posIters) {
     }
   }
   for (int c = 0; c < N; ++c) for (int q = 0; q < 4; ++q) joint_init(E.cars[c], jord[c][q]);
+  for (int c = 0; c < N; ++c) for (int q = 0; q < 4; ++q) {      // orc_dynamics_coverage: the limit states the velocity sweeps run with
+    const int ls = E.cars[c].j[q].limitState; long long* dy = E.dyn_last(c);
+    dy[DY_LIM_J0 + q] = ls; dy[DY_LIM_INACTIVE + ls] += 1;
+  }
   // diagnostics (orc_debug_fixed_point): the sweep is a pure function of (velocities, accumulated impulses) — masses, anchors, motor speeds
   // and limit states are constants of the step —, so once a sweep changes none of them no later sweep does.  Per car without contacts:
   // the first sweep that is the identity (velIters: none was).
@@ -468,7 +472,7 @@ void world_solve(Env& E, f32 h, int velIters, int posIters) {
   for (int it = 0; it < velIters; ++it) {
     for (int c = 0; c < N; ++c) {
       Snap before; if (track_fix && fix_at[c] == velIters) before = snap_of(E.cars[c]);
-      for (int q = 0; q < 4; ++q) joint_solve_velocity(E.cars[c], jord[c][q], h);
+      for (int q = 0; q < 4; ++q) joint_solve_velocity(E.cars[c], jord[c][q], h, E.dyn_last(c));
       if (track_fix && fix_at[c] == velIters) { const Snap after = snap_of(E.cars[c]); if (memcmp(&before, &after, sizeof(Snap)) == 0) fix_at[c] = it; }
     }
     for (int oi : cord) contact_solve_velocity(vcs[oi], E.cov);
@@ -488,9 +492,9 @@ void world_solve(Env& E, f32 h, int velIters, int posIters) {
   for (int c = 0; c < N; ++c) for (int k = 0; k < 5; ++k) {
     Body& b = E.cars[c].b[k];
     V2 tr = h * b.v;
-    if (dot(tr, tr) > b2_maxTranslationSquared) { f32 ratio = b2_maxTranslation / length(tr); b.v = ratio * b.v; E.cov[COV_TRANSLATION_CLAMP] += 1; }
+    if (dot(tr, tr) > b2_maxTranslationSquared) { f32 ratio = b2_maxTranslation / length(tr); b.v = ratio * b.v; E.cov[COV_TRANSLATION_CLAMP] += 1; E.dyn_last(c)[DY_TRANSLATION_CLAMP] += 1; }
     f32 rot = h * b.w;
-    if (rot * rot > b2_maxRotationSquared) { f32 ratio = b2_maxRotation / fabsf(rot); b.w *= ratio; E.cov[COV_ROTATION_CLAMP] += 1; }
+    if (rot * rot > b2_maxRotationSquared) { f32 ratio = b2_maxRotation / fabsf(rot); b.w *= ratio; E.cov[COV_ROTATION_CLAMP] += 1; E.dyn_last(c)[DY_ROTATION_CLAMP] += 1; }
     b.c = b.c + h * b.v; b.a += h * b.w;
   }
   // position iterations + sleep, per island
@@ -500,6 +504,9 @@ void world_solve(Env& E, f32 h, int velIters, int posIters) {
     for (const CarContact& C : S.cur) has_contact = has_contact || isl[C.carA] == root;
     for (int it = 0; it < posIters; ++it) {
       sweeps = it + 1;
+      f32 before[8][15];                                       // orc_dynamics_coverage: did a failing sweep move the car at all?
+      auto poses_of = [](const Car& car, f32* o) { for (int k = 0; k < 5; ++k) { o[3 * k] = car.b[k].c.x; o[3 * k + 1] = car.b[k].c.y; o[3 * k + 2] = car.b[k].a; } };
+      for (int c = 0; c < N; ++c) if (isl[c] == root) poses_of(E.cars[c], before[c]);
       E.dbg_pos_iters = std::max(E.dbg_pos_iters, it + 1);
       f32 minSep = 0.0f;
       for (int oi : cord) { const CarContact& C = S.cur[oi]; if (isl[C.carA] != root) continue;
@@ -509,7 +516,12 @@ void world_solve(Env& E, f32 h, int velIters, int posIters) {
       for (int c = 0; c < N; ++c) if (isl[c] == root)
         for (int q = 0; q < 4; ++q) { bool ok = joint_solve_position(E.cars[c], jord[c][q]); jointsOkay = jointsOkay && ok; }
       if (contactsOkay && jointsOkay) { positionSolved = true; break; }
+      for (int c = 0; c < N; ++c) if (isl[c] == root && E.dyn_last(c)[DY_FIXED_AT] == 0) {
+        f32 after[15]; poses_of(E.cars[c], after);
+        if (memcmp(before[c], after, sizeof(after)) == 0) E.dyn_last(c)[DY_FIXED_AT] = it + 1;
+      }
     }
+    for (int c = 0; c < N; ++c) if (isl[c] == root) { E.dyn_last(c)[DY_SWEEPS] = sweeps; E.dyn_last(c)[DY_SOLVED] = positionSolved ? 1 : 0; }
     if (has_contact && sweeps == posIters) E.cov[COV_POS_SWEEPS_ALL] += 1;
     f32 minSleepTime = 3.402823466e+38f;
     const f32 linTolSqr = b2_linearSleepTolerance * b2_linearSleepTolerance;
@@ -520,6 +532,8 @@ void world_solve(Env& E, f32 h, int velIters, int posIters) {
       if (b.w * b.w > angTolSqr || dot(b.v, b.v) > linTolSqr) { b.sleepTime = 0.0f; minSleepTime = 0.0f; }
       else { b.sleepTime += h; minSleepTime = std::min(minSleepTime, b.sleepTime); }
     }
+    if (minSleepTime >= b2_timeToSleep && positionSolved)
+      for (int c = 0; c < N; ++c) if (isl[c] == root) E.dyn_last(c)[DY_SLEPT] = 1;
     if (minSleepTime >= b2_timeToSleep && positionSolved)
       for (int c = 0; c < N; ++c) if (isl[c] == root) for (int k = 0; k < 5; ++k) {
         Body& b = E.cars[c].b[k]; b.awake = false; b.sleepTime = 0.0f; b.v = v2(0, 0); b.w = 0.0f;
@@ -568,6 +582,14 @@ extern "C" int orc_contact_coverage(void* h, long long* out, int reset) {
   Env& E = *(Env*)h;
   for (int i = 0; i < ORC_COV_ROWS; ++i) { out[i] = E.cov[i]; if (reset) E.cov[i] = 0; }
   return COV_ROWS;
+}
+// What the per-car dynamics reached (mcr_oracle.cpp: DY_*): out[N][2][DY_ROWS] — each car's rows of the last step, then their totals since the
+// counters were last reset (reset != 0 clears the totals after the read).  Returns DY_ROWS.
+extern "C" int orc_dynamics_coverage(void* h, long long* out, int reset) {
+  Env& E = *(Env*)h;
+  for (size_t i = 0; i < E.dyn.size(); ++i) out[i] = E.dyn[i];
+  if (reset) for (int c = 0; c < E.N; ++c) std::fill(E.dyn_last(c) + DY_ROWS, E.dyn_last(c) + 2 * DY_ROWS, 0LL);
+  return DY_ROWS;
 }
 // 0 (default): no cap.  cap > 0: THE DROP RULE of the header, the product's MCR_CC_MAX
 extern "C" void orc_set_contact_cap(void* h, int cap) { ((Env*)h)->contact_cap = cap < 0 ? 0 : cap; }

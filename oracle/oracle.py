@@ -8,6 +8,10 @@ Python side of the CPU oracle:
   * `OracleEnv`: ctypes binding of oracle/_build/libmcr_oracle.so (physics + tile contacts +
     bookkeeping + raster restatement; see mcr_oracle.cpp header for what is / is not pinned).
 
+  * `OracleEnv.dynamics_coverage()` (orc_dynamics_coverage): what the per-car dynamics of the last step reached, per car, and the totals —
+    position sweeps, fixed points, limit states, solver branches, clamps, the sleep rule, every branch of the tyre model (DYNAMICS_ROWS).
+  * `OracleEnv.set_wheels()` (orc_set_wheels): omega and phase of a car's wheels and nothing else, the product's mcr_set_wheels.
+
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 """
 import ctypes, math, os, subprocess
@@ -206,6 +210,14 @@ def new_episode(N, track_rng, global_rng, direction="CCW", use_random_direction=
 COVERAGE_ROWS = ("max_manifolds", "block_both", "block_x1", "block_x2", "block_neither", "block_none", "ill_conditioned", "face_a", "face_b",
                  "flipped", "pos_sweeps_all", "id_match", "id_miss", "translation_clamp", "rotation_clamp", "max_island_cars", "max_candidates",
                  "dropped", "ill_then_well")
+# orc_dynamics_coverage's rows (mcr_oracle.cpp: DY_*).  "sweeps", "fixed_at" and "lim_j0".."lim_j3" are values of a step — position sweeps run,
+# 1-based index of the first failing sweep that moved none of the car's 15 position values (0: none), the limit state each joint's velocity
+# sweeps ran with (0 inactive, 1 lower, 2 upper, 3 equal) —; in the totals "sweeps" is summed and the others count the steps where they were not 0.
+# Every other row counts events; a tyre row exists once per surface, "<row>_road" and "<row>_grass".
+TYRE_ROWS = ("brake_lock", "brake_clamped", "brake_unclamped", "brake_omega0", "gas_clamped", "gas_falling", "wheel", "over_limit", "over_2limit",
+             "force_zero", "motor_capped", "motor_proportional", "steer_equal")
+DYNAMICS_ROWS = ("sweeps", "solved", "fixed_at", "lim_j0", "lim_j1", "lim_j2", "lim_j3", "lim_inactive", "lim_lower", "lim_upper", "lim_equal",
+                 "solve33", "reduce22", "translation_clamp", "rotation_clamp", "slept") + tuple(f"{r}_{s}" for r in TYRE_ROWS for s in ("road", "grass"))
 _lib = None
 
 
@@ -236,6 +248,10 @@ def lib():
         L.orc_get_car_contacts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.orc_contact_coverage.restype = ctypes.c_int
         L.orc_contact_coverage.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.orc_dynamics_coverage.restype = ctypes.c_int
+        L.orc_dynamics_coverage.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.orc_set_wheels.restype = None
+        L.orc_set_wheels.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.orc_set_contact_cap.restype = None
         L.orc_set_contact_cap.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _lib = L
@@ -554,6 +570,20 @@ class OracleEnv:
         n = self.L.orc_contact_coverage(self.h, _p(out), int(bool(reset)))
         assert n == len(COVERAGE_ROWS), (n, len(COVERAGE_ROWS))
         return {k: int(out[i]) for i, k in enumerate(COVERAGE_ROWS)}
+
+    def dynamics_coverage(self, reset=False):
+        """what the per-car dynamics reached: (last, total) — two dicts row name -> int64 array [N], the rows of the last step per car and
+        their totals since the counters were last reset (DYNAMICS_ROWS)"""
+        out = np.zeros((self.N, 2, len(DYNAMICS_ROWS)), np.int64)
+        n = self.L.orc_dynamics_coverage(self.h, _p(out), int(bool(reset)))
+        assert n == len(DYNAMICS_ROWS), (n, len(DYNAMICS_ROWS))
+        return tuple({k: out[:, part, i].copy() for i, k in enumerate(DYNAMICS_ROWS)} for part in (0, 1))
+
+    def set_wheels(self, car, omega, phase=(0, 0, 0, 0)):
+        """omega and phase of a car's four wheels and nothing else (the product's mcr_set_wheels)"""
+        om = np.ascontiguousarray(omega, dtype=np.float64); ph = np.ascontiguousarray(phase, dtype=np.float64)
+        assert om.shape == (4,) and ph.shape == (4,)
+        self.L.orc_set_wheels(self.h, ctypes.c_int(car), _p(om), _p(ph))
 
     def set_contact_cap(self, cap):
         """0 (default): no cap on the touching car<->car pairs of a step.  cap > 0: the product's manifold store (MCR_CC_MAX) — the first
